@@ -9,9 +9,11 @@ value = algorithmic GB/s = (4 * 8 * N * L * B bytes per step, i.e. each transfor
 once) * n_gpus / step time.  Multi-GPU: the batch of independent polynomials is sharded, B per GPU (weak
 scaling), no collective on the data path; the barrier + max-over-ranks timing uses torch.distributed (RCCL).
 
-Extra fields on the same JSON line: `roofline` (dominant kernel, live hipEvent timing), `cpu_baseline`
-(reference compiled from its own sources, or the oracle port, timed on this host) and `evalmult` (CKKS
-EvalMult + HYBRID key switch throughput at config 3's shape: N=2^16, l=21, k=7, dnum=3).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the headline line
+(`ms_per_step` = milliseconds per timed step).  `--dump-outputs DIR` writes a fixed sample of the last step's result to DIR/*.npy.
+`--full` adds everything else to the same JSON line: the parity checks at full size, `power`, `roofline` (dominant kernel, live
+hipEvent timing), `cpu_baseline` (reference compiled from its own sources, or the oracle port, timed on this host), `evalmult`
+(CKKS EvalMult + HYBRID key switch throughput at config 3's shape: N=2^16, l=21, k=7, dnum=3) and the other legs.
 """
 import argparse
 import ctypes as C
@@ -63,7 +65,15 @@ def parse():
     ap.add_argument("--no-power", action="store_true", help="skip the package-power reading of the headline leg")
     ap.add_argument("--evalmult-logn", type=int, default=16, help="ring of the EvalMult leg (config 3: 16)")
     ap.add_argument("--evalmult-limbs", type=int, default=21, help="Q limbs of the EvalMult leg (config 3: 21)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: parity checks, power, roofline and per-kernel timings, the other "
+                         "legs (Hadamard, EvalMult, BFV, BSGS, EvalBootstrap, cc->EvalMult, key replication) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of what the last step computed to DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def source_sha():
@@ -157,6 +167,32 @@ def fill_random_tower(ctx, q, batch, seed, seed_polys=8):
         done += n
     ctx.sync()
     return dev
+
+
+def dump_outputs(out_dir, lib, ctx, x, batch, n_limbs):
+    """--dump-outputs: a fixed, seeded sample of limb-rows of the resident batch [batch][n_limbs][N] as the last timed step left it
+    (ntt_roundtrip: forward + inverse, what a caller of the step receives) and the same rows after one more forward transform of the batch
+    (ntt_forward: the step's forward half, so that a wrong but invertible transform shows too; the inverse that follows restores the
+    batch).  Residues are < 2^60, so every word is stored exactly as two float64 halves [..., 0] = high 32 bits, [..., 1] = low 32 bits.
+    sample_rows holds the row indices (row = tower * n_limbs + limb).  At most 2 x 16 MiB of samples."""
+    N = ctx.N
+    rows = batch * n_limbs
+    nrows = max(1, min(rows, (16 << 20) // (16 * N)))
+    pick = np.sort(np.random.default_rng(20261016).choice(rows, nrows, replace=False))
+
+    def sample():
+        out = np.empty((nrows, N), np.uint64)
+        for i, r in enumerate(pick):
+            lib.check(lib.L.fhe_memcpy_d2h(ctx.h, out[i].ctypes.data_as(C.c_void_p), C.c_void_p(x.value + int(r) * N * 8), N * 8, None))
+        ctx.sync()
+        return np.stack([(out >> np.uint64(32)).astype(np.float64), (out & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample_rows.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, "ntt_roundtrip.npy"), sample())
+    lib.check(lib.L.fhe_ntt_fwd(ctx.h, x, None, n_limbs, batch, None))
+    np.save(os.path.join(out_dir, "ntt_forward.npy"), sample())
+    lib.check(lib.L.fhe_ntt_inv(ctx.h, x, None, n_limbs, batch, None))
+    ctx.sync()
 
 
 def cpu_baseline(q, psi, logN, L, seconds):
@@ -1166,7 +1202,7 @@ def main():
         else:
             tdev = torch.device("cpu")
             dist.init_process_group(backend)
-    elif not os.environ.get("FHE_BENCH_NO_TORCH"):
+    elif a.full and not os.environ.get("FHE_BENCH_NO_TORCH"):  # (a plain one-process run needs no torch: the timed steps end in ctx.sync())
         try:
             import torch
         except Exception:
@@ -1203,7 +1239,7 @@ def main():
         step()
     barrier()
     gpu_sync()
-    psamp = PowerSampler(device) if rank == 0 else None
+    psamp = PowerSampler(device) if rank == 0 and a.full else None
     if psamp is not None:
         psamp.start()
     t0 = time.perf_counter()
@@ -1213,7 +1249,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     power = psamp.stop() if psamp is not None else None
-    if rank == 0 and world == 1 and power is None and not a.no_power and shutil_which("rocm-smi"):
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, lib, ctx, x, B, L)
+    if a.full and rank == 0 and world == 1 and power is None and not a.no_power and shutil_which("rocm-smi"):
         # no hwmon files: ~3 s of extra steps of the same leg (untimed) with one rocm-smi reading in the middle
         import threading
         box = {}
@@ -1236,6 +1274,25 @@ def main():
     ms_per_step = dt / a.steps * 1e3
     bytes_per_step = 4.0 * 8 * N * L * B  # fwd + inv, each: read once + write once
     value = bytes_per_step * world / (ms_per_step * 1e-3) / 1e9
+    headline = {
+        "metric": "NTT GB/s vs HBM roofline + CKKS EvalMultKeySwitch/sec, N=2^16 L=30, 1/2/4/8 GPU",
+        "value": round(value, 1), "unit": "GB/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": f"batched fwd+inv negacyclic NTT, N=2^{logN}, L={L} x 60-bit limbs, "
+                               f"{B} polynomials per GPU (BASELINE configs[1])",
+                   "global_batch": B * world, "bytes_per_step_per_gpu": bytes_per_step,
+                   "parallelism": f"batch-sharded x{world}, no data-path collective"},
+        "hbm_roofline_frac_fwd_inv": round(value / world / HBM_PEAK_GBPS, 4), "ms_per_step_per_rank": per_rank_ms, "full": a.full,
+    }
+    if not a.full:  # the plain run: the headline figure and nothing else (everything below runs with --full)
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        ctx.free(x)
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- parity at the full workload.  Every timed step is NTT followed by INTT, so the resident batch must still be the
     # generated one (round trip); and ONE more forward transform of the resident 16 GB batch is compared word for word with
@@ -1497,29 +1554,20 @@ def main():
     def emit(boot, ccm, cpu):
         if rank != 0:
             return
-        out = {
-            "metric": "NTT GB/s vs HBM roofline + CKKS EvalMultKeySwitch/sec, N=2^16 L=30, 1/2/4/8 GPU",
-            "value": round(value, 1), "unit": "GB/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-            "config": {"workload": f"batched fwd+inv negacyclic NTT, N=2^{logN}, L={L} x 60-bit limbs, "
-                                   f"{B} polynomials per GPU (BASELINE configs[1])",
-                       "global_batch": B * world, "bytes_per_step_per_gpu": bytes_per_step,
-                       "parallelism": f"batch-sharded x{world}, no data-path collective"},
-            "hbm_roofline_frac_fwd_inv": round(value / world / HBM_PEAK_GBPS, 4),
+        out = dict(headline, **{
             "roofline": roof, "cpu_baseline": cpu, "evalmult": em,
             # the leg runs at the package power cap (profiles/r06_sweeps.md section 2): time = energy / cap
             "power": power,
             # the legs that run the reference's own CryptoContext on the backend need the reference-built test programs
             "hal_build": "present" if os.path.exists(os.path.join(ROOT, "tests", "hal", "_build", "shim_ckks_hip")) else "absent",
-            "hadamard": hadamard, "parity_at_full_size": roundtrip, "ms_per_step_per_rank": per_rank_ms,
+            "hadamard": hadamard, "parity_at_full_size": roundtrip,
             # ONE rule for every cpu_baseline of this line: the reference runs with its best OpenMP team out of {8, 16, 32, 64, 128, all
             # logical cores}.  Legs whose probe takes seconds search it live (headline NTT, linear transform, BFV: "cores" = the winner);
             # the legs where one probe is a 10-100 s program (bootstrap, cc->EvalMult) use 32, the team that search selects on this host
             # class (rounds 1-3: 32 every time; 8.9-10.2 s per bootstrap at 32 threads, 45 s at 256).
             "cpu_team_rule": "best OpenMP team of {8,16,32,64,128,all}: searched live by the in-process legs, fixed at 32 (= what the search "
                              "picks on these hosts) for the legs that run the reference as a separate program",
-        }
+        })
         out["distributed"] = dinfo
         if keyrep is not None:
             out["rotation_key_replication"] = keyrep

@@ -187,7 +187,7 @@ def test_bench_self_launches_two_ranks_on_gloo(backend):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--logn", "12", "--limbs", "2",
            "--batch", "4", "--evalmult-logn", "10", "--evalmult-limbs", "5", "--evalmult-batch", "3", "--no-bfv", "--no-lt",
-           "--no-hadamard", "--no-cpu-baseline"]
+           "--no-hadamard", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -211,7 +211,7 @@ def _bench_on_gloo(world, extra_env=None, extra_args=(), timeout=2400):
     env.update(extra_env or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--logn", "12", "--limbs", "2",
            "--batch", "4", "--evalmult-logn", "10", "--evalmult-limbs", "5", "--evalmult-batch", "3", "--no-bfv", "--no-lt",
-           "--no-hadamard", "--no-cpu-baseline", *extra_args]
+           "--no-hadamard", "--no-cpu-baseline", "--full", *extra_args]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
 
 

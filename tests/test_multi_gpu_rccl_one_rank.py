@@ -116,7 +116,7 @@ def test_bench_forced_dist_on_one_gpu(tmp_path):
     env["FHE_BENCH_KEYREP_KEYS"] = "3"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4", "--steps", "1", "--warmup", "0", "--evalmult-batch", "4",
                         "--no-hadamard", "--no-bfv", "--no-lt", "--no-cc-evalmult", "--no-cpu-baseline", "--bootstrap-logn", "13",
-                        "--bootstrap-batch", "4", "--bootstrap-threads", "2"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--bootstrap-batch", "4", "--bootstrap-threads", "2", "--full"], env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     line = json.loads(p.stdout.strip().split("\n")[-1])
     assert line["n_gpus"] == 1 and "rccl" in line["evalmult"]["eval_key"], line["evalmult"]["eval_key"]

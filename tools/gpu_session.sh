@@ -14,7 +14,8 @@
 set -u
 S=${1:-help}; shift || true
 mkdir -p gpurun_out
-NTT_ONLY="--no-bootstrap --no-cc-evalmult --no-cpu-baseline --no-evalmult --no-bfv --no-hadamard --no-lt"
+OUT=$PWD/$_  # (the session output folder made on the line above, as an absolute path: the record session changes directory)
+NTT_ONLY="--full --no-bootstrap --no-cc-evalmult --no-cpu-baseline --no-evalmult --no-bfv --no-hadamard --no-lt"
 case "$S" in
   mall)
     timeout 600 tools/mallbench | tee gpurun_out/mall_bench.json
@@ -47,13 +48,13 @@ PY
     cd /tmp && export TMPDIR=/tmp
     G=$GRAFT_REPO_ROOT
     D=/tmp/rec; mkdir -p $D   # (traces and counter files are large: only summaries go to gpurun_out, which is merged back up to 64 MiB)
-    NTTLEG="--no-bootstrap --no-cc-evalmult --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-evalmult --no-bfv --no-hadamard --no-lt"
+    NTTLEG="--full --no-bootstrap --no-cc-evalmult --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-evalmult --no-bfv --no-hadamard --no-lt"
     for c in FETCH_SIZE WRITE_SIZE; do
       timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $D/pmc_${R}_$c -- python $G/bench.py $NTTLEG > $D/pmc_${R}_$c.log 2>&1
     done
     SQ="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_WAVES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY"
     timeout 600 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $D/pmc_${R}_sq_ntt -- python $G/bench.py $NTTLEG > $D/pmc_${R}_sq_ntt.log 2>&1
-    timeout 600 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $D/pmc_${R}_sq_evalmult -- python $G/bench.py --no-bootstrap --no-cc-evalmult --batch 8 --steps 1 --warmup 0 --no-cpu-baseline --no-parity --no-bfv --no-hadamard --no-lt > $D/pmc_${R}_sq_evalmult.log 2>&1
+    timeout 600 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $D/pmc_${R}_sq_evalmult -- python $G/bench.py --full --no-bootstrap --no-cc-evalmult --batch 8 --steps 1 --warmup 0 --no-cpu-baseline --no-parity --no-bfv --no-hadamard --no-lt > $D/pmc_${R}_sq_evalmult.log 2>&1
     echo "== bootstrap (64 ciphertexts, groups of 16 on 2 host threads): census, then FETCH / WRITE passes"
     timeout 900 rocprofv3 --kernel-trace --output-format csv -d $D/boot_${R}_trace -- python $G/tools/boot_wide_profile.py run 64 16 2 2 > $D/boot_${R}_trace.log 2>&1
     tail -1 $D/boot_${R}_trace.log
@@ -74,12 +75,12 @@ PY
     FHE_PROFILE_DIR=$D python tools/collect_profiles.py $R --pmc-only
     cp profiles/${R}_pmc_traffic.json profiles/${R}_pmc_valu.json profiles/${R}_bootstrap_pmc.json gpurun_out/ 2>/dev/null
     unset FHE_BENCH_NO_TORCH
-    echo "== bench (default flags, as the driver runs it)"
-    timeout 1500 python bench.py 2>gpurun_out/bench_$R.err | tail -1 | tee gpurun_out/bench_$R.json | cut -c1-500
+    echo "== bench --full (every leg, default flags otherwise)"
+    timeout 1500 python bench.py --full 2>$OUT/bench_$R.err | tail -1 | tee $OUT/bench_$R.json | cut -c1-500
     export FHE_BENCH_NO_TORCH=1
     cd /tmp
-    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof_${R}_ntt -- python $G/bench.py --no-bootstrap --no-cc-evalmult --no-cpu-baseline --no-parity --no-evalmult --no-bfv --no-hadamard --no-lt > $D/prof_${R}_ntt.log 2>&1
-    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof_${R}_evalmult -- python $G/bench.py --no-bootstrap --no-cc-evalmult --batch 8 --steps 1 --warmup 0 --no-cpu-baseline --no-parity --no-bfv --no-hadamard --no-lt > $D/prof_${R}_evalmult.log 2>&1
+    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof_${R}_ntt -- python $G/bench.py --full --no-bootstrap --no-cc-evalmult --no-cpu-baseline --no-parity --no-evalmult --no-bfv --no-hadamard --no-lt > $D/prof_${R}_ntt.log 2>&1
+    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof_${R}_evalmult -- python $G/bench.py --full --no-bootstrap --no-cc-evalmult --batch 8 --steps 1 --warmup 0 --no-cpu-baseline --no-parity --no-bfv --no-hadamard --no-lt > $D/prof_${R}_evalmult.log 2>&1
     cd $G
     f=$(ls -t $D/prof_${R}_ntt/*/*kernel_stats.csv | head -1); cp $f gpurun_out/${R}_rocprof_kernel_stats_ntt_leg.csv; head -6 $f | cut -c1-170
     f=$(ls -t $D/prof_${R}_evalmult/*/*kernel_stats.csv | head -1); cp $f gpurun_out/${R}_rocprof_kernel_stats_evalmult256.csv; head -10 $f | cut -c1-170 ;;

@@ -12,7 +12,7 @@ per = collections.defaultdict(lambda: collections.defaultdict(float))
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
     D = f"/tmp/pmcleg_{tag}_{c}"
     subprocess.run(["rm", "-rf", D])
-    cmd = ["timeout", "600", "rocprofv3", "--kernel-trace", "--pmc", c, "--output-format", "csv", "-d", D, "--", sys.executable, os.path.join(G, "bench.py"), *flags]
+    cmd = ["timeout", "600", "rocprofv3", "--kernel-trace", "--pmc", c, "--output-format", "csv", "-d", D, "--", sys.executable, os.path.join(G, "bench.py"), "--full", *flags]
     r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True)
     dur = {}
     for f in glob.glob(f"{D}/*/*kernel_trace.csv"):

@@ -8,7 +8,7 @@ tag, counters = sys.argv[1], sys.argv[2:]
 G = os.environ.get("GRAFT_REPO_ROOT", os.getcwd())
 D = f"/tmp/pmc_{tag}"
 env = dict(os.environ, FHE_BENCH_NO_TORCH="1", TMPDIR="/tmp")
-leg = "--no-bootstrap --no-cc-evalmult --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-evalmult --no-bfv --no-hadamard --no-lt".split()
+leg = "--full --no-bootstrap --no-cc-evalmult --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-evalmult --no-bfv --no-hadamard --no-lt".split()
 cmd = ["rocprofv3", "--kernel-trace", "--pmc", *counters, "--output-format", "csv", "-d", D, "--", sys.executable, os.path.join(G, "bench.py"), *leg]
 r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=900)
 open(os.path.join(G, "gpurun_out", f"pmc_{tag}.log"), "w").write(r.stdout[-3000:] + "\n" + r.stderr[-3000:])

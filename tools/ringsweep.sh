@@ -1,4 +1,4 @@
-NTT_ONLY="--no-bootstrap --no-cc-evalmult --no-cpu-baseline --no-evalmult --no-bfv --no-hadamard --no-lt --no-parity"
+NTT_ONLY="--full --no-bootstrap --no-cc-evalmult --no-cpu-baseline --no-evalmult --no-bfv --no-hadamard --no-lt --no-parity"
 for ln in 13 14 15 17; do
   b=$((1024 * 65536 / (1 << ln)))
   for m in 0 1; do
