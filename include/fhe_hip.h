@@ -538,6 +538,30 @@ fhe_status fhe_sample_gaussian(fhe_ctx* ctx, uint64_t* out, const uint32_t* limb
 fhe_status fhe_sample_ternary(fhe_ctx* ctx, uint64_t* out, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, uint64_t seed,
                               uint32_t streamId, void* stream);
 
+/* ---- f3: the same samplers on the reference's cryptographic PRNG construction (csrc/blake2_kernels.h) --------------------------
+ * default_prng::Blake2Engine (src/core/lib/utils/prng/blake2engine.cpp) draws 4 KiB per Generate(): blake2xb (blake2xb-ref.c) with
+ * out = 4096 bytes, in = the engine's 64-bit counter (8 bytes little-endian), key = its 512-bit seed; then the counter is incremented.
+ * These entries compute that stream on the device, every block and every BLAKE2b leaf of a block in parallel:
+ *   fhe_blake2xb_stream   out[k * 1024 + i] = word i of the block of counter counter0 + k (k < nBlocks): the words
+ *                         Blake2Engine(key, counter0) returns from successive calls.  out must be 8-byte aligned.
+ * With R[i] = S[2i] | S[2i+1] << 32 the 64-bit words of that stream, the samplers (same output layout and format as fhe_sample_*):
+ *   fhe_sample_uniform_blake2    element e = (t * nLimbs + l) * N + j:  (R[2e+1] * 2^64 + R[2e]) mod q_l.  Statistical distance from
+ *                                uniform at most q / 2^128 < 2^-68 per coefficient (the reference rejects instead: exact)
+ *   fhe_sample_gaussian_blake2   element e = t * N + j:  Peikert's inversion of s = (R[e] >> 11) * 2^-53 - 0.5 over the same table
+ *                                (and the same per-sigma cache and 1 < sigma < 300 range) as fhe_sample_gaussian
+ *   fhe_sample_ternary_blake2    element e = t * N + j:  mulhi(R[e], 3) - 1 (each outcome within 2^-64 of 1/3)
+ * A call uses counters counter0 ... counter0 + ceil(words64 / 512) - 1, words64 = 2 * batch * nLimbs * N (uniform) or batch * N; give
+ * every call its own counter range.  The key travels by value in the kernel arguments: it is never stored in a device buffer.
+ * Against the Philox entries above: a cryptographic generator keyed by 512 bits (Philox4x32-10 is a statistical generator keyed by 64
+ * bits: its words are not fit for keys that will ever be published), and the words are pinned on the reference's own blake2xb. */
+fhe_status fhe_blake2xb_stream(fhe_ctx* ctx, uint32_t* out, uint64_t nBlocks, const uint32_t key[16], uint64_t counter0, void* stream);
+fhe_status fhe_sample_uniform_blake2(fhe_ctx* ctx, uint64_t* out, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch,
+                                     const uint32_t key[16], uint64_t counter0, void* stream);
+fhe_status fhe_sample_gaussian_blake2(fhe_ctx* ctx, uint64_t* out, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, double sigma,
+                                      const uint32_t key[16], uint64_t counter0, void* stream);
+fhe_status fhe_sample_ternary_blake2(fhe_ctx* ctx, uint64_t* out, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch,
+                                     const uint32_t key[16], uint64_t counter0, void* stream);
+
 /* ---- measurement helper ----------------------------------------------------------------------------
  * Runs `iters` back-to-back launches of fwd (dir=0), inv (dir=1) or fwd+inv (dir=2) NTT on x — or of a single
  * pass kernel of a two-pass ring: 10/11 = column/row pass of the forward, 12/13 = row/column pass of the

@@ -27,6 +27,7 @@
 #include "ntt_row8.h"
 #include "rt.h"
 #include "sampler_kernels.h"
+#include "blake2_kernels.h"
 
 using namespace fhe;
 
@@ -1417,6 +1418,31 @@ extern "C" fhe_status fhe_crt_decompose(fhe_ctx* c, const uint64_t* x, const uin
 }
 
 // ---- f3: sampled towers on the device (sampler_kernels.h) ----------------------------------------------------------------------
+// the reference's table (DiscreteGaussianGeneratorImpl::Initialize, discretegaussiangenerator-impl.h:75-89), built once per sigma and
+// shared by both generators
+static fhe_status dgg_table(fhe_ctx* c, double sigma, const double** cdf, uint32_t* len, double* av, const char* who) {
+    ARG_CHECK(sigma > 1.000000001 && sigma < 300.0, std::string(who) + ": the inversion sampler covers 1 < sigma < 300 (the reference's Peikert range)");
+    std::lock_guard<std::mutex> lk(c->cacheMutex);
+    auto it = c->dggTabs.find(sigma);
+    if (it == c->dggTabs.end()) {
+        const double M = 12.00610553538285;
+        const int64_t fin = (int64_t)std::ceil(sigma * M);
+        std::vector<double> vals((size_t)fin);
+        const double variance = 2 * sigma * sigma;
+        double cusum = 0.0;
+        for (int64_t x = 1; x <= fin; ++x)
+            vals[(size_t)(x - 1)] = (cusum += std::exp(-((double)(x * x) / variance)));
+        const double a = 1.0 / (2 * cusum + 1.0);
+        for (auto& v : vals)
+            v *= a;
+        void* d = nullptr;
+        if (fhe_status s = upload(c, vals.data(), vals.size() * sizeof(double), &d))
+            return s;
+        it = c->dggTabs.emplace(sigma, std::make_tuple((const double*)d, (uint32_t)fin, a)).first;
+    }
+    *cdf = std::get<0>(it->second), *len = std::get<1>(it->second), *av = std::get<2>(it->second);
+    return FHE_OK;
+}
 static fhe_status sample_run(fhe_ctx* c, uint64_t* out, const uint32_t* li, uint32_t nl, uint32_t bt, uint32_t kind, double sigma,
                              uint64_t seed, uint32_t streamId, void* st, const char* who) {
     ARG_CHECK(c && out && bt >= 1, "fhe_sample: null argument or empty batch");
@@ -1426,29 +1452,9 @@ static fhe_status sample_run(fhe_ctx* c, uint64_t* out, const uint32_t* li, uint
     RT_CHECK(rt::set_device(c->device));
     a.out = out, a.q = c->d_q, a.logN = c->logN, a.nLimbs = nl, a.batch = bt, a.seed = seed, a.stream = streamId, a.kind = kind;
     a.cdf = nullptr, a.cdfLen = 0, a.a = 0.0;
-    if (kind == 1) {
-        // the reference's table (DiscreteGaussianGeneratorImpl::Initialize, discretegaussiangenerator-impl.h:75-89), built once per sigma
-        ARG_CHECK(sigma > 1.000000001 && sigma < 300.0, "fhe_sample_gaussian: the inversion sampler covers 1 < sigma < 300 (the reference's Peikert range)");
-        std::lock_guard<std::mutex> lk(c->cacheMutex);
-        auto it = c->dggTabs.find(sigma);
-        if (it == c->dggTabs.end()) {
-            const double M = 12.00610553538285;
-            const int64_t fin = (int64_t)std::ceil(sigma * M);
-            std::vector<double> vals((size_t)fin);
-            const double variance = 2 * sigma * sigma;
-            double cusum = 0.0;
-            for (int64_t x = 1; x <= fin; ++x)
-                vals[(size_t)(x - 1)] = (cusum += std::exp(-((double)(x * x) / variance)));
-            const double av = 1.0 / (2 * cusum + 1.0);
-            for (auto& v : vals)
-                v *= av;
-            void* d = nullptr;
-            if (fhe_status s = upload(c, vals.data(), vals.size() * sizeof(double), &d))
-                return s;
-            it = c->dggTabs.emplace(sigma, std::make_tuple((const double*)d, (uint32_t)fin, av)).first;
-        }
-        a.cdf = std::get<0>(it->second), a.cdfLen = std::get<1>(it->second), a.a = std::get<2>(it->second);
-    }
+    if (kind == 1)
+        if (fhe_status s = dgg_table(c, sigma, &a.cdf, &a.cdfLen, &a.a, who))
+            return s;
     const uint64_t lanes = kind == 0 ? ((uint64_t)bt * nl) << c->logN : (uint64_t)bt << c->logN;
     FHE_LAUNCH(sample_kernel, (uint32_t)((lanes + kThreads - 1) / kThreads), st, a);
     LAUNCH_CHECK();
@@ -1465,6 +1471,66 @@ extern "C" fhe_status fhe_sample_gaussian(fhe_ctx* c, uint64_t* out, const uint3
 extern "C" fhe_status fhe_sample_ternary(fhe_ctx* c, uint64_t* out, const uint32_t* li, uint32_t nl, uint32_t bt, uint64_t seed,
                                          uint32_t streamId, void* st) {
     return sample_run(c, out, li, nl, bt, 2, 0.0, seed, streamId, st, "fhe_sample_ternary");
+}
+
+// ---- f3: the same samplers on blake2xb in counter mode (blake2_kernels.h) ------------------------------------------------------------
+template <int KIND>
+static fhe_status blake2_launch(const fhe_ctx* c, Blake2Args& a, const uint32_t* key, uint64_t counter0, void* st) {
+    for (int i = 0; i < 16; ++i)
+        a.key[i] = key[i];
+    a.counter0 = counter0;
+    // the longest walk that leaves at least two waves per SIMD (one H0 per counter is computed by one lane: a shorter walk costs
+    // 2 / walk compressions more per leaf)
+    const uint64_t minWaves = 8ull * (c->cus ? c->cus : 256);
+    a.walk = kB2MaxWalk;
+    while (a.walk > 1 && a.nBlocks / a.walk < minWaves)
+        a.walk >>= 1;
+    const uint64_t perWg = (uint64_t)(kB2Threads / 64) * a.walk;
+    if (a.nBlocks)
+        FHE_LAUNCH_BARRIER_N(blake2xb_kernel<KIND>, (a.nBlocks + perWg - 1) / perWg, kB2Threads, st, a);
+    for (int i = 0; i < 16; ++i)  // (the argument copy on the host stack: the key leaves no trace here)
+        ((volatile uint32_t*)a.key)[i] = 0;
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+extern "C" fhe_status fhe_blake2xb_stream(fhe_ctx* c, uint32_t* out, uint64_t nBlocks, const uint32_t key[16], uint64_t counter0, void* st) {
+    ARG_CHECK(c && key && (out || nBlocks == 0), "fhe_blake2xb_stream: null argument");
+    ARG_CHECK(((uintptr_t)out & 7u) == 0, "fhe_blake2xb_stream: out must be 8-byte aligned");
+    ARG_CHECK(nBlocks <= ((uint64_t)UINT32_MAX - 1) * 4, "fhe_blake2xb_stream: nBlocks too large for one launch");
+    RT_CHECK(rt::set_device(c->device));
+    Blake2Args a{};
+    a.out = (uint64_t*)out, a.nBlocks = nBlocks;
+    return blake2_launch<3>(c, a, key, counter0, st);
+}
+static fhe_status blake2_sample(fhe_ctx* c, uint64_t* out, const uint32_t* li, uint32_t nl, uint32_t bt, int kind, double sigma,
+                                const uint32_t* key, uint64_t counter0, void* st, const char* who) {
+    ARG_CHECK(c && out && key && bt >= 1, std::string(who) + ": null argument or empty batch");
+    Blake2Args a{};
+    if (fhe_status s = make_sel(c, li, nl, &a.sel, who))
+        return s;
+    RT_CHECK(rt::set_device(c->device));
+    a.out = out, a.q = c->d_q, a.mu128 = c->d_mu128, a.logN = c->logN, a.nLimbs = nl;
+    if (kind == 1)
+        if (fhe_status s = dgg_table(c, sigma, &a.cdf, &a.cdfLen, &a.a, who))
+            return s;
+    // uniform: 2 words of 64 bits per coefficient, 256 coefficients per 4 KiB block; Gaussian / ternary: 1 word, 512 per block
+    a.total   = kind == 0 ? ((uint64_t)bt * nl) << c->logN : (uint64_t)bt << c->logN;
+    a.nBlocks = kind == 0 ? (a.total + 255) / 256 : (a.total + 511) / 512;
+    return kind == 0   ? blake2_launch<0>(c, a, key, counter0, st)
+           : kind == 1 ? blake2_launch<1>(c, a, key, counter0, st)
+                       : blake2_launch<2>(c, a, key, counter0, st);
+}
+extern "C" fhe_status fhe_sample_uniform_blake2(fhe_ctx* c, uint64_t* out, const uint32_t* li, uint32_t nl, uint32_t bt,
+                                                const uint32_t key[16], uint64_t counter0, void* st) {
+    return blake2_sample(c, out, li, nl, bt, 0, 0.0, key, counter0, st, "fhe_sample_uniform_blake2");
+}
+extern "C" fhe_status fhe_sample_gaussian_blake2(fhe_ctx* c, uint64_t* out, const uint32_t* li, uint32_t nl, uint32_t bt, double sigma,
+                                                 const uint32_t key[16], uint64_t counter0, void* st) {
+    return blake2_sample(c, out, li, nl, bt, 1, sigma, key, counter0, st, "fhe_sample_gaussian_blake2");
+}
+extern "C" fhe_status fhe_sample_ternary_blake2(fhe_ctx* c, uint64_t* out, const uint32_t* li, uint32_t nl, uint32_t bt,
+                                                const uint32_t key[16], uint64_t counter0, void* st) {
+    return blake2_sample(c, out, li, nl, bt, 2, 0.0, key, counter0, st, "fhe_sample_ternary_blake2");
 }
 
 // ------------------------------------------------------------------------------------------------

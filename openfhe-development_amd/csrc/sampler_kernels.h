@@ -58,11 +58,10 @@ FHE_HD uint64_t sample_uniform_word(uint64_t e, uint64_t q, uint64_t seed, uint3
     }
 }
 // Peikert's inversion, discretegaussiangenerator-impl.h:101-107: seed = U[0,1) - 0.5, tmp = |seed| - a / 2, 0 if tmp <= 0, else
-// (1 + index of the first table entry >= tmp) with the sign of seed.  U = 53 random bits * 2^-53.
-FHE_HD int64_t sample_gaussian_int(uint64_t e, const double* cdf, uint32_t n, double a, uint64_t seed, uint32_t stream) {
-    const Philox4 r  = philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), 0u, stream, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const uint64_t m = ((((uint64_t)r.v[1] << 32) | r.v[0]) >> 11);
-    const double s   = (double)m * (1.0 / 9007199254740992.0) - 0.5;
+// (1 + index of the first table entry >= tmp) with the sign of seed.  U = the top 53 bits of the random word x * 2^-53.  Shared by the
+// Philox path below and the blake2xb path (blake2_kernels.h).
+FHE_HD int64_t peikert_invert(uint64_t x, const double* cdf, uint32_t n, double a) {
+    const double s   = (double)(x >> 11) * (1.0 / 9007199254740992.0) - 0.5;
     const double tmp = (s < 0 ? -s : s) - a / 2;
     if (tmp <= 0.0)
         return 0;
@@ -78,6 +77,10 @@ FHE_HD int64_t sample_gaussian_int(uint64_t e, const double* cdf, uint32_t n, do
         lo = n - 1;  // (the reference throws here: probability below 2^-100)
     const int64_t v = (int64_t)lo + 1;
     return s > 0.0 ? v : -v;
+}
+FHE_HD int64_t sample_gaussian_int(uint64_t e, const double* cdf, uint32_t n, double a, uint64_t seed, uint32_t stream) {
+    const Philox4 r = philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), 0u, stream, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return peikert_invert(((uint64_t)r.v[1] << 32) | r.v[0], cdf, n, a);
 }
 // uniform in {-1, 0, 1}: two random bits until they are not 3 (sixteen tries per 32-bit word)
 FHE_HD int64_t sample_ternary_int(uint64_t e, uint64_t seed, uint32_t stream) {

@@ -105,6 +105,10 @@ class Lib:
         S("fhe_sample_uniform", C.c_int, [vp, vp, u32p, u32, u32, C.c_uint64, u32, vp])
         S("fhe_sample_gaussian", C.c_int, [vp, vp, u32p, u32, u32, C.c_double, C.c_uint64, u32, vp])
         S("fhe_sample_ternary", C.c_int, [vp, vp, u32p, u32, u32, C.c_uint64, u32, vp])
+        S("fhe_blake2xb_stream", C.c_int, [vp, vp, u64, u32p, u64, vp])
+        S("fhe_sample_uniform_blake2", C.c_int, [vp, vp, u32p, u32, u32, u32p, u64, vp])
+        S("fhe_sample_gaussian_blake2", C.c_int, [vp, vp, u32p, u32, u32, C.c_double, u32p, u64, vp])
+        S("fhe_sample_ternary_blake2", C.c_int, [vp, vp, u32p, u32, u32, u32p, u64, vp])
         S("fhe_conv_create", C.c_int, [vp, u32p, u32, u32p, u32, C.POINTER(vp)])
         S("fhe_conv_destroy", None, [vp])
         S("fhe_approx_switch_basis", C.c_int, [vp, vp, u32, u32, vp, u32, u32, u32, vp])
@@ -193,6 +197,13 @@ class Lib:
             if k.split("::")[-1] == kernel:
                 return int(n)
         return 0
+
+    def blake2xb_stream(self, key, counter0, n_blocks):
+        """uint32[n_blocks][1024]: the 4 KiB blocks blake2xb(in = counter0 + k, key) of Blake2Engine (fhe_blake2xb_stream)"""
+        if getattr(self, "_tiny", None) is None:
+            # the smallest context the library builds (N = 16, q = 97 = 1 mod 32, 19 a primitive 32nd root of unity): it only names the device
+            self._tiny = Context(self, 4, [97], [19])
+        return self._tiny.blake2xb_stream(key, counter0, n_blocks)
 
     def version(self):
         return self.L.fhe_version().decode()
@@ -317,10 +328,28 @@ class Context:
         return Tower(self, self.malloc(batch * n_limbs * self.N * 8), batch, n_limbs, limb_idx, fmt, owned=True)
 
     # ---- sampled towers (the sampling constructors of DCRTPolyImpl, dcrtpoly-impl.h:126-205, on the device: fhe_sample_*) ----
-    def sample(self, kind, batch, n_limbs, seed, stream_id, limb_idx=None, sigma=3.19, stream=None):
-        """kind: "uniform" (DugType), "gaussian" (DggType, standard deviation sigma) or "ternary" (TugType); COEFFICIENT format"""
+    def sample(self, kind, batch, n_limbs, seed=0, stream_id=0, limb_idx=None, sigma=3.19, stream=None, generator="philox", key=None,
+               counter0=0):
+        """kind: "uniform" (DugType), "gaussian" (DggType, standard deviation sigma) or "ternary" (TugType); COEFFICIENT format.
+        generator "philox": Philox4x32-10 keyed by `seed`, sub-stream `stream_id` (fhe_sample_*; a statistical generator);
+        generator "blake2": the reference's blake2xb counter mode keyed by `key` (64 bytes or 16 uint32 words) from block `counter0`
+        (fhe_sample_*_blake2)"""
         t = self.empty(batch, n_limbs, limb_idx, COEFFICIENT)
         L = self.lib.L
+        if generator == "blake2":
+            k = _key_words(key)
+            kp = k.ctypes.data_as(u32p)
+            if kind == "uniform":
+                self.lib.check(L.fhe_sample_uniform_blake2(self.h, t.ptr, t._li(), n_limbs, batch, kp, counter0, stream))
+            elif kind == "gaussian":
+                self.lib.check(L.fhe_sample_gaussian_blake2(self.h, t.ptr, t._li(), n_limbs, batch, sigma, kp, counter0, stream))
+            elif kind == "ternary":
+                self.lib.check(L.fhe_sample_ternary_blake2(self.h, t.ptr, t._li(), n_limbs, batch, kp, counter0, stream))
+            else:
+                raise ValueError(kind)
+            return t
+        if generator != "philox":
+            raise ValueError(generator)
         if kind == "uniform":
             self.lib.check(L.fhe_sample_uniform(self.h, t.ptr, t._li(), n_limbs, batch, seed, stream_id, stream))
         elif kind == "gaussian":
@@ -330,6 +359,31 @@ class Context:
         else:
             raise ValueError(kind)
         return t
+
+
+    def blake2xb_stream(self, key, counter0, n_blocks, stream=None):
+        """uint32[n_blocks][1024]: word i of row k is word i of blake2xb(4096 bytes, in = counter0 + k, key) (fhe_blake2xb_stream)"""
+        k = _key_words(key)
+        d = self.malloc(max(n_blocks, 1) * 4096)
+        try:
+            self.lib.check(self.lib.L.fhe_blake2xb_stream(self.h, d, n_blocks, k.ctypes.data_as(u32p), counter0, stream))
+            return self.download(d, (n_blocks, 512), stream).view(np.uint32)
+        finally:
+            self.free(d)
+
+
+def _key_words(key):
+    """the 512-bit blake2xb key as 16 little-endian uint32 words (Blake2Engine's seed array)"""
+    if key is None:
+        raise ValueError("generator='blake2' needs a 64-byte key")
+    if isinstance(key, (bytes, bytearray)):
+        if len(key) != 64:
+            raise ValueError("a blake2xb key is 64 bytes")
+        return np.frombuffer(bytes(key), dtype="<u4").astype(np.uint32)
+    k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32))
+    if k.shape != (16,):
+        raise ValueError("a blake2xb key is 16 uint32 words")
+    return k
 
 
 class Tower:

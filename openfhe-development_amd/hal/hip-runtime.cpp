@@ -31,6 +31,7 @@
 
 #include "utils/exception.h"
 #include "math/distributiongenerator.h"  // PseudoRandomNumberGenerator (the device sampler's seed is drawn from the reference's PRNG)
+#include "utils/memory.h"                 // secure_memset (the blake2 sampler key is cleared at exit)
 
 namespace lbcrypto {
 namespace hiprt {
@@ -185,6 +186,9 @@ Runtime* build() {
                   FHE_SYM(ckks_eval_mult, fhe_ckks_eval_mult) && FHE_SYM(bsgs_workspace_bytes, fhe_ckks_bsgs_workspace_bytes) &&
                   FHE_SYM(bsgs_transform, fhe_ckks_bsgs_transform) && FHE_SYM(checksum, fhe_checksum);
 #undef FHE_SYM
+        sym(h, "fhe_sample_uniform_blake2", &a.sample_uniform_blake2);  // (optional: FHE_HAL_DEVICE_SAMPLER=blake2 throws without them)
+        sym(h, "fhe_sample_gaussian_blake2", &a.sample_gaussian_blake2);
+        sym(h, "fhe_sample_ternary_blake2", &a.sample_ternary_blake2);
         if (!ok)
             r->why = path + " does not export the C ABI of include/fhe_hip.h";
         else if (a.device_count() < 1)
@@ -403,23 +407,50 @@ CtxHolder::~CtxHolder() {
     r.api.ctx_destroy(ctx);
 }
 bool Available() { return rt().live; }
-bool DeviceSamplerEnabled() {
-    static const bool on = [] {
+DeviceSampler DeviceSamplerEnabled() {
+    static const DeviceSampler mode = [] {
         const char* v = std::getenv("FHE_HAL_DEVICE_SAMPLER");
-        return v && v[0] == '1';
+        if (v && std::string(v) == "blake2")
+            return DeviceSampler::Blake2;
+        return v && v[0] == '1' ? DeviceSampler::Philox : DeviceSampler::Off;
     }();
-    return on && Available();
+    if (mode == DeviceSampler::Off || !Available())
+        return DeviceSampler::Off;
+    if (mode == DeviceSampler::Blake2) {
+        const Api& a = rt().api;
+        if (!a.sample_uniform_blake2 || !a.sample_gaussian_blake2 || !a.sample_ternary_blake2)
+            OPENFHE_THROW("FHE_HAL_DEVICE_SAMPLER=blake2: the device library does not export fhe_sample_*_blake2 (no fall-back to Philox)");
+    }
+    return mode;
 }
+static std::atomic<uint32_t> g_samplerStreams{1};
 void DeviceSamplerStream(uint64_t* seed, uint32_t* streamId) {
     static std::once_flag once;
     static uint64_t s = 0;
-    static std::atomic<uint32_t> next{1};
     std::call_once(once, [] {
         auto& g = lbcrypto::PseudoRandomNumberGenerator::GetPRNG();
         s       = ((uint64_t)g() << 32) | (uint64_t)g();
     });
     *seed     = s;
-    *streamId = next.fetch_add(1, std::memory_order_relaxed);
+    *streamId = g_samplerStreams.fetch_add(1, std::memory_order_relaxed);
+}
+namespace {
+// like ~Blake2Engine (blake2engine.cpp): the key is cleared when the process ends
+struct Blake2Key {
+    uint32_t w[16] = {};
+    ~Blake2Key() { lbcrypto::secure_memset(w, 0, sizeof(w)); }
+};
+}  // namespace
+void DeviceSamplerBlake2Stream(const uint32_t** key, uint64_t* counter0) {
+    static std::once_flag once;
+    static Blake2Key k;
+    std::call_once(once, [] {
+        auto& g = lbcrypto::PseudoRandomNumberGenerator::GetPRNG();
+        for (auto& w : k.w)
+            w = (uint32_t)g();
+    });
+    *key      = k.w;
+    *counter0 = (uint64_t)g_samplerStreams.fetch_add(1, std::memory_order_relaxed) << 32;
 }
 const Api& api() { return rt().api; }
 int Device() { return rt().device; }

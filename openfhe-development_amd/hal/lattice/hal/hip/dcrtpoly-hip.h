@@ -129,8 +129,9 @@ public:
         }
     }
     // the sampling constructors (dcrtpoly-impl.h:126-205).  Default: the reference's host samplers on the reference's PRNG stream (same seed,
-    // same words as the default backend), the tower uploaded at its first device use.  FHE_HAL_DEVICE_SAMPLER=1: device kernels on a
-    // counter-based generator (SampleOnDevice below) — a bootstrapping key set is 5-6 GB of uniform words that then never cross PCIe.
+    // same words as the default backend), the tower uploaded at its first device use.  FHE_HAL_DEVICE_SAMPLER=1 (Philox) or =blake2 (the
+    // reference's blake2xb): device kernels on a counter-based generator (SampleOnDevice below) — a bootstrapping key set is 5-6 GB of
+    // uniform words that then never cross PCIe.
     DCRTPolyHipImpl(const DggType& dgg, const std::shared_ptr<Params>& p, Format f = Format::EVALUATION) {
         if (!SampleOnDevice(1, p, f, dgg.GetStd()))
             m_h = HostType(dgg, p, f);
@@ -2266,37 +2267,56 @@ private:
         DropLastMeta();  // :698 (a narrow tower's device copy keeps its leading limbs; the result buffer already has the new height)
         return true;
     }
-    // kind 0: uniform residues, 1: discrete Gaussian (Peikert's inversion, the reference's table), 2: uniform ternary; COEFFICIENT words on the
-    // device, transformed there when EVALUATION is asked for
+    // kind 0: uniform residues, 1: discrete Gaussian (Peikert's inversion, the reference's table), 2: uniform ternary.
+    // Philox (FHE_HAL_DEVICE_SAMPLER=1): COEFFICIENT words on the device, transformed there when EVALUATION is asked for.
+    // blake2 (=blake2): uniform towers are labelled with the requested format directly, as the reference does (dcrtpoly-impl.h:153-160:
+    // uniform residues are uniform in either domain); Gaussian and ternary towers are sampled in COEFFICIENT format and transformed.
     bool SampleOnDevice(int kind, const std::shared_ptr<Params>& params, Format format, double sigma) {
-        if (!hiprt::DeviceSamplerEnabled() || !params || params->GetParams().empty() || (kind == 1 && !(sigma > 1.000000001 && sigma < 300.0)))
+        const hiprt::DeviceSampler gen = hiprt::DeviceSamplerEnabled();
+        if (gen == hiprt::DeviceSampler::Off || !params || params->GetParams().empty() || (kind == 1 && !(sigma > 1.000000001 && sigma < 300.0)))
             return false;
         hiprt::Resolved r;
         if (!ResolveSets(params->GetRingDimension(), {params}, &r))
             return false;
-        hiprt::MemberScope scope("DeviceSampler");
         const size_t N   = params->GetRingDimension();
         const uint32_t L = (uint32_t)params->GetParams().size();
-        uint64_t seed;
-        uint32_t sid;
-        hiprt::DeviceSamplerStream(&seed, &sid);
+        const bool blake2 = gen == hiprt::DeviceSampler::Blake2;
+        const Format sampled = blake2 && kind == 0 ? format : Format::COEFFICIENT;
         {
-            hiprt::Op op;
-            auto d = hiprt::Alloc((size_t)L * N);
-            const auto& A = hiprt::api();
-            const fhe_status st = kind == 0   ? A.sample_uniform(r.ctx, op.W(d), r.idx[0].data(), L, 1, seed, sid, op.s)
-                                  : kind == 1 ? A.sample_gaussian(r.ctx, op.W(d), r.idx[0].data(), L, 1, sigma, seed, sid, op.s)
-                                              : A.sample_ternary(r.ctx, op.W(d), r.idx[0].data(), L, 1, seed, sid, op.s);
-            hiprt::Check(st, "DeviceSampler");
-            hiprt::CountDevice();
-            m_h         = HostType(params, Format::COEFFICIENT, false);
-            m_d         = std::move(d);
-            m_hostValid = false;
-            m_zero      = false;
-            m_k         = 1;
+            hiprt::MemberScope scope(blake2 ? "DeviceSamplerBlake2" : "DeviceSampler");
+            {
+                hiprt::Op op;
+                auto d = hiprt::Alloc((size_t)L * N);
+                const auto& A = hiprt::api();
+                fhe_status st;
+                if (blake2) {
+                    const uint32_t* key;
+                    uint64_t c0;
+                    hiprt::DeviceSamplerBlake2Stream(&key, &c0);
+                    st = kind == 0   ? A.sample_uniform_blake2(r.ctx, op.W(d), r.idx[0].data(), L, 1, key, c0, op.s)
+                         : kind == 1 ? A.sample_gaussian_blake2(r.ctx, op.W(d), r.idx[0].data(), L, 1, sigma, key, c0, op.s)
+                                     : A.sample_ternary_blake2(r.ctx, op.W(d), r.idx[0].data(), L, 1, key, c0, op.s);
+                } else {
+                    uint64_t seed;
+                    uint32_t sid;
+                    hiprt::DeviceSamplerStream(&seed, &sid);
+                    st = kind == 0   ? A.sample_uniform(r.ctx, op.W(d), r.idx[0].data(), L, 1, seed, sid, op.s)
+                         : kind == 1 ? A.sample_gaussian(r.ctx, op.W(d), r.idx[0].data(), L, 1, sigma, seed, sid, op.s)
+                                     : A.sample_ternary(r.ctx, op.W(d), r.idx[0].data(), L, 1, seed, sid, op.s);
+                }
+                hiprt::Check(st, blake2 ? "DeviceSamplerBlake2" : "DeviceSampler");
+                hiprt::CountDevice();
+                m_h         = HostType(params, sampled, false);
+                m_d         = std::move(d);
+                m_hostValid = false;
+                m_zero      = false;
+                m_k         = 1;
+            }
+            if (!blake2 && format == Format::EVALUATION)
+                SwitchFormat();
         }
-        if (format == Format::EVALUATION)
-            SwitchFormat();
+        if (blake2 && sampled != format)
+            SwitchFormat();  // (outside the sampler's scope: that scope holds sampling kernels only, no forward transform)
         return true;
     }
     bool ModRaiseOnDevice(const PolyType& e, const std::shared_ptr<Params>& params) {

@@ -62,6 +62,9 @@ struct Api {
     decltype(&fhe_sample_uniform) sample_uniform;    // (optional sampling on the device: FHE_HAL_DEVICE_SAMPLER=1)
     decltype(&fhe_sample_gaussian) sample_gaussian;
     decltype(&fhe_sample_ternary) sample_ternary;
+    decltype(&fhe_sample_uniform_blake2) sample_uniform_blake2;    // (FHE_HAL_DEVICE_SAMPLER=blake2; resolved optionally: null when the
+    decltype(&fhe_sample_gaussian_blake2) sample_gaussian_blake2;  // library predates them, and then that option throws)
+    decltype(&fhe_sample_ternary_blake2) sample_ternary_blake2;
     decltype(&fhe_rescale_limbs) rescale_limbs;
     decltype(&fhe_rescale_limbs_pair) rescale_limbs_pair;
     decltype(&fhe_add_pair) add_pair;
@@ -108,12 +111,19 @@ struct Api {
 
 // true when the library is loaded and a device is usable; otherwise every DCRTPoly member runs on its host mirror
 bool Available();
-// FHE_HAL_DEVICE_SAMPLER=1: the sampling constructors of DCRTPoly (uniform / Gaussian / ternary) run as device kernels on a counter-based
-// generator (csrc/sampler_kernels.h): the distributions are the reference's, the words are not its Blake2 stream's.  Off by default: with
-// the reference's PRNG seeded the default backend and this one then produce the same keys and ciphertexts, word for word.
-bool DeviceSamplerEnabled();
-// the process's sampler seed (drawn once from the reference's PRNG, so a seeded PRNG gives reproducible device streams) and a fresh stream id
+// FHE_HAL_DEVICE_SAMPLER: the sampling constructors of DCRTPoly (uniform / Gaussian / ternary) as device kernels.  Unset: the reference's
+// host samplers (with the reference's PRNG seeded, the default backend and this one produce the same keys and ciphertexts, word for word).
+//   =1       Philox4x32-10 (csrc/sampler_kernels.h) keyed by 64 bits: a STATISTICAL generator, not for keys that will ever be published
+//   =blake2  the reference's own construction, blake2xb in counter mode (csrc/blake2_kernels.h), keyed by 512 bits from the reference's PRNG
+// The distributions are the reference's; the words are not its sequential Blake2 stream's.
+enum class DeviceSampler { Off, Philox, Blake2 };
+DeviceSampler DeviceSamplerEnabled();
+// Philox: the process's sampler seed (drawn once from the reference's PRNG, so a seeded PRNG gives reproducible device streams) and a
+// fresh stream id
 void DeviceSamplerStream(uint64_t* seed, uint32_t* streamId);
+// blake2: the process's 512-bit key (16 draws of the reference's PRNG, taken once, zeroed at exit) and the first counter of a fresh
+// stream id: (streamId << 32), so sampled tower sets never share a counter
+void DeviceSamplerBlake2Stream(const uint32_t** key, uint64_t* counter0);
 const Api& api();
 // throws (OPENFHE_THROW) with the library's message when a call failed
 void Check(fhe_status s, const char* what);
