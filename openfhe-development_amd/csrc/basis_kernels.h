@@ -214,6 +214,7 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ks_inner_product_kernel(const KsInne
     // lost: 1.61 ms instead of 1.14 ms per launch at config 3's shape, the pinned temporaries cost occupancy.)
     const uint64_t redc = g.red[idx];
     const uint32_t redM = (uint32_t)redc, redR = (uint32_t)(redc >> 32);
+    FHE_BOUND_CHECK(redR == 255u || redR >= 3u, "key switch: the quotient estimate on a modulus below 36 bits");
     const uint32_t N    = 1u << g.logN;
     const uint32_t rEnd = ((tr + 1u) << kTileLog) < N ? ((tr + 1u) << kTileLog) : N;
     const uint64_t q = lc.q;
@@ -239,6 +240,7 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ks_inner_product_kernel(const KsInne
                 d = csub(d, q << 1);
             }
             d = csub(d, q);
+            FHE_BOUND_CHECK(d < q, "key switch: a digit of q or more enters the 64-bit column sums");
             const uint64_t koff = (((uint64_t)(g.j0 + j) * (g.sizeQ + g.sizeP) + idx) << g.logN) + r;
             sum8_add(s0, d, g.keyB[koff]);
             sum8_add(s1, d, g.keyA[koff]);
@@ -313,6 +315,7 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ks_inner_multi_kernel(const KsInnerM
     const uint64_t mulo = g.mu128[2 * idx], muhi = g.mu128[2 * idx + 1];
     const uint64_t redc = g.red[idx];
     const uint32_t redM = (uint32_t)redc, redR = (uint32_t)(redc >> 32);
+    FHE_BOUND_CHECK(redR == 255u || redR >= 3u, "key switch: the quotient estimate on a modulus below 36 bits");
     const bool addFirst = g.first != nullptr && i < g.sizeQl;
     TwPair fc{0, 0};
     if (addFirst)
@@ -362,6 +365,7 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ks_inner_multi_kernel(const KsInnerM
                     v = csub(v, q << 1);
                 }
                 d[j][u] = csub(v, q);
+                FHE_BOUND_CHECK(d[j][u] < q, "key switch: a digit of q or more enters the 64-bit column sums");
             }
         uint64_t f[CPL];
 #pragma unroll

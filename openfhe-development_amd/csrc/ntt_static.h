@@ -47,15 +47,6 @@ FHE_HD uint64_t shoup_trunc(uint64_t y, const TwPair w, uint64_t nq) {
     const uint64_t Q            = yh * ph + (uint64_t)(mid >> 32);
     return y * w.w + Q * nq;
 }
-// any 64-bit x -> x - k q in [0, 2q): k = ((x >> 32) * redM >> 32) >> redR  (red_stream); limbs below 2^35 (redR == 255) take the ladder of
-// three conditional subtractions, which needs x < 16q (red_slow_stream)
-FHE_HD uint64_t red_estimate(uint64_t x, const BflyConst c) {
-    if (c.redR == 255u)
-        return csub2(csub2(csub2(x, c.q << 3), c.q << 2), c.twoq);
-    const uint64_t nq = ((uint64_t)c.nqh << 32) | c.nql;
-    const uint32_t k  = (uint32_t)(((x >> 32) * (uint64_t)c.redM) >> 32) >> c.redR;
-    return x + (uint64_t)k * nq;
-}
 #if defined(FHE_EMU)
 #define FHE_BOUND_CHECK(cond, what)                                                                  \
     do {                                                                                             \
@@ -68,6 +59,17 @@ FHE_HD uint64_t red_estimate(uint64_t x, const BflyConst c) {
 #define FHE_BOUND_CHECK(cond, what) ((void)0)
 #endif
 
+// any 64-bit x -> x - k q in [0, 2q): k = ((x >> 32) * redM >> 32) >> redR  (red_stream); limbs below 2^35 (redR == 255) take the ladder of
+// three conditional subtractions, which needs x < 16q (red_slow_stream)
+FHE_HD uint64_t red_estimate(uint64_t x, const BflyConst c) {
+    if (c.redR == 255u)
+        return csub2(csub2(csub2(x, c.q << 3), c.q << 2), c.twoq);
+    // (k misses floor(x / q) by less than 2^32 / q + 2^-redR: redR = bitlen(q) - 33 >= 3 is the domain fhe_ctx_create states)
+    FHE_BOUND_CHECK(c.redR >= 3u, "the quotient estimate on a modulus below 36 bits");
+    const uint64_t nq = ((uint64_t)c.nqh << 32) | c.nql;
+    const uint32_t k  = (uint32_t)(((x >> 32) * (uint64_t)c.redM) >> 32) >> c.redR;
+    return x + (uint64_t)k * nq;
+}
 // compile-time plan of one pass: the same grouping of the T stages into register-resident steps as plan_pass()
 template <bool LA, bool INV, int T>
 struct SPlan {

@@ -24,18 +24,31 @@ from openfhe_amd import fhe_hip as fh
 lib = fh.Lib({so!r})
 o = libs.load_oracle()
 rng = np.random.default_rng(61)
-for logN, L, B in {shapes!r}:
-    N, M = 1 << logN, 2 << logN
-    q = [o.orc_last_prime(60, M)]
-    for _ in range(L - 1):
-        q.append(o.orc_previous_prime(q[-1], M))
+for logN, sizes, B in {shapes!r}:
+    N, M, L = 1 << logN, 2 << logN, len(sizes)
+    q = []
+    for s in sizes:  # the last prime of every size asked for; a repeated size descends
+        v = o.orc_last_prime(s, M)
+        while v in q:
+            v = o.orc_previous_prime(v, M)
+        assert int(v).bit_length() == s and v % M == 1, (logN, s, v)
+        q.append(v)
     q = np.array(q, np.uint64)
     psi = np.array([o.orc_root_of_unity(M, int(v)) for v in q], np.uint64)
     ctx = fh.Context(lib, logN, q, psi)
     octx = o.orc_ctx_create(N, L, q, psi)
     x = libs.rand_tower(rng, q, N, B)
-    x[0, :, 0] = 0
-    x[0, :, 1] = q - np.uint64(1)
+    if min(sizes) == 60:
+        x[0, :, 0] = 0
+        x[0, :, 1] = q - np.uint64(1)
+    else:  # one tower at the top of the range: its even limbs all q-1, its odd limbs a quarter q-1, a quarter 0, the rest uniform
+        for l in range(L):
+            if l % 2 == 0:
+                x[0, l, :] = q[l] - np.uint64(1)
+            else:
+                sel = rng.permutation(N)
+                x[0, l, sel[:N // 4]] = q[l] - np.uint64(1)
+                x[0, l, sel[N // 4:N // 2]] = 0
     want = x.copy()
     o.orc_ntt_fwd_tower(octx, want, None, L, B, 0)
     t = ctx.tower(x, fmt=fh.COEFFICIENT)
@@ -86,15 +99,24 @@ def test_row8_default_shapes_run_row8(backend):
     assert backend.launch_count("ntt_row8_kernel") - before == 6
 
 
+SMALL = (60, 35, 33, 30)  # limbs on the ladder reductions (below 36 bits) next to a 60-bit one
+
+
 def test_row8_forced_shapes_on_emulator():
-    """8 waves per tile (12 stages: 2^16 and 2^17) and the 5 + 11 split of 2^16, moduli of 60 and 36..45 bits (ladder reductions)"""
+    """8 waves per tile (12 stages: 2^16 and 2^17) and the 5 + 11 split of 2^16, moduli of 60 bits alone and limbs on the ladder
+    reductions next to a 60-bit one in one launch: 60, 35, 33 and 30 bits at 2^16 (both splits), 30 and 60 bits at 2^17 (the GPU test
+    runs all four sizes at 2^17 too)"""
     so = os.path.join(ROOT, "tests", "emu", "libfhe_emu.so")
-    run_child(so, [(16, 2, 1), (17, 1, 1)], {"FHE_NTT_ROW8": "1"}, 6)
-    run_child(so, [(16, 1, 2)], {"FHE_NTT_ROW8": "1", "FHE_NTT_T1": "5"}, 3)
+    run_child(so, [(16, (60, 60), 1), (17, (60,), 1)], {"FHE_NTT_ROW8": "1"}, 6)
+    run_child(so, [(16, (60,), 2)], {"FHE_NTT_ROW8": "1", "FHE_NTT_T1": "5"}, 3)
+    run_child(so, [(16, SMALL, 1), (17, (30, 60), 1)], {"FHE_NTT_ROW8": "1"}, 6)
+    run_child(so, [(16, (35, 60, 30, 33), 1)], {"FHE_NTT_ROW8": "1", "FHE_NTT_T1": "5"}, 3)
 
 
 @pytest.mark.gpu
 def test_row8_forced_shapes_on_gpu():
     so = os.path.join(ROOT, "openfhe-development_amd", "csrc", "libfhe_hip.so")
-    run_child(so, [(16, 4, 3), (17, 2, 2)], {"FHE_NTT_ROW8": "1"}, 6)
-    run_child(so, [(16, 3, 2)], {"FHE_NTT_ROW8": "1", "FHE_NTT_T1": "5"}, 3)
+    run_child(so, [(16, (60,) * 4, 3), (17, (60, 60), 2)], {"FHE_NTT_ROW8": "1"}, 6)
+    run_child(so, [(16, (60,) * 3, 2)], {"FHE_NTT_ROW8": "1", "FHE_NTT_T1": "5"}, 3)
+    run_child(so, [(16, SMALL, 3), (17, SMALL, 2)], {"FHE_NTT_ROW8": "1"}, 6)
+    run_child(so, [(16, (35, 60, 30, 33), 2)], {"FHE_NTT_ROW8": "1", "FHE_NTT_T1": "5"}, 3)
