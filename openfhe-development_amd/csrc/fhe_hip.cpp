@@ -686,22 +686,48 @@ static int static_mode(const fhe_ctx* c, const PassPlan& pp, bool inverse) {
     return inverse ? ((pp.layoutA || !twoPass) ? 1 : 0) : fclass;
 }
 // Which row pass runs (both are bit-exact; profiles/r06_sweeps.md section 4): ntt_row8.h for 9..11 stages (rings 2^13..2^15: 2-10 % faster),
-// ntt_static.h's 16-residues-per-lane kernel for 12 stages (1-3 % faster there).  FHE_NTT_ROW8 = 0 / 1 forces one of them (measurements).
-static bool row8_for(uint32_t T) {
+// ntt_static.h's 16-residues-per-lane kernel for 12 stages (1-3 % faster there) -- for what row8_batch_for leaves of a 12-stage batch: its
+// P-aligned part runs ntt_row8.h's batched kernel.  FHE_NTT_ROW8 = 0 / 1 forces one of them (measurements).
+constexpr uint32_t kRow8BatchDefault = 2;
+constexpr bool kRow8X1RegionsP2 = false, kRow8X1RegionsP4 = false;
+static int row8_forced() {
     static const int forced = [] {
         const char* v = std::getenv("FHE_NTT_ROW8");
         return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : -1;
     }();
-    return forced >= 0 ? forced == 1 : T <= 11u;
+    return forced;
+}
+static bool row8_for(uint32_t T) { return row8_forced() >= 0 ? row8_forced() == 1 : T <= 11u; }
+// Polynomials per workgroup of the 12-stage row pass (ntt_row8.h, the batched kernel: one twiddle fetch serves P polynomials): the
+// measured winner per stage count (profiles/r09_sweeps.md: P = 2 with one set of X1 regions, 27.33 against 27.92 ms per headline step;
+// P = 4 27.37, a set of regions per polynomial 28.4 / 32.7); 1 = the kernel row8_for names.  FHE_NTT_ROW8_BATCH = 1 / 2 / 4 forces P for
+// the stage counts that have an instance (12), FHE_NTT_ROW8_X1 = 0 / 1 the form of the exchange between waves (0: one set of LDS regions
+// and a barrier between the polynomials, 1: a set per polynomial).  Both are read once per process (measurements, tests).
+static uint32_t row8_batch_for(uint32_t T) {
+    static const uint32_t forced = [] {
+        const char* v = std::getenv("FHE_NTT_ROW8_BATCH");
+        return v && (v[0] == '1' || v[0] == '2' || v[0] == '4') && !v[1] ? (uint32_t)(v[0] - '0') : 0u;
+    }();
+    if (T != 12u)
+        return 1u;
+    // (a forced unbatched kernel, FHE_NTT_ROW8, takes the whole batch unless P is forced as well)
+    return forced ? forced : row8_forced() >= 0 ? 1u : kRow8BatchDefault;
+}
+static bool row8_x1_regions(uint32_t P) {
+    static const int forced = [] {
+        const char* v = std::getenv("FHE_NTT_ROW8_X1");
+        return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : -1;
+    }();
+    return forced >= 0 ? forced == 1 : (P == 2 ? kRow8X1RegionsP2 : kRow8X1RegionsP4);
 }
 static fhe_status launch_pass(const fhe_ctx* c, const PassPlan& pp, bool inverse, const uint64_t* xin, uint64_t* xout,
                               const LimbSel& sel, uint32_t nLimbs, uint32_t batch, bool canonOut, void* stream,
                               uint32_t inStride = 0, uint32_t inFirst = 0, uint32_t outStride = 0, uint32_t outFirst = 0,
                               const NttEpilogue* epi = nullptr, const uint32_t* proSrcLimb = nullptr, int64_t inDelta = 0) {
     NttPassArgs a;
-    const uint32_t grid = fill_pass_args(c, pp, inverse, xin, xout, sel, nLimbs, batch, canonOut, inStride, inFirst, outStride,
-                                         outFirst, a);
-    if (inDelta) {  // (the static kernels only)
+    uint32_t grid = fill_pass_args(c, pp, inverse, xin, xout, sel, nLimbs, batch, canonOut, inStride, inFirst, outStride,
+                                   outFirst, a);
+    if (inDelta) {  // (the static and row8 kernels only)
         if (c->logN < (uint32_t)kTileLog)
             return fail(FHE_ERR_UNSUPPORTED, "ntt: separately allocated towers need a ring of at least 4096");
         a.inDelta = inDelta;
@@ -747,14 +773,45 @@ static fhe_status launch_pass(const fhe_ctx* c, const PassPlan& pp, bool inverse
         FHE_LAUNCH_BARRIER((ntt_static_kernel<LA, INV, TT, MODE>), grid, stream, a); \
         launched = true; \
     }
+        // 12-stage row passes, several polynomials per workgroup (ntt_row8.h, batched): the P-aligned part of the batch; what is left of
+        // the batch follows below on the same stream, as the same pass over a view that starts at its first polynomial
+        const uint32_t P = (!pp.layoutA && c->logN > (uint32_t)kTileLog && mode == (inverse ? 0 : 9)) ? row8_batch_for(pp.T) : 1u;
+        if (P > 1 && batch >= P) {
+            NttPassArgs g = a;
+            g.batch      = batch / P;  // groups of P polynomials: the batch-fastest XCD order, in units of P
+            g.rows       = g.batch * nLimbs;
+            g.xcdSwizzle = ((nLimbs << (c->logN - pp.T)) % 8u == 0) ? 1u : 0u;
+            const uint32_t ggrid = g.rows << (c->logN - pp.T);
+            const bool x1p       = row8_x1_regions(P);
+            bool batched         = false;
+#define FHE_ROW8B_CASE(INV, MODE, PP, X1P) \
+    if (!batched && inverse == INV && P == PP && x1p == X1P) { \
+        FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P>), ggrid, 512u, stream, g); \
+        batched = true; \
+    }
+            FHE_ROW8B_CASE(false, 9, 2, false) FHE_ROW8B_CASE(true, 0, 2, false) FHE_ROW8B_CASE(false, 9, 2, true) FHE_ROW8B_CASE(true, 0, 2, true)
+            FHE_ROW8B_CASE(false, 9, 4, false) FHE_ROW8B_CASE(true, 0, 4, false) FHE_ROW8B_CASE(false, 9, 4, true) FHE_ROW8B_CASE(true, 0, 4, true)
+#undef FHE_ROW8B_CASE
+            const uint32_t done = g.batch * P;
+            if (done == batch) {
+                LAUNCH_CHECK();
+                return FHE_OK;
+            }
+            a.xin += a.inDelta ? (int64_t)done * a.inDelta : (int64_t)(((uint64_t)done * (a.inStride ? a.inStride : nLimbs)) << c->logN);
+            a.x += ((uint64_t)done * (a.outStride ? a.outStride : nLimbs)) << c->logN;
+            a.batch = batch - done;
+            a.rows  = a.batch * nLimbs;
+            grid    = tiles_for(c, a.rows);
+        }
         // row passes of two-pass rings at 8 residues per lane (ntt_row8.h: 8 waves per SIMD, one barrier per tile)
         if (!pp.layoutA && c->logN > (uint32_t)kTileLog && row8_for(pp.T)) {
-            // tiles of 2^T words on 2^(T-9) waves: grid and XCD order for that tile size
-            const uint32_t rgrid = a.rows << (c->logN - pp.T);
-            a.xcdSwizzle         = ((nLimbs << (c->logN - pp.T)) % 8u == 0) ? 1u : 0u;
+            // tiles of 2^T words on 2^(T-9) waves: grid and XCD order for that tile size (in a copy: a kernel below keeps its own)
+            NttPassArgs r = a;
+            const uint32_t rgrid = r.rows << (c->logN - pp.T);
+            r.xcdSwizzle         = ((nLimbs << (c->logN - pp.T)) % 8u == 0) ? 1u : 0u;
 #define FHE_ROW8_CASE(INV, TT, MODE) \
     if (!launched && inverse == INV && pp.T == TT && mode == MODE) { \
-        FHE_LAUNCH_BARRIER_N((r8::ntt_row8_kernel<INV, TT - 9, MODE>), rgrid, 64u << (TT - 9), stream, a); \
+        FHE_LAUNCH_BARRIER_N((r8::ntt_row8_kernel<INV, TT - 9, MODE>), rgrid, 64u << (TT - 9), stream, r); \
         launched = true; \
     }
             FHE_ROW8_CASE(false, 12, 9) FHE_ROW8_CASE(true, 12, 0) FHE_ROW8_CASE(false, 11, 9) FHE_ROW8_CASE(true, 11, 0)

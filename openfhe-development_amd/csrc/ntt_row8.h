@@ -27,6 +27,29 @@
 #define FHE_NTT_ROW8_H
 #include "ntt_static.h"
 #include "ntt_bfly8_pinned.h"
+#include <type_traits>
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(FHE_NO_BFLY_ASM)
+// the blocks the batched kernel runs on register banks 1..3 (bank 0 = ntt_bfly8_pinned.h's own): one text, included once per bank
+namespace fhe {
+namespace r8 {
+#define FHE_BK 1
+namespace bk1 {
+#include "ntt_bfly8_banked.h"
+}
+#undef FHE_BK
+#define FHE_BK 2
+namespace bk2 {
+#include "ntt_bfly8_banked.h"
+}
+#undef FHE_BK
+#define FHE_BK 3
+namespace bk3 {
+#include "ntt_bfly8_banked.h"
+}
+#undef FHE_BK
+}  // namespace r8
+}  // namespace fhe
+#endif
 
 namespace fhe {
 namespace r8 {
@@ -42,19 +65,28 @@ FHE_HD constexpr uint32_t fc3(uint32_t c) { return 8u * (c & 3u) + 264u * (c >> 
 FHE_HD constexpr uint32_t fc4(uint32_t c) { return 8u * (c & 3u) + 288u * (c >> 2); }
 
 // ---- butterflies: generated gfx950 code (device) or the same arithmetic in C++ with the bounds checked (emulator) ----------
-template <bool UNI, int B>
+// BK: the register bank the residues are pinned to (bank p = v[48+16p : 63+16p]); the batched kernel keeps polynomial p of its group in
+// bank p, every other caller uses bank 0.  Banks 1..3 (ntt_bfly8_banked.h) have the blocks of a 12-stage pass only.
+#define FHE_R8_BK(CALL)                        \
+    do {                                       \
+        if constexpr (BK == 0) CALL;           \
+        else if constexpr (BK == 1) bk1::CALL; \
+        else if constexpr (BK == 2) bk2::CALL; \
+        else bk3::CALL;                        \
+    } while (0)
+template <bool UNI, int B, int BK = 0>
 FHE_HD void fwd_stage(uint64_t (&r)[8], const TwPair (&w)[4], const BflyConst c, uint32_t (&bnd)[8]) {
 #ifdef FHE_PINNED_ASM
     (void)bnd;
     if constexpr (UNI) {
-        if constexpr (B == 0) stage_fwd_s_b0(r, w, c);
-        if constexpr (B == 1) stage_fwd_s_b1(r, w, c);
-        if constexpr (B == 2) stage_fwd_s_b2(r, w, c);
+        if constexpr (B == 0) FHE_R8_BK(stage_fwd_s_b0(r, w, c));
+        if constexpr (B == 1) FHE_R8_BK(stage_fwd_s_b1(r, w, c));
+        if constexpr (B == 2) FHE_R8_BK(stage_fwd_s_b2(r, w, c));
     }
     else {
-        if constexpr (B == 0) stage_fwd_v_b0(r, w, c);
-        if constexpr (B == 1) stage_fwd_v_b1(r, w, c);
-        if constexpr (B == 2) stage_fwd_v_b2(r, w, c);
+        if constexpr (B == 0) FHE_R8_BK(stage_fwd_v_b0(r, w, c));
+        if constexpr (B == 1) FHE_R8_BK(stage_fwd_v_b1(r, w, c));
+        if constexpr (B == 2) FHE_R8_BK(stage_fwd_v_b2(r, w, c));
     }
 #else
     const uint64_t nq = ((uint64_t)c.nqh << 32) | c.nql;
@@ -72,13 +104,14 @@ FHE_HD void fwd_stage(uint64_t (&r)[8], const TwPair (&w)[4], const BflyConst c,
 #endif
 }
 // the 4 residues whose index has bit B clear (the `a` inputs of the stage on bit B) below 2q
-template <int B>
+template <int B, int BK = 0>
 FHE_HD void red4_a(uint64_t (&r)[8], const BflyConst c, uint32_t (&bnd)[8]) {
 #ifdef FHE_PINNED_ASM
     (void)bnd;
+    static_assert(BK == 0 || B == 2, "row8: banks 1..3 sweep on register bit 2 only");
     if constexpr (B == 0) red4_a0(r, c);
     if constexpr (B == 1) red4_a1(r, c);
-    if constexpr (B == 2) red4_a2(r, c);
+    if constexpr (B == 2) FHE_R8_BK(red4_a2(r, c));
 #else
     for (int k = 0; k < 8; ++k)
         if (!((k >> B) & 1)) {
@@ -88,9 +121,10 @@ FHE_HD void red4_a(uint64_t (&r)[8], const BflyConst c, uint32_t (&bnd)[8]) {
         }
 #endif
 }
+template <int BK = 0>
 FHE_HD void red_all(uint64_t (&r)[8], const BflyConst c) {
 #ifdef FHE_PINNED_ASM
-    red8(r, c);
+    FHE_R8_BK(red8(r, c));
 #else
     for (int k = 0; k < 8; ++k) {
         r[k] = red_estimate(r[k], c);
@@ -98,9 +132,10 @@ FHE_HD void red_all(uint64_t (&r)[8], const BflyConst c) {
     }
 #endif
 }
+template <int BK = 0>
 FHE_HD void csub_all(uint64_t (&r)[8], uint64_t m) {
 #ifdef FHE_PINNED_ASM
-    csub8(r, m);
+    FHE_R8_BK(csub8(r, m));
 #else
     for (int k = 0; k < 8; ++k)
         r[k] = csub2(r[k], m);
@@ -138,20 +173,21 @@ FHE_HD void apply_red_op(uint64_t (&r)[8], const RedOp op, const BflyConst c, ui
 #endif
 // inverse stage on register bit B of a step with NB stages: the plan's reductions, then  a' = u + v (not reduced),
 // b' = shoup_trunc(u - v + K q, w) < 3q
-template <bool UNI, int NB, int B>
+template <bool UNI, int NB, int B, int BK = 0>
 FHE_HD void inv_stage(uint64_t (&r)[8], const TwPair (&w)[4], const BflyConst c, uint32_t (&bnd)[8]) {
 #ifdef FHE_PINNED_ASM
     (void)bnd;
+    static_assert(BK == 0 || NB == 3, "row8: banks 1..3 have the full inverse step only");
 #define FHE_R8_INV(TAG, NBB, NAME, BB) if constexpr (NB == NBB && B == BB) stage_invl_##TAG##_##NAME##_b##BB(r, w, c);
+#define FHE_R8_INVB(TAG, BB) if constexpr (NB == 3 && B == BB) FHE_R8_BK(stage_invl_##TAG##_full_b##BB(r, w, c));
     if constexpr (UNI) {
-        FHE_R8_INV(s, 3, full, 0) FHE_R8_INV(s, 3, full, 1) FHE_R8_INV(s, 3, full, 2) FHE_R8_INV(s, 2, two, 1) FHE_R8_INV(s, 2, two, 2)
-        FHE_R8_INV(s, 1, one, 2)
+        FHE_R8_INVB(s, 0) FHE_R8_INVB(s, 1) FHE_R8_INVB(s, 2) FHE_R8_INV(s, 2, two, 1) FHE_R8_INV(s, 2, two, 2) FHE_R8_INV(s, 1, one, 2)
     }
     else {
-        FHE_R8_INV(v, 3, full, 0) FHE_R8_INV(v, 3, full, 1) FHE_R8_INV(v, 3, full, 2) FHE_R8_INV(v, 2, two, 1) FHE_R8_INV(v, 2, two, 2)
-        FHE_R8_INV(v, 1, one, 2)
+        FHE_R8_INVB(v, 0) FHE_R8_INVB(v, 1) FHE_R8_INVB(v, 2) FHE_R8_INV(v, 2, two, 1) FHE_R8_INV(v, 2, two, 2) FHE_R8_INV(v, 1, one, 2)
     }
 #undef FHE_R8_INV
+#undef FHE_R8_INVB
 #else
     using P = InvPlan<NB, true>;  // (the stages' reductions and constants do not depend on the closing reductions)
     const uint64_t nq = ((uint64_t)c.nqh << 32) | c.nql;
@@ -175,11 +211,12 @@ FHE_HD void inv_stage(uint64_t (&r)[8], const TwPair (&w)[4], const BflyConst c,
         }
 #endif
 }
-template <int NB>
+template <int NB, int BK = 0>
 FHE_HD void inv_end(uint64_t (&r)[8], const BflyConst c, uint32_t (&bnd)[8]) {
 #ifdef FHE_PINNED_ASM
     (void)bnd;
-    if constexpr (NB == 3) inv_end_full(r, c);
+    static_assert(BK == 0 || NB == 3, "row8: banks 1..3 have the full inverse step only");
+    if constexpr (NB == 3) FHE_R8_BK(inv_end_full(r, c));
     if constexpr (NB == 2) inv_end_two(r, c);
     if constexpr (NB == 1) inv_end_one(r, c);
 #else
@@ -499,6 +536,247 @@ template <bool INV, int WB, int MODE>
 FHE_GLOBAL void FHE_LAUNCH_BOUNDS2(64 << WB, 8) ntt_row8_kernel(const NttPassArgs a) {
     FHE_SHARED_U64(lds, (1 << WB) * kRegion);
     ntt_row8_core<INV, WB, MODE>(a, lds);
+}
+
+
+// ---- the batched form: one workgroup transforms the same (limb, tile) of P consecutive polynomials of the batch -----------------------
+// Twiddles depend on (limb, tile) and not on the polynomial: every twiddle pair, per-lane or scalar, is fetched ONCE per step and serves
+// the P register banks r[0..P-1] (ntt_bfly8_pinned.h: bank p = v[48+16p : 63+16p], one shared butterfly slot); so are the tile's address
+// arithmetic and its scalar constants.  The butterflies, reductions and lazy bounds of a polynomial are those of ntt_row8_core, so the
+// words are bit-identical.  LDS is time-shared: the exchanges X2, X3, X4 are private to a wave and a wave's LDS operations execute in
+// order, so polynomial 0, 1, ... go through the wave's one region in turn.  Only X1 crosses waves: X1P = false sends the polynomials
+// through the one set of regions with a workgroup barrier between them (2 P - 1 barriers per tile group), X1P = true gives every
+// polynomial its own set (P barriers, P x 36 KiB of LDS).
+template <int P, int I = 0, class F>
+FHE_HD void for_bank(F&& f) {
+    if constexpr (I < P) {
+        f(std::integral_constant<int, I>{});
+        for_bank<P, I + 1>(f);
+    }
+}
+#define FHE_R8_BANKS(pv) for_bank<P>([&](auto pc_) { constexpr int pv = decltype(pc_)::value;
+#define FHE_R8_BANKS_END });
+template <bool UNI, int NB, bool SWEEP, int P>
+FHE_HD void fwd_step_b(uint64_t (&r)[P][8], const TwPair* tw, uint32_t hi, uint32_t F, uint32_t logN, const BflyConst c, uint32_t inBound) {
+    uint32_t bnd[P][8];
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < 8; ++k)
+            bnd[p][k] = inBound;
+    TwPair w2[4], w1[4], w0[4];
+    if constexpr (NB >= 1) load_tw<UNI, 2>(w2, tw, hi, F, logN);
+    if constexpr (NB >= 2) load_tw<UNI, 1>(w1, tw, hi, F, logN);
+    FHE_R8_BANKS(p)
+        if constexpr (SWEEP && NB >= 1) red4_a<2, p>(r[p], c, bnd[p]);
+        if constexpr (NB >= 1) fwd_stage<UNI, 2, p>(r[p], w2, c, bnd[p]);
+    FHE_R8_BANKS_END
+    if constexpr (NB >= 3) load_tw<UNI, 0>(w0, tw, hi, F, logN);
+    FHE_R8_BANKS(p)
+        if constexpr (NB >= 2) fwd_stage<UNI, 1, p>(r[p], w1, c, bnd[p]);
+    FHE_R8_BANKS_END
+    FHE_R8_BANKS(p)
+        if constexpr (NB >= 3) fwd_stage<UNI, 0, p>(r[p], w0, c, bnd[p]);
+    FHE_R8_BANKS_END
+}
+template <bool UNI, int NB, bool LAZY, int P>
+FHE_HD void inv_step_b(uint64_t (&r)[P][8], const TwPair* tw, uint32_t hi, uint32_t F, uint32_t logN, const BflyConst c) {
+    uint32_t bnd[P][8];
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < 8; ++k)
+            bnd[p][k] = 3;
+    TwPair w2[4], w1[4], w0[4];
+    if constexpr (NB >= 3) load_tw<UNI, 0>(w0, tw, hi, F, logN);
+    if constexpr (NB >= 2) load_tw<UNI, 1>(w1, tw, hi, F, logN);
+    if constexpr (NB >= 1 && NB < 3) load_tw<UNI, 2>(w2, tw, hi, F, logN);
+    FHE_R8_BANKS(p)
+        if constexpr (NB >= 3) inv_stage<UNI, NB, 0, p>(r[p], w0, c, bnd[p]);
+    FHE_R8_BANKS_END
+    if constexpr (NB >= 3) load_tw<UNI, 2>(w2, tw, hi, F, logN);
+    FHE_R8_BANKS(p)
+        if constexpr (NB >= 2) inv_stage<UNI, NB, 1, p>(r[p], w1, c, bnd[p]);
+    FHE_R8_BANKS_END
+    FHE_R8_BANKS(p)
+        if constexpr (NB >= 1) inv_stage<UNI, NB, 2, p>(r[p], w2, c, bnd[p]);
+        if constexpr (!LAZY && NB >= 1) inv_end<NB, p>(r[p], c, bnd[p]);
+    FHE_R8_BANKS_END
+}
+
+// a.batch / a.rows count GROUPS of P polynomials (the host passes batch / P): the tile order of tile_at, in units of P polynomials
+template <bool INV, int WB, int MODE, int P, bool X1P>
+FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
+    static_assert(WB == 3, "row8 batched: 8 waves per tile (12 stages): the banked blocks exist for full radix-8 steps only");
+    static_assert(P >= 2 && P <= 4, "row8 batched: register banks 0..3");
+    static_assert(!(INV && MODE != 0), "row8: the inverse pass that ends a transform is ntt_static.h's");
+    constexpr uint32_t tileLog = 9u + (uint32_t)WB;
+    constexpr uint32_t threads = 64u << WB;
+    constexpr int WLOW         = 3 - WB;
+    constexpr uint32_t x1Set   = X1P ? (uint32_t)kRegion << WB : 0u;  // LDS words between the X1 regions of two polynomials
+    const uint32_t t     = FHE_TID;
+    const uint32_t wv    = FHE_UNIFORM(t >> 6);
+    const uint32_t logN  = a.logN;
+    const uint32_t trLog = logN - tileLog;
+    uint64_t* reg = lds + (size_t)wv * kRegion;  // this wave's region
+    uint64_t r[P][8];
+    const TileAt at      = tile_at(a, FHE_BID, trLog, a.xcdSwizzle != 0);
+    const uint32_t jbase = at.tr << tileLog;
+    const uint32_t rit   = at.rit;
+    const uint32_t tb0   = at.tb * (uint32_t)P;  // the group's first polynomial
+    const uint64_t inRow  = a.inStride ? ((uint64_t)tb0 * a.inStride + a.inFirst + rit) : ((uint64_t)tb0 * a.nLimbs + rit);
+    const uint64_t outRow = a.outStride ? ((uint64_t)tb0 * a.outStride + a.outFirst + rit) : ((uint64_t)tb0 * a.nLimbs + rit);
+    const uint32_t limb = FHE_UNIFORM(a.sel.idx[rit]);
+    const uint64_t q    = FHE_ULOAD64(a.q, limb);
+    const uint64_t twoq = q << 1, nq = 0 - q;
+    const TwPair* tw    = a.tw + ((uint64_t)limb << logN);
+    const uint64_t redc = FHE_ULOAD64(a.red, limb);
+    const BflyConst c{(uint32_t)nq, (uint32_t)(nq >> 32), q, twoq, 0 - twoq, twoq + q, (uint32_t)redc, (uint32_t)(redc >> 32)};
+    // polynomial p of the group: src + p * inStep, dst + p * outStep (words)
+    const uint64_t* src = (a.inDelta ? a.xin + (int64_t)tb0 * a.inDelta + ((uint64_t)(a.inFirst + rit) << logN) : a.xin + (inRow << logN)) + jbase;
+    uint64_t* dst       = a.x + (outRow << logN) + jbase;
+    const int64_t inStep  = a.inDelta ? a.inDelta : (int64_t)((uint64_t)(a.inStride ? a.inStride : a.nLimbs) << logN);
+    const int64_t outStep = (int64_t)((uint64_t)(a.outStride ? a.outStride : a.nLimbs) << logN);
+    auto x1 = [](int rr) { return (uint32_t)kRegion * ((uint32_t)rr >> WLOW) + (64u << WB) * ((uint32_t)rr & ((1u << WLOW) - 1u)); };
+#define FHE_R8_LANE()                 \
+    uint32_t tq_ = t;                 \
+    FHE_R8_OPAQUE_V(tq_);             \
+    const uint32_t l = tq_ & 63u, lhi = l >> 3, llo = l & 7u; \
+    (void)lhi, (void)llo
+// one exchange of a wave through its region: write pattern WR(k), read pattern RD(k) (words from the two lane bases)
+#define FHE_R8_XCHG(pp, WBASE, WR, RBASE, RD)             \
+    do {                                                  \
+        FHE_WAVE_SYNC();                                  \
+        uint64_t* Lw_ = (WBASE);                          \
+        _Pragma("unroll") for (int k = 0; k < 8; ++k)     \
+            FHE_LDS_ST(Lw_[WR], r[pp][k]);                \
+        FHE_WAVE_SYNC();                                  \
+        const uint64_t* Lr_ = (RBASE);                    \
+        _Pragma("unroll") for (int k = 0; k < 8; ++k)     \
+            FHE_LDS_LD(r[pp][k], Lr_[RD]);                \
+    } while (0)
+
+    if constexpr (!INV) {
+        using S = FwdSched<WB, (MODE == 9 ? 2 : MODE)>;
+        {   // the loads of all P polynomials first: polynomial 0's butterflies wait for its own eight only
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                const uint64_t* s0 = src + (int64_t)p * inStep + tq_;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    r[p][k] = FHE_GLD(&s0[threads * (uint32_t)k]);
+            FHE_R8_BANKS_END
+        }
+        fwd_step_b<true, WB, S::sweep(0), P>(r, tw, at.tr, 6 + WB, logN, c, S::sweep(0) ? 2u : (uint32_t)S::before(0));
+        {   // X1: 576 w + 64 c + 8 k + m, the only exchange between waves
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                if constexpr (!X1P && p > 0)
+                    FHE_SSYNC();  // every wave has read the previous polynomial
+                uint64_t* Lw = lds + (uint32_t)p * x1Set + tq_;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    FHE_LDS_ST(Lw[x1(k)], r[p][k]);
+                FHE_SSYNC();
+                const uint64_t* Lr = reg + (uint32_t)p * x1Set + l;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    FHE_LDS_LD(r[p][k], Lr[64 * k]);
+            FHE_R8_BANKS_END
+        }
+        fwd_step_b<true, 3, S::sweep(1), P>(r, tw, (jbase >> 9) + wv, 6, logN, c, S::sweep(1) ? 2u : (uint32_t)S::before(1));
+        {   // X2: 72 c + 8 k + m
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                FHE_R8_XCHG(p, reg + l, 72 * k, reg + 72u * lhi + llo, 8 * k);
+            FHE_R8_BANKS_END
+            fwd_step_b<false, 3, S::sweep(2), P>(r, tw, (jbase >> 6) + (wv << 3) + lhi, 3, logN, c, S::sweep(2) ? 2u : (uint32_t)S::before(2));
+        }
+        {   // X3: FC3(c) + 33 k + m
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                FHE_R8_XCHG(p, reg + fc3(lhi) + llo, 33 * k, reg + fc3(lhi) + 33u * llo, k);
+            FHE_R8_BANKS_END
+            fwd_step_b<false, 3, S::sweep(3), P>(r, tw, (jbase >> 3) + (wv << 6) + l, 0, logN, c, S::sweep(3) ? 2u : (uint32_t)S::before(3));
+        }
+        {   // per polynomial: canonical form, X4 (FC4(c) + k + 36 m, read back in the c-layout = the store layout), its stores
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                if (a.canonStep != 0xffffffffu) {
+                    red_all<p>(r[p], c);
+                    csub_all<p>(r[p], q);
+                }
+                FHE_R8_XCHG(p, reg + fc4(lhi) + llo, 36 * k, reg + lhi + 36u * llo, fc4((uint32_t)k));
+                uint64_t* d0 = dst + (int64_t)p * outStep + (wv << 9) + l;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    FHE_GST(&d0[64u * (uint32_t)k], r[p][k]);
+            FHE_R8_BANKS_END
+        }
+    }
+    else {
+        {   // c-layout loads of all P polynomials, then X4 backwards into the m-layout
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                const uint64_t* s0 = src + (int64_t)p * inStep + (wv << 9) + l;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    r[p][k] = FHE_GLD(&s0[64u * (uint32_t)k]);
+            FHE_R8_BANKS_END
+            FHE_R8_BANKS(p)
+                FHE_R8_XCHG(p, reg + lhi + 36u * llo, fc4((uint32_t)k), reg + fc4(lhi) + llo, 36 * k);
+            FHE_R8_BANKS_END
+            inv_step_b<false, 3, false, P>(r, tw, (jbase >> 3) + (wv << 6) + l, 0, logN, c);
+        }
+        {   // X3 backwards
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                FHE_R8_XCHG(p, reg + fc3(lhi) + 33u * llo, k, reg + fc3(lhi) + llo, 33 * k);
+            FHE_R8_BANKS_END
+            inv_step_b<false, 3, false, P>(r, tw, (jbase >> 6) + (wv << 3) + lhi, 3, logN, c);
+        }
+        {   // X2 backwards
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                FHE_R8_XCHG(p, reg + 72u * lhi + llo, 8 * k, reg + l, 72 * k);
+            FHE_R8_BANKS_END
+        }
+        inv_step_b<true, 3, false, P>(r, tw, (jbase >> 9) + wv, 6, logN, c);
+        {   // X1 backwards, between the waves (the wave's own exchanges of every polynomial are behind it)
+            FHE_R8_LANE();
+            FHE_R8_BANKS(p)
+                if constexpr (!X1P && p > 0)
+                    FHE_SSYNC();  // every wave has read the previous polynomial
+                FHE_WAVE_SYNC();
+                uint64_t* Lw = reg + (uint32_t)p * x1Set + l;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    FHE_LDS_ST(Lw[64 * k], r[p][k]);
+                FHE_SSYNC();
+                const uint64_t* Lr = lds + (uint32_t)p * x1Set + tq_;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    FHE_LDS_LD(r[p][k], Lr[x1(k)]);
+            FHE_R8_BANKS_END
+            // the column pass that follows reduces on the way in: no closing reductions
+            inv_step_b<true, WB, true, P>(r, tw, at.tr, 6 + WB, logN, c);
+            FHE_R8_BANKS(p)
+                uint64_t* d0 = dst + (int64_t)p * outStep + tq_;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    FHE_GST(&d0[threads * (uint32_t)k], r[p][k]);
+            FHE_R8_BANKS_END
+        }
+    }
+#undef FHE_R8_XCHG
+#undef FHE_R8_LANE
+}
+#undef FHE_R8_BANKS
+#undef FHE_R8_BANKS_END
+
+// 16 P + 48 VGPRs: P = 2 at 80 (6 waves per SIMD: 3 workgroups, 6 tiles per CU), P = 4 at no more than 128 (4 waves: 2 workgroups,
+// 8 tiles); with a set of X1 regions per polynomial LDS sets the residency (P x 36 KiB: 2 workgroups / 1 workgroup per CU)
+constexpr int batched_waves(int P, bool X1P) { return X1P ? (P == 2 ? 4 : 2) : (P == 2 ? 6 : 4); }
+template <bool INV, int WB, int MODE, int P, bool X1P>
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS2(64 << WB, batched_waves(P, X1P)) ntt_row8_batched_kernel(const NttPassArgs a) {
+    FHE_SHARED_U64(lds, (X1P ? P : 1) * (1 << WB) * kRegion);
+    ntt_row8_batched_core<INV, WB, MODE, P, X1P>(a, lds);
 }
 
 }  // namespace r8

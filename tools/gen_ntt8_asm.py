@@ -8,6 +8,12 @@ Gentleman-Sande sums — imported from there), on a register file sized for EIGH
     v[0:35]   the compiler's: addresses and up to 7 per-lane twiddle pairs (28 registers)
     v[36:47]  the temporaries of ONE butterfly slot (12 registers)
     v[48:63]  the lane's 8 residues (residue k = v[48+2k : 49+2k])
+    v[64:111] banks 1..3 of the batched row pass: the same 8 residues of the next polynomials of the batch (residue k of bank p =
+              v[48+16p+2k : 49+16p+2k]); their blocks share the temporaries and the twiddle operands
+
+The blocks of banks 1..3 are written ONCE, to ntt_bfly8_banked.h, with the residue registers spelled as macros (FHE_BKV<n>, FHE_BKP<k>);
+ntt_row8.h includes that file once per bank.  For every bank the generator checks that the expanded text is the text it generates
+(and simulates) for that bank's registers.  Only what the batched kernel (12 stages) calls is emitted there.
 
 One butterfly at a time: with 8 waves per SIMD the two wait states between a VALU carry write and its reader are filled by
 other waves; the second interleaved butterfly of the 16-residue kernel buys nothing there (tools/occbench.hip,
@@ -32,6 +38,8 @@ ROOT = os.path.dirname(HERE)
 OUT = os.path.join(ROOT, "openfhe-development_amd", "csrc", "ntt_bfly8_pinned.h")
 
 DATA0, TEMP0 = 48, 36
+OUT_B = os.path.join(ROOT, "openfhe-development_amd", "csrc", "ntt_bfly8_banked.h")
+BANKS = (1, 2, 3)  # banks of the batched row pass beside bank 0; bank p starts at v[DATA0 + 16 p]
 g.DATA0 = DATA0
 g.CSUB_TMP = (TEMP0, TEMP0 + 2, TEMP0 + 4, TEMP0 + 6)
 M64 = g.M64
@@ -100,10 +108,11 @@ def inv_plan(bLo=0, bHi=2, lazy_out=False, B0=3):
 
 
 # ---- simulation ------------------------------------------------------------------------------------------------------------
-def check_blocks():
+def check_blocks(iters=3000, steps=60):
+    """simulates the blocks on the bank g.DATA0 points at"""
     rnd = random.Random(11)
     run, St, sched = g.run, g.St, g.schedule
-    for it in range(3000):
+    for it in range(iters):
         q = g.rand_modulus(rnd) if it % 4 else (1 << 60) - 16383
         w = [rnd.randrange(q), rnd.randrange(q)]
         S = St()
@@ -156,7 +165,7 @@ def check_blocks():
     for (bLo, bHi) in ((0, 2), (1, 2), (2, 2)):
         for lazy in (False, True):
             pre, K, end, final = inv_plan(bLo, bHi, lazy)
-            for it in range(60):
+            for it in range(steps):
                 q = (1 << 60) - 16383 if it < 4 else g.rand_modulus(rnd)
                 slow = it % 5 == 4
                 S = St()
@@ -283,8 +292,84 @@ def op_table(ops, n):
 RANGES = ((0, 2), (1, 2), (2, 2))  # inverse stage ranges of a radix-8 step: all three bits, or the top 2 / top 1 (the step on the wave field of tiles with 4 / 2 waves)
 
 
+def bank_text(data0):
+    """what the batched row pass calls, for the bank whose residues start at v[data0]: forward stages, the full lazy-inverse step,
+    the sweep of the first forward stage, the closing reduction and conditional subtraction"""
+    g.DATA0 = data0
+    H = []
+    for b in range(3):
+        prs = stage_pairs(b)
+        for cls in ("v", "s"):
+            fn = []
+            for i in range(0, 4, 2):
+                (a0, a1, ga), (b0, b1, gb) = prs[i], prs[i + 1]
+                name = f"bfly2_fwd_{cls}_b{b}_{i // 2}"
+                H.append(emit_pair_fn(name, (a0, a1), (b0, b1), cls, g.fwd_stream(T, R(a0), R(a1), 0), g.fwd_stream(T, R(b0), R(b1), 1)))
+                fn.append(f"    {name}(r, w[{ga}], w[{gb}], c);\n")
+            H.append(f"__device__ __forceinline__ void stage_fwd_{cls}_b{b}(uint64_t (&r)[8], const TwPair (&w)[4], const BflyConst c) {{\n"
+                     + "".join(fn) + "}\n")
+    pre, K, _, _ = inv_plan(0, 2, True)
+    for b in range(3):
+        H.append(emit_reduce_fn(f"inv_pre_full_b{b}", pre[b]))
+        prs = stage_pairs(b)
+        for cls in ("v", "s"):
+            fn = []
+            for i in range(0, 4, 2):
+                (a0, a1, ga), (b0, b1, gb) = prs[i], prs[i + 1]
+                fname = f"bfly2_invl_{cls}_full_b{b}_{i // 2}"
+                H.append(emit_pair_fn(fname, (a0, a1), (b0, b1), cls, g.inv_lazy_stream(T, R(a0), R(a1), 0, f"%[k{K[b][i]}]"),
+                                      g.inv_lazy_stream(T, R(b0), R(b1), 1, f"%[k{K[b][i + 1]}]")))
+                fn.append(f"    {fname}(r, w[{ga}], w[{gb}], c);\n")
+            H.append(f"__device__ __forceinline__ void stage_invl_{cls}_full_b{b}(uint64_t (&r)[8], const TwPair (&w)[4], "
+                     f"const BflyConst c) {{\n    inv_pre_full_b{b}(r, c);\n" + "".join(fn) + "}\n")
+    H.append(emit_reduce_fn("inv_end_full", inv_plan(0, 2, False)[2]))
+    for i in range(2):
+        H.append(emit_csub_fn(f"csub4_{i}", [4 * i + j for j in range(4)]))
+    H.append("""__device__ __forceinline__ void csub8(uint64_t (&r)[8], uint64_t m) {
+    const uint64_t negm = 0 - m;
+    csub4_0(r, m, negm);
+    csub4_1(r, m, negm);
+}
+""")
+    H.append(emit_reduce_fn("red8", [("r", k) for k in range(8)]))
+    H.append(emit_reduce_fn("red4_a2", [("r", k) for k in range(8) if not (k >> 2) & 1]))
+    g.DATA0 = DATA0
+    return "".join(H)
+
+
+SENTINEL = 200  # a register range no block uses: the template is generated there and its registers are replaced by macros
+
+
+def banked_header():
+    tmpl = bank_text(SENTINEL)
+    tmpl = re.sub(r"v\[(2\d\d):2\d\d\]", lambda m: f'" FHE_BKP{(int(m.group(1)) - SENTINEL) // 2} "', tmpl)
+    tmpl = re.sub(r"\bv(2\d\d)\b", lambda m: f'" FHE_BKV{int(m.group(1)) - SENTINEL} "', tmpl)
+    for bank in BANKS:  # the template with the bank's registers is the text generated for that bank, and that text simulates
+        base = DATA0 + 16 * bank
+        exp = re.sub(r'" FHE_BKP(\d+) "', lambda m: f"v[{base + 2 * int(m.group(1))}:{base + 2 * int(m.group(1)) + 1}]", tmpl)
+        exp = re.sub(r'" FHE_BKV(\d+) "', lambda m: f"v{base + int(m.group(1))}", exp)
+        assert exp == bank_text(base), f"bank {bank}: the macro form does not expand to the generated text"
+        g.DATA0 = base
+        check_blocks(300, 10)
+        g.DATA0 = DATA0
+    defs = []
+    for i, bank in enumerate(BANKS):
+        base = DATA0 + 16 * bank
+        defs.append(f"#{'if' if i == 0 else 'elif'} FHE_BK == {bank}\n"
+                    + "".join(f'#define FHE_BKV{n} "v{base + n}"\n' for n in range(16))
+                    + "".join(f'#define FHE_BKP{k} "v[{base + 2 * k}:{base + 2 * k + 1}]"\n' for k in range(8)))
+    defs.append("#else\n#error \"FHE_BK: bank 1, 2 or 3\"\n#endif\n")
+    undefs = "".join(f"#undef FHE_BKV{n}\n" for n in range(16)) + "".join(f"#undef FHE_BKP{k}\n" for k in range(8))
+    return ("""// GENERATED by tools/gen_ntt8_asm.py — do not edit; edit the generator and re-run it.
+// The blocks of ntt_bfly8_pinned.h that the batched row pass (ntt_row8.h) runs on register banks 1..3: residue k of bank p =
+// v[48+16p+2k : 49+16p+2k], same temporaries v[36:47], same twiddle operands.  No include guard: ntt_row8.h includes this file once per
+// bank, inside namespace fhe::r8::bk<p>, with FHE_BK = p; the residue registers are the macros FHE_BKV<n> (32-bit) / FHE_BKP<k> (pair).
+""" + "".join(defs) + tmpl + undefs)
+
+
 def main():
     check_blocks()
+    banked = banked_header()
     H = []
     H.append("""// GENERATED by tools/gen_ntt8_asm.py — do not edit; edit the generator and re-run it.
 // In-place gfx950 butterflies of the 8-residues-per-lane row pass (ntt_row8.h): residue k = v[48+2k:49+2k], the one butterfly
@@ -361,12 +446,13 @@ struct RedOp {
     H.append("}  // namespace r8\n}  // namespace fhe\n#endif\n#endif\n")
     text = "".join(H)
     if "--check" in sys.argv:
-        if open(OUT).read() != text:
-            print("ntt_bfly8_pinned.h is stale: run python tools/gen_ntt8_asm.py")
+        if open(OUT).read() != text or open(OUT_B).read() != banked:
+            print("ntt_bfly8_pinned.h / ntt_bfly8_banked.h is stale: run python tools/gen_ntt8_asm.py")
             return 1
         print("ntt_bfly8_pinned.h is up to date; all blocks simulated OK")
         return 0
     open(OUT, "w").write(text)
+    open(OUT_B, "w").write(banked)
     nf = g.count(g.schedule([g.fwd_stream(T, R(0), R(1), 0)]))
     print(f"wrote {OUT}: forward butterfly {nf} VALU in one slot; inverse plans "
           + ", ".join(f"{s}: pre {sum(len(x) for x in inv_plan(*s)[0].values())} end {len(inv_plan(*s)[2])}" for s in RANGES))
