@@ -490,6 +490,42 @@ fhe_status fhe_bfv_eval_mult_relin_behz(fhe_behz* plan, fhe_ks_plan* ks, const f
                                         const uint64_t* a1, const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1,
                                         uint32_t batch, void* ws, size_t wsBytes, void* stream);
 
+/* ---- a18: BFV EvalMult, HPS family ----------------------------------------------------------------------------
+ * LeveledSHEBFVRNS::EvalMult for the multiplication techniques HPS (1), HPSPOVERQ (2) and HPSPOVERQLEVELED (3, the
+ * reference's default; enum MultiplicationTechnique, constants-defs.h:97), without relinearisation
+ * (src/pke/lib/scheme/bfvrns/bfvrns-leveledshe.cpp:198-302, 354-412, 435-438).
+ * fhe_param_hps_r returns the auxiliary basis R the reference picks (bfvrns-cryptoparameters.cpp:75, 126-139):
+ * r_0 = PreviousPrime(q_{numQ-1}, 2N), r_j = PreviousPrime(r_{j-1}, 2N) with their minimum primitive 2N-th roots; numQ + 1
+ * moduli for HPS, numQ otherwise.  Returns the count, 0 on a bad argument.
+ * fhe_hps_create builds, in the call, every table of CryptoParametersBFVRNS::PrecomputeCRTTables' HPS block (:143-265, 267-665)
+ * for Q (context limbs qLimbIdx) and R (rLimbIdx), for every level l = 0 .. numQ-1 with HPSPOVERQ[LEVELED], from the moduli with
+ * 64-bit modular arithmetic.  numQ + numR <= 256.  fhe_hps_table reads a derived table back (ids and layouts: see the definition
+ * in fhe_hip.cpp; doubles as bit patterns); it returns the table's length in 64-bit words, 0 if the plan has no such table.
+ * fhe_bfv_eval_mult_hps: inputs [batch][numQ][N] EVALUATION -> outputs [batch][numQ][N], COEFFICIENT as the reference leaves
+ * them, or EVALUATION when outEval != 0 (then fhe_keyswitch_hybrid_acc relinearises).  sizeQl = l + 1 is the number of Q limbs the
+ * product is computed over: numQ for HPS and HPSPOVERQ; for HPSPOVERQLEVELED the caller's numQ - levelsDropped (FindLevelsToDrop is
+ * host-side noise estimation and stays in pke).  A wrong sizeQl or too small a workspace is an error and enqueues nothing.  The call
+ * builds nothing lazily, allocates nothing and does not synchronise: it can be captured into a graph.
+ * Sequences (the replaced reference lines):
+ *   HPS        a, b: ExpandCRTBasis Q -> QR (:223-235); product: ScaleAndRound QR -> R, SwitchCRTBasis R -> Q (:368-383)
+ *   HPSPOVERQ  a: ExpandCRTBasis (:239-246); b: FastExpandCRTBasisPloverQ (:256-261); product: ScaleAndRound QR -> Q (:385-395)
+ *   LEVELED    sizeQl == numQ as HPSPOVERQ; below: a: ScaleAndRound Q -> Q_l, ExpandCRTBasis Q_l -> Q_lR_l (:274-287);
+ *              b: FastExpandCRTBasisPloverQ from Q (:289-301); product: ScaleAndRound Q_lR_l -> Q_l, ExpandCRTBasisQlHat (:397-411)
+ * FastExpandCRTBasisPloverQ, the HPS tail and the LEVELED head run as ONE kernel each that keeps the middle basis in registers
+ * (p_over_q_expand_kernel, scale_round_switch_kernel; bfv_kernels.h) while every basis involved has at most 16 limbs (HPS: numQ <= 15,
+ * since R has numQ + 1); beyond that the same residues come from the separate launches.
+ * Not covered: ciphertexts with more than two elements, and the compressed-ciphertext branch (sizeQ < sizeQM, :237-262). */
+typedef struct fhe_hps fhe_hps;
+uint32_t   fhe_param_hps_r(uint32_t logN, uint32_t numQ, const uint64_t* q, int technique, uint64_t* r, uint64_t* psiR);
+fhe_status fhe_hps_create(fhe_ctx* ctx, const uint32_t* qLimbIdx, uint32_t numQ, const uint32_t* rLimbIdx, uint32_t numR,
+                          uint64_t t, int technique, fhe_hps** out);
+void       fhe_hps_destroy(fhe_hps* plan);
+size_t     fhe_hps_table(const fhe_hps* plan, int tableId, uint32_t level, uint64_t* out, size_t cap);
+size_t     fhe_bfv_eval_mult_hps_workspace_bytes(const fhe_hps* plan, uint32_t sizeQl, uint32_t batch);
+fhe_status fhe_bfv_eval_mult_hps(fhe_hps* plan, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
+                                 uint64_t* d0, uint64_t* d1, uint64_t* d2, uint32_t sizeQl, int outEval, uint32_t batch,
+                                 void* ws, size_t wsBytes, void* stream);
+
 /* ---- parity helper: whole-tower checksums ----------------------------------------------------------------
  * out[row] = { sum_i w_i, sum_i (2i + 1) * w_i } mod 2^64 over the row's N words, for every limb-row of x[rows][N] (rows = batch *
  * nLimbs; the second word depends on the ORDER of the words); out is DEVICE memory, uint64_t[rows][2].  One read of the batch: bench.py and the full-shape tests compare EVERY

@@ -7,6 +7,8 @@
 //   FastBaseConvqToBskMontgomery (core)       :1731-1774     behz_q_to_bsk_kernel
 //   FastRNSFloorq                             :1791-1840     behz_floorq_kernel
 //   FastBaseConvSK                            :1845-1929     behz_conv_sk_kernel
+//   FastExpandCRTBasisPloverQ (one launch)    :1151-1164     p_over_q_expand_kernel
+//   ScaleAndRound + SwitchCRTBasis (one launch) :1513-1590, 1008-1085   scale_round_switch_kernel<KEEP_MID>
 // One coefficient per lane; limbs of that coefficient are 8-byte loads that are contiguous across lanes
 // (coalesced per limb).  All tables are wave-uniform (scalar cache).  Integer results are exact residues; the one
 // floating-point quantity (ScaleAndRound's nu) is accumulated in the reference's order with contraction disabled.
@@ -480,6 +482,147 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) behz_conv_sk_wide_kernel(const BehzA
         a = mul_shoup(a, c.w, c.wp, qj);
         *tv_at(g.outQ, b, j, g.logN, ri) = sub_mod(v, a, qj);
     }
+}
+
+// ---- HPS family: conversions that keep the middle basis in registers (fhe_bfv_eval_mult_hps) ------------------------------------
+// LeveledSHEBFVRNS::EvalMult with HPS / HPSPOVERQ / HPSPOVERQLEVELED (bfvrns-leveledshe.cpp:222-302, 368-412) chains two
+// per-coefficient conversions three times: FastExpandCRTBasisPloverQ (approximate Q -> R_l, exact R_l -> Q_l), the HPS tail
+// (ScaleAndRound QR -> R, exact R -> Q) and the LEVELED head (ScaleAndRound Q -> Q_l, exact Q_l -> R_l).  The two kernels below do each
+// chain in one launch: the first conversion's residues stay in registers, so the middle tower is not written and read back.
+// Conventions are the conversion kernel's (basis_kernels.h): source residues loaded once with a clamped row index, vector tables
+// padded to kMaxBfvLimbs and matrices stored [target][kMaxBfvLimbs], output limbs one at a time as column sums of 30-bit halves
+// (dot_row_mod<true>), the two floating-point sums in the reference's order.  Every basis that is held in registers has at most
+// kMaxBfvLimbs = 16 limbs; beyond that the composite issues the separate launches (same residues, see fhe_hip.cpp).
+struct HpsSwitchTables {       // exact SwitchCRTBasis S -> D (dcrtpoly-impl.h:1008-1085) of residues held in registers
+    const TwPair* hatInv;      // [16]  [(S/s_i)^-1]_{s_i}
+    const uint64_t* srcQ;      // [16]  (padding = 1)
+    const double* srcQInv;     // [16]  1.0 / s_i
+    const uint64_t* hatMod;    // [nDst][16]  [S/s_i]_{d_j}
+    const uint64_t* dstQ;      // [nDst]
+    const uint64_t* dstMu;     // [nDst][2]
+    const uint64_t* alphaMod;  // [nSrc+1][nDst]  [alpha*S]_{d_j}
+    uint32_t nSrc, nDst;
+};
+struct HpsScaleTables {        // ScaleAndRound I -> O (dcrtpoly-impl.h:1513-1590)
+    const uint64_t* tab;       // [sizeO][16]  columns i < sizeI of tOSHatInvModsDivsModo[j]
+    const TwPair* last;        // [16]  its last column tOSHatInvModsDivsModo[j][sizeI], as a Shoup pair modulo o_j
+    const double* frac;        // [16]
+    const uint64_t* o;         // [16]  (padding = 1)
+    const uint64_t* mu;        // [16][2]
+    uint32_t sizeI, sizeO;
+};
+// y (residues over S, all < s_i) -> rows of `out` over D; y is overwritten with y_i * [(S/s_i)^-1]_{s_i}
+FHE_HD void switch_exact_regs(uint64_t (&y)[kMaxBfvLimbs], const HpsSwitchTables& t, const TowerView out, uint32_t b, uint32_t logN,
+                              uint32_t ri) {
+    double nu = 0.5;  // :1056-1063, i ascending, one rounding per multiply and per add
+#pragma unroll
+    for (int i = 0; i < kMaxBfvLimbs; ++i) {
+        const TwPair c    = uload_pair(t.hatInv, i);
+        const uint64_t si = FHE_ULOAD64(t.srcQ, i);
+        const double sinv = FHE_ULOADF64(t.srcQInv, i);
+        if (i < (int)t.nSrc) {
+            y[i] = mul_shoup(y[i], c.w, c.wp, si);
+            nu += (double)y[i] * sinv;
+        }
+    }
+    const uint32_t alpha = (uint32_t)nu;
+    for (uint32_t j = 0; j < t.nDst; ++j) {
+        const uint64_t dj = FHE_ULOAD64(t.dstQ, j);
+        const uint64_t v  = dot_row_mod<true>(y, t.hatMod + (uint64_t)j * kMaxBfvLimbs, t.nSrc, dj, FHE_ULOAD64(t.dstMu, 2 * j),
+                                             FHE_ULOAD64(t.dstMu, 2 * j + 1));
+        *tv_at(out, b, j, logN, ri) = sub_mod(v, t.alphaMod[(uint64_t)alpha * t.nDst + j], dj);
+    }
+}
+
+// FastExpandCRTBasisPloverQ (dcrtpoly-impl.h:1151-1164) in one launch: in (nSrc rows over Q, COEFFICIENT) -> out = [Q_l | R_l]
+struct POverQExpandArgs {
+    TowerView in, out;       // out: rows [0, sw.nDst) = Q_l, rows [sw.nDst, sw.nDst + sw.nSrc) = R_l
+    const TwPair* hatInv;    // [16]  mNegRlQHatInvModq (or mNegRlQlHatInvModq)
+    const uint64_t* srcQ;    // [16]
+    const uint64_t* hatMod;  // [nR_l][16]  [q_i^-1]_{r_j}
+    const uint64_t* r;       // [16]
+    const uint64_t* muR;     // [16][2]
+    HpsSwitchTables sw;      // R_l -> Q_l
+    uint32_t nSrc, logN, batch;
+};
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) p_over_q_expand_kernel(const POverQExpandArgs g) {
+    const uint64_t gid = (uint64_t)FHE_BID * kThreads + FHE_TID;
+    if (gid >= ((uint64_t)g.batch << g.logN))
+        return;
+    const uint32_t b = (uint32_t)(gid >> g.logN), ri = (uint32_t)gid & ((1u << g.logN) - 1u);
+    uint64_t y[kMaxBfvLimbs], z[kMaxBfvLimbs];
+    load_rows(y, g.in, b, g.nSrc, g.logN, ri);
+#pragma unroll
+    for (int i = 0; i < kMaxBfvLimbs; ++i) {
+        const TwPair c    = uload_pair(g.hatInv, i);
+        const uint64_t qi = FHE_ULOAD64(g.srcQ, i);
+        if (i < (int)g.nSrc)
+            y[i] = mul_shoup(y[i], c.w, c.wp, qi);
+    }
+    // ApproxSwitchCRTBasis Q -> R_l (:900-915): exact residues of the 128-bit sums
+#pragma unroll
+    for (int j = 0; j < kMaxBfvLimbs; ++j) {
+        // (entries at and above R_l's size are never read.  They are given a value the compiler cannot fold: with a constant here it
+        // specialises the second conversion per limb count — 256 VGPRs + 164 AGPRs, one wave per SIMD, instead of 84 VGPRs)
+        z[j] = y[j];
+        if (j < (int)g.sw.nSrc) {
+            z[j] = dot_row_mod<true>(y, g.hatMod + (uint64_t)j * kMaxBfvLimbs, g.nSrc, FHE_ULOAD64(g.r, j), FHE_ULOAD64(g.muR, 2 * j),
+                                     FHE_ULOAD64(g.muR, 2 * j + 1));
+            *tv_at(g.out, b, g.sw.nDst + j, g.logN, ri) = z[j];
+        }
+    }
+    switch_exact_regs(z, g.sw, g.out, b, g.logN, ri);  // SwitchCRTBasis R_l -> Q_l
+}
+
+// ScaleAndRound I -> O followed by the exact SwitchCRTBasis O -> D of its result.
+//   KEEP_MID = false: the HPS tail (QR -> R -> Q); only the D rows are stored.
+//   KEEP_MID = true : the HPSPOVERQLEVELED head (Q -> Q_l, then Q_l -> R_l); both parts are stored = the expanded operand.
+struct ScaleSwitchArgs {
+    TowerView in, own;        // input-basis rows, output-basis rows of the same tower
+    TowerView outMid, outDst;
+    HpsScaleTables sr;
+    HpsSwitchTables sw;
+    uint32_t logN, batch;
+};
+template <bool KEEP_MID>
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) scale_round_switch_kernel(const ScaleSwitchArgs g) {
+    const uint64_t gid = (uint64_t)FHE_BID * kThreads + FHE_TID;
+    if (gid >= ((uint64_t)g.batch << g.logN))
+        return;
+    const uint32_t b = (uint32_t)(gid >> g.logN), ri = (uint32_t)gid & ((1u << g.logN) - 1u);
+    uint64_t x[kMaxBfvLimbs], mid[kMaxBfvLimbs];
+    load_rows(x, g.in, b, g.sr.sizeI, g.logN, ri);
+    load_rows(mid, g.own, b, g.sr.sizeO, g.logN, ri);
+    double nu = 0.5;
+#pragma unroll
+    for (int i = 0; i < kMaxBfvLimbs; ++i) {
+        const double f = FHE_ULOADF64(g.sr.frac, i);
+        if (i < (int)g.sr.sizeI)
+            nu += f * (double)x[i];  // :1543-1548, i ascending
+    }
+    // isConvertableToNativeInt(nu) split as in scale_round_kernel: a 64-bit or a 128-bit integer conversion of nu.  (The residue
+    // of that integer modulo o_j is one number whichever way it is reduced; one Barrett reduction serves both branches.)
+    uint64_t alo, ahi = 0;
+    if (nu <= 18446744073709551616.0)
+        alo = (uint64_t)nu;
+    else {
+        ahi = (uint64_t)(nu * (1.0 / 18446744073709551616.0));
+        alo = (uint64_t)(nu - (double)ahi * 18446744073709551616.0);
+    }
+#pragma unroll
+    for (int j = 0; j < kMaxBfvLimbs; ++j) {
+        if (j < (int)g.sr.sizeO) {
+            const uint64_t oj = FHE_ULOAD64(g.sr.o, j), mlo = FHE_ULOAD64(g.sr.mu, 2 * j), mhi = FHE_ULOAD64(g.sr.mu, 2 * j + 1);
+            const TwPair c    = uload_pair(g.sr.last, j);
+            uint64_t v        = dot_row_mod<true>(x, g.sr.tab + (uint64_t)j * kMaxBfvLimbs, g.sr.sizeI, oj, mlo, mhi);
+            v                 = add_mod(v, mul_shoup(mid[j], c.w, c.wp, oj), oj);
+            v                 = add_mod(v, barrett128(u128w{alo, ahi}, oj, mlo, mhi), oj);
+            mid[j]            = v;
+            if (KEEP_MID)
+                *tv_at(g.outMid, b, j, g.logN, ri) = v;
+        }
+    }
+    switch_exact_regs(mid, g.sw, g.outDst, b, g.logN, ri);
 }
 
 }  // namespace fhe

@@ -3704,6 +3704,472 @@ extern "C" fhe_status fhe_bfv_eval_mult_relin_behz(fhe_behz* bz, fhe_ks_plan* p,
     return keyswitch_run(p, key, d2, p->sizeQ, batch, c0, c1, (uint64_t*)(w + nrB), lay, st, true);
 }
 
+// ------------------------------------------------------------------------------------------------
+// BFV EvalMult, HPS family (HPS, HPSPOVERQ, HPSPOVERQLEVELED)
+// ------------------------------------------------------------------------------------------------
+// The plan derives every table of CryptoParametersBFVRNS::PrecomputeCRTTables' HPS block (bfvrns-cryptoparameters.cpp:143-665)
+// from the moduli with 64-bit modular arithmetic.  The reference forms X = t*M*[(B/s)^-1]_s as a big integer and stores
+// floor(X/s) mod o and (X mod s)/s; with o | M, floor(X/s) = -(X mod s) * s^-1 (mod o), and X/o_j = t*(M/o_j)*[(B/o_j)^-1]_{o_j}
+// is a product of residues — the same numbers.
+struct fhe_hps {
+    fhe_ctx* ctx;
+    uint32_t numQ, numR;
+    int technique;
+    uint64_t t;
+    std::vector<uint32_t> qIdx, rIdx;
+    std::vector<uint64_t> q, r;
+    struct Level {
+        uint32_t L = 0, Lr = 0, nApprox = 0;  // limbs of Q_l, of R_l, and source limbs of the approximate Q -> R_l conversion
+        std::vector<uint32_t> idx;            // context limbs of [Q_l | R_l]
+        fhe_conv* qToR    = nullptr;          // ExpandCRTBasis Q_l -> R_l
+        fhe_conv* rToQ    = nullptr;          // SwitchCRTBasis R_l -> Q_l
+        fhe_conv* pOverQ  = nullptr;          // FastExpandCRTBasisPloverQ's approximate half (null for HPS)
+        fhe_sr_plan* tail = nullptr;          // HPS: QR -> R;  else Q_lR_l -> Q_l
+        fhe_sr_plan* drop = nullptr;          // Q -> Q_l (levels below the top)
+        std::vector<uint64_t> QlHatModq;
+        // the register-resident kernels (bfv_kernels.h); usable when every basis they hold has at most kMaxBfvLimbs limbs
+        bool fuseExpand = false, fuseTail = false, fuseHead = false;
+        HpsSwitchTables swRQ{}, swQR{};
+        HpsScaleTables scTail{}, scDrop{};
+        const TwPair* exHatInv  = nullptr;
+        const uint64_t *exSrcQ = nullptr, *exHatMod = nullptr, *exR = nullptr, *exMuR = nullptr;
+    };
+    std::vector<Level> lv;
+    std::map<std::pair<int, uint32_t>, std::vector<uint64_t>> tables;  // (table id, level) -> values, for fhe_hps_table
+    std::vector<void*> owned;
+};
+enum {
+    HPS_T_QlHatInvModq = 0, HPS_T_QlHatModr, HPS_T_alphaQlModr, HPS_T_qInv, HPS_T_RlHatInvModr, HPS_T_RlHatModq, HPS_T_alphaRlModq,
+    HPS_T_rInv, HPS_T_tRSHatInvModsDivsModr, HPS_T_tRSHatInvModsDivsFrac, HPS_T_tQlSlHatInvModsDivsModq, HPS_T_tQlSlHatInvModsDivsFrac,
+    HPS_T_negRlQHatInvModq, HPS_T_negRlQlHatInvModq, HPS_T_qInvModr, HPS_T_QlQHatInvModqDivqModq, HPS_T_QlQHatInvModqDivqFrac,
+    HPS_T_QlHatModq, HPS_T_COUNT
+};
+
+extern "C" uint32_t fhe_param_hps_r(uint32_t logN, uint32_t numQ, const uint64_t* q, int technique, uint64_t* r, uint64_t* psiR) {
+    if (!q || !r || !psiR || numQ < 1 || technique < 1 || technique > 3)
+        return 0;
+    const uint32_t numR = technique == 1 ? numQ + 1 : numQ;  // bfvrns-cryptoparameters.cpp:126
+    if (numQ + numR > (uint32_t)kMaxLimbs)
+        return 0;
+    const uint64_t M = 2ull << logN;
+    uint64_t cur     = q[numQ - 1];
+    for (uint32_t j = 0; j < numR; ++j) {  // :75, :135-137
+        cur     = host::previous_prime(cur, M);
+        r[j]    = cur;
+        psiR[j] = host::min_root_of_unity(M, cur);
+    }
+    return numR;
+}
+
+namespace {
+std::vector<uint64_t> head_of(const std::vector<uint64_t>& v, uint32_t n) { return std::vector<uint64_t>(v.begin(), v.begin() + n); }
+uint64_t dbits(double d) {
+    uint64_t u;
+    std::memcpy(&u, &d, 8);
+    return u;
+}
+// plain CRT conversion tables S -> D in the layout of fhe_conv_create_custom: hatInv[nS], hatMod[nS][nD], alpha[nS+1][nD], inv[nS]
+struct CrtTabs {
+    std::vector<uint64_t> hatInv, hatMod, alpha, inv;
+};
+CrtTabs crt_tabs(const std::vector<uint64_t>& S, const std::vector<uint64_t>& D) {
+    const size_t nS = S.size(), nD = D.size();
+    CrtTabs c;
+    c.hatInv.resize(nS), c.hatMod.resize(nS * nD), c.alpha.resize((nS + 1) * nD), c.inv.resize(nS);
+    for (size_t i = 0; i < nS; ++i) {
+        c.hatInv[i] = host::invmod(host::prod_mod(S, (int)i, S[i]), S[i]);
+        c.inv[i]    = dbits(1. / static_cast<double>(S[i]));
+        for (size_t j = 0; j < nD; ++j)
+            c.hatMod[i * nD + j] = host::prod_mod(S, (int)i, D[j]);
+    }
+    for (size_t j = 0; j < nD; ++j) {
+        const uint64_t Sm = host::prod_mod(S, -1, D[j]);
+        for (size_t a = 0; a <= nS; ++a)
+            c.alpha[a * nD + j] = host::mulmod(a % D[j], Sm, D[j]);
+    }
+    return c;
+}
+// ScaleAndRound tables for input basis I, output basis O, B = I u O, factor t * prod(O):
+//   tab[j][i] = floor(X_i / s_i) mod o_j, tab[j][nI] = (X'_j / o_j) mod o_j, frac[i] = (X_i mod s_i) / s_i,
+//   X_i = t * prod(O) * [(B/s_i)^-1]_{s_i},  X'_j = t * prod(O) * [(B/o_j)^-1]_{o_j}
+void sr_tabs(const std::vector<uint64_t>& I, const std::vector<uint64_t>& O, uint64_t t, std::vector<uint64_t>& tab,
+             std::vector<uint64_t>& frac) {
+    const size_t nI = I.size(), nO = O.size();
+    tab.assign(nO * (nI + 1), 0);
+    frac.assign(nI, 0);
+    for (size_t i = 0; i < nI; ++i) {
+        const uint64_t s  = I[i];
+        const uint64_t h  = host::invmod(host::mulmod(host::prod_mod(I, (int)i, s), host::prod_mod(O, -1, s), s), s);
+        const uint64_t Xm = host::mulmod(host::mulmod(t % s, host::prod_mod(O, -1, s), s), h, s);
+        frac[i]           = dbits(static_cast<double>(Xm) / static_cast<double>(s));
+        for (size_t j = 0; j < nO; ++j) {
+            const uint64_t o         = O[j];
+            tab[j * (nI + 1) + i] = host::mulmod((o - Xm % o) % o, host::invmod(s % o, o), o);
+        }
+    }
+    for (size_t j = 0; j < nO; ++j) {
+        const uint64_t o = O[j], hat = host::prod_mod(O, (int)j, o);
+        const uint64_t g = host::invmod(host::mulmod(host::prod_mod(I, -1, o), hat, o), o);
+        tab[j * (nI + 1) + nI] = host::mulmod(host::mulmod(t % o, hat, o), g, o);
+    }
+}
+}  // namespace
+
+static void hps_free_level(fhe_hps::Level& v) {
+    fhe_conv_destroy(v.qToR);
+    fhe_conv_destroy(v.rToQ);
+    fhe_conv_destroy(v.pOverQ);
+    fhe_sr_plan_destroy(v.tail);
+    fhe_sr_plan_destroy(v.drop);
+}
+extern "C" void fhe_hps_destroy(fhe_hps* h) {
+    if (!h)
+        return;
+    for (auto& v : h->lv)
+        hps_free_level(v);
+    for (void* p : h->owned)
+        rt::dfree(p);
+    delete h;
+}
+// device tables of the register-resident kernels: vectors padded to kMaxBfvLimbs, matrices [target][kMaxBfvLimbs]
+static fhe_status hps_switch_tables(fhe_hps* h, const std::vector<uint64_t>& S, const std::vector<uint64_t>& D, const CrtTabs& c,
+                                    HpsSwitchTables* out) {
+    const size_t W = kMaxBfvLimbs, nS = S.size(), nD = D.size();
+    std::vector<TwPair> hatInv(W, TwPair{0, 0});
+    std::vector<uint64_t> srcQ(W, 1), hatMod(nD * W, 0), mu(2 * nD);
+    std::vector<double> inv(W, 0.0);
+    for (size_t i = 0; i < nS; ++i) {
+        hatInv[i] = TwPair{c.hatInv[i], host::shoup(c.hatInv[i], S[i])};
+        srcQ[i]   = S[i];
+        inv[i]    = 1. / static_cast<double>(S[i]);
+        for (size_t j = 0; j < nD; ++j)
+            hatMod[j * W + i] = c.hatMod[i * nD + j];
+    }
+    for (size_t j = 0; j < nD; ++j)
+        host::mu128(D[j], &mu[2 * j]);
+    TwPair* p1;
+    uint64_t *d1, *d2, *d3, *d4, *d5;
+    double* f1;
+    fhe_status s;
+    if ((s = dev_copy(h->owned, hatInv.data(), W, &p1)) || (s = dev_copy(h->owned, srcQ.data(), W, &d1)) ||
+        (s = dev_copy(h->owned, inv.data(), W, &f1)) || (s = dev_copy(h->owned, hatMod.data(), hatMod.size(), &d2)) ||
+        (s = dev_copy(h->owned, D.data(), nD, &d3)) || (s = dev_copy(h->owned, mu.data(), mu.size(), &d4)) ||
+        (s = dev_copy(h->owned, c.alpha.data(), c.alpha.size(), &d5)))
+        return s;
+    *out = HpsSwitchTables{p1, d1, f1, d2, d3, d4, d5, (uint32_t)nS, (uint32_t)nD};
+    return FHE_OK;
+}
+static fhe_status hps_scale_tables(fhe_hps* h, const std::vector<uint64_t>& I, const std::vector<uint64_t>& O,
+                                   const std::vector<uint64_t>& tab, const std::vector<uint64_t>& frac, HpsScaleTables* out) {
+    const size_t W = kMaxBfvLimbs, nI = I.size(), nO = O.size();
+    std::vector<uint64_t> t16(nO * W, 0), o(W, 1), mu(2 * W, 0);
+    std::vector<TwPair> last(W, TwPair{0, 0});
+    std::vector<double> f(W, 0.0);
+    for (size_t j = 0; j < nO; ++j) {
+        for (size_t i = 0; i < nI; ++i)
+            t16[j * W + i] = tab[j * (nI + 1) + i];
+        last[j] = TwPair{tab[j * (nI + 1) + nI], host::shoup(tab[j * (nI + 1) + nI], O[j])};
+        o[j]    = O[j];
+        host::mu128(O[j], &mu[2 * j]);
+    }
+    for (size_t i = 0; i < nI; ++i)
+        std::memcpy(&f[i], &frac[i], 8);
+    uint64_t *d1, *d2, *d3;
+    TwPair* p1;
+    double* f1;
+    fhe_status s;
+    if ((s = dev_copy(h->owned, t16.data(), t16.size(), &d1)) || (s = dev_copy(h->owned, last.data(), W, &p1)) ||
+        (s = dev_copy(h->owned, f.data(), W, &f1)) || (s = dev_copy(h->owned, o.data(), W, &d2)) ||
+        (s = dev_copy(h->owned, mu.data(), mu.size(), &d3)))
+        return s;
+    *out = HpsScaleTables{d1, p1, f1, d2, d3, (uint32_t)nI, (uint32_t)nO};
+    return FHE_OK;
+}
+static fhe_status hps_conv(fhe_hps* h, const std::vector<uint32_t>& sIdx, const std::vector<uint32_t>& dIdx, const uint64_t* hatInv,
+                           const uint64_t* hatMod, const uint64_t* alpha, const uint64_t* inv, fhe_conv** out) {
+    std::vector<double> invd;
+    if (inv) {
+        invd.resize(sIdx.size());
+        std::memcpy(invd.data(), inv, sIdx.size() * 8);
+    }
+    return fhe_conv_create_custom(h->ctx, sIdx.data(), (uint32_t)sIdx.size(), dIdx.data(), (uint32_t)dIdx.size(), hatInv, hatMod, alpha,
+                                  inv ? invd.data() : nullptr, out);
+}
+static fhe_status hps_sr(fhe_hps* h, uint32_t sizeI, const std::vector<uint32_t>& oIdx, const std::vector<uint64_t>& tab,
+                         const std::vector<uint64_t>& frac, fhe_sr_plan** out) {
+    std::vector<double> f(frac.size());
+    std::memcpy(f.data(), frac.data(), frac.size() * 8);
+    return fhe_sr_plan_create(h->ctx, sizeI, oIdx.data(), (uint32_t)oIdx.size(), tab.data(), f.data(), out);
+}
+
+extern "C" fhe_status fhe_hps_create(fhe_ctx* c, const uint32_t* qLimbIdx, uint32_t numQ, const uint32_t* rLimbIdx, uint32_t numR,
+                                     uint64_t t, int technique, fhe_hps** out) {
+    ARG_CHECK(c && qLimbIdx && rLimbIdx && out, "fhe_hps_create: null argument");
+    ARG_CHECK(technique >= 1 && technique <= 3, "fhe_hps_create: technique must be HPS (1), HPSPOVERQ (2) or HPSPOVERQLEVELED (3)");
+    ARG_CHECK(numQ >= 1 && numR == (technique == 1 ? numQ + 1 : numQ), "fhe_hps_create: R has numQ + 1 limbs for HPS, numQ otherwise");
+    ARG_CHECK(numQ + numR <= (uint32_t)kMaxLimbs, "fhe_hps_create: numQ + numR exceeds the row bound of a tower (256)");
+    ARG_CHECK(t >= 2, "fhe_hps_create: bad plaintext modulus");
+    std::vector<uint64_t> q(numQ), r(numR);
+    for (uint32_t i = 0; i < numQ; ++i) {
+        ARG_CHECK(qLimbIdx[i] < c->L, "fhe_hps_create: limb index exceeds context size");
+        q[i] = c->q[qLimbIdx[i]];
+    }
+    for (uint32_t j = 0; j < numR; ++j) {
+        ARG_CHECK(rLimbIdx[j] < c->L, "fhe_hps_create: limb index exceeds context size");
+        r[j] = c->q[rLimbIdx[j]];
+    }
+    RT_CHECK(rt::set_device(c->device));
+    fhe_hps* h = new fhe_hps;
+    h->ctx = c, h->numQ = numQ, h->numR = numR, h->technique = technique, h->t = t, h->q = q, h->r = r;
+    h->qIdx.assign(qLimbIdx, qLimbIdx + numQ);
+    h->rIdx.assign(rLimbIdx, rLimbIdx + numR);
+    const bool hps = technique == 1;
+    auto& T        = h->tables;
+    // level-independent tables
+    {
+        std::vector<uint64_t> qInv(numQ), rInv(numR), qInvModr((size_t)numQ * numR);
+        for (uint32_t i = 0; i < numQ; ++i) {
+            qInv[i] = dbits(1. / static_cast<double>(q[i]));  // :262-265
+            for (uint32_t j = 0; j < numR; ++j)
+                qInvModr[(size_t)i * numR + j] = host::invmod(q[i] % r[j], r[j]);  // :524-530
+        }
+        for (uint32_t j = 0; j < numR; ++j)
+            rInv[j] = dbits(1. / static_cast<double>(r[j]));  // :429-432
+        T[{HPS_T_qInv, 0}] = qInv, T[{HPS_T_rInv, 0}] = rInv, T[{HPS_T_qInvModr, 0}] = qInvModr;
+        sr_tabs(q, r, t, T[{HPS_T_tRSHatInvModsDivsModr, 0}], T[{HPS_T_tRSHatInvModsDivsFrac, 0}]);  // :281-304
+    }
+    const uint32_t nLevels = hps ? 1u : numQ;
+    h->lv.resize(nLevels);
+    fhe_status s = FHE_OK;
+    for (uint32_t l = 0; l < numQ && !s; ++l) {
+        const uint32_t L = l + 1;
+        const std::vector<uint64_t> Ql = head_of(q, L), Qrest(q.begin() + L, q.end());
+        // ScaleAndRound Q -> Q_l (:599-623) and ExpandCRTBasisQlHat (:629-639): functions of Q alone, kept for every technique
+        std::vector<uint64_t> &dropTab = T[{HPS_T_QlQHatInvModqDivqModq, l}], &dropFrac = T[{HPS_T_QlQHatInvModqDivqFrac, l}];
+        sr_tabs(Qrest, Ql, 1, dropTab, dropFrac);
+        std::vector<uint64_t> hatq(L);
+        for (uint32_t i = 0; i < L; ++i)
+            hatq[i] = host::prod_mod(Qrest, -1, q[i]);
+        T[{HPS_T_QlHatModq, l}] = hatq;
+        if (hps && l != numQ - 1)
+            continue;
+        fhe_hps::Level& v = h->lv[hps ? 0 : l];
+        const uint32_t lev = hps ? 0 : l;  // the reference keeps HPS's single table set at index 0
+        v.L = L, v.Lr = hps ? numR : L, v.QlHatModq = hatq;
+        const std::vector<uint64_t> Rl = head_of(r, v.Lr);
+        std::vector<uint32_t> qlIdx(h->qIdx.begin(), h->qIdx.begin() + L), rlIdx(h->rIdx.begin(), h->rIdx.begin() + v.Lr);
+        v.idx = qlIdx;
+        v.idx.insert(v.idx.end(), rlIdx.begin(), rlIdx.end());
+        const CrtTabs qr = crt_tabs(Ql, Rl), rq = crt_tabs(Rl, Ql);  // :143-203, :334-427
+        T[{HPS_T_QlHatInvModq, lev}] = qr.hatInv, T[{HPS_T_QlHatModr, lev}] = qr.hatMod, T[{HPS_T_alphaQlModr, lev}] = qr.alpha;
+        T[{HPS_T_RlHatInvModr, lev}] = rq.hatInv, T[{HPS_T_RlHatModq, lev}] = rq.hatMod, T[{HPS_T_alphaRlModq, lev}] = rq.alpha;
+        if ((s = hps_conv(h, qlIdx, rlIdx, qr.hatInv.data(), qr.hatMod.data(), qr.alpha.data(), qr.inv.data(), &v.qToR)) ||
+            (s = hps_conv(h, rlIdx, qlIdx, rq.hatInv.data(), rq.hatMod.data(), rq.alpha.data(), rq.inv.data(), &v.rToQ)))
+            break;
+        const bool regs = L <= (uint32_t)kMaxBfvLimbs && v.Lr <= (uint32_t)kMaxBfvLimbs;
+        if (regs && (s = hps_switch_tables(h, Rl, Ql, rq, &v.swRQ)))
+            break;
+        if (hps) {
+            const std::vector<uint64_t>&tab = T[{HPS_T_tRSHatInvModsDivsModr, 0}], &frac = T[{HPS_T_tRSHatInvModsDivsFrac, 0}];
+            if ((s = hps_sr(h, numQ, rlIdx, tab, frac, &v.tail)))
+                break;
+            v.fuseTail = regs;
+            if (regs && (s = hps_scale_tables(h, q, Rl, tab, frac, &v.scTail)))
+                break;
+            continue;
+        }
+        // Q_lR_l -> Q_l with t*Q_l/(Q_lR_l) (:565-593)
+        std::vector<uint64_t> &tab = T[{HPS_T_tQlSlHatInvModsDivsModq, l}], &frac = T[{HPS_T_tQlSlHatInvModsDivsFrac, l}];
+        sr_tabs(Rl, Ql, t, tab, frac);
+        if ((s = hps_sr(h, L, qlIdx, tab, frac, &v.tail)))
+            break;
+        // FastExpandCRTBasisPloverQ (:490-522): [-R_l (Q/q_i)^-1]_{q_i} from all of Q, [-R_l (Q_l/q_i)^-1]_{q_i} from Q_l
+        std::vector<uint64_t> negQ(numQ), negQl(L);
+        for (uint32_t i = 0; i < numQ; ++i) {
+            const uint64_t Rm = host::prod_mod(Rl, -1, q[i]);
+            negQ[i]           = q[i] - host::mulmod(Rm, host::invmod(host::prod_mod(q, (int)i, q[i]), q[i]), q[i]);
+            if (i < L)
+                negQl[i] = q[i] - host::mulmod(Rm, qr.hatInv[i], q[i]);
+        }
+        T[{HPS_T_negRlQHatInvModq, l}] = negQ, T[{HPS_T_negRlQlHatInvModq, l}] = negQl;
+        // (at the top level Q_l = Q and the two tables coincide; below it the composite converts from all of Q)
+        v.nApprox = numQ;
+        std::vector<uint64_t> invMod((size_t)numQ * L);
+        for (uint32_t i = 0; i < numQ; ++i)
+            for (uint32_t j = 0; j < L; ++j)
+                invMod[(size_t)i * L + j] = T[{HPS_T_qInvModr, 0}][(size_t)i * numR + j];
+        if ((s = hps_conv(h, h->qIdx, rlIdx, negQ.data(), invMod.data(), nullptr, nullptr, &v.pOverQ)))
+            break;
+        v.fuseExpand = regs && numQ <= (uint32_t)kMaxBfvLimbs;
+        if (v.fuseExpand) {
+            const size_t W = kMaxBfvLimbs;
+            std::vector<TwPair> hi(W, TwPair{0, 0});
+            std::vector<uint64_t> sq(W, 1), hm((size_t)L * W, 0), rr(W, 1), mu(2 * W, 0);
+            for (uint32_t i = 0; i < numQ; ++i) {
+                hi[i] = TwPair{negQ[i], host::shoup(negQ[i], q[i])};
+                sq[i] = q[i];
+                for (uint32_t j = 0; j < L; ++j)
+                    hm[(size_t)j * W + i] = invMod[(size_t)i * L + j];
+            }
+            for (uint32_t j = 0; j < L; ++j) {
+                rr[j] = r[j];
+                host::mu128(r[j], &mu[2 * j]);
+            }
+            TwPair* p1;
+            uint64_t *d1, *d2, *d3, *d4;
+            if ((s = dev_copy(h->owned, hi.data(), W, &p1)) || (s = dev_copy(h->owned, sq.data(), W, &d1)) ||
+                (s = dev_copy(h->owned, hm.data(), hm.size(), &d2)) || (s = dev_copy(h->owned, rr.data(), W, &d3)) ||
+                (s = dev_copy(h->owned, mu.data(), mu.size(), &d4)))
+                break;
+            v.exHatInv = p1, v.exSrcQ = d1, v.exHatMod = d2, v.exR = d3, v.exMuR = d4;
+        }
+        if (technique == 3 && L < numQ) {
+            std::vector<uint32_t> restIdx(h->qIdx.begin() + L, h->qIdx.end());
+            if ((s = hps_sr(h, numQ - L, qlIdx, dropTab, dropFrac, &v.drop)))
+                break;
+            v.fuseHead = regs && numQ - L <= (uint32_t)kMaxBfvLimbs;
+            if (v.fuseHead && ((s = hps_scale_tables(h, Qrest, Ql, dropTab, dropFrac, &v.scDrop)) || (s = hps_switch_tables(h, Ql, Rl, qr, &v.swQR))))
+                break;
+        }
+    }
+    if (s) {
+        fhe_hps_destroy(h);
+        return s;
+    }
+    *out = h;
+    return FHE_OK;
+}
+
+// Read-only view of a derived table (tests compare every one with the reference's, bit for bit).  Layouts, row-major, L = level + 1
+// limbs of Q_l and Lr limbs of R_l (HPS keeps one set at level 0 with L = numQ, Lr = numR); doubles are returned as their bit patterns:
+//    0 QlHatInvModq [L]           1 QlHatModr [L][Lr]           2 alphaQlModr [L+1][Lr]        3 qInv [numQ] (double)
+//    4 RlHatInvModr [Lr]          5 RlHatModq [Lr][L]           6 alphaRlModq [Lr+1][L]        7 rInv [numR] (double)
+//    8 tRSHatInvModsDivsModr [numR][numQ+1]                     9 tRSHatInvModsDivsFrac [numQ] (double)
+//   10 tQlSlHatInvModsDivsModq [L][L+1]                        11 tQlSlHatInvModsDivsFrac [L] (double)
+//   12 mNegRlQHatInvModq [numQ]  13 mNegRlQlHatInvModq [L]      14 qInvModr [numQ][numR]
+//   15 QlQHatInvModqDivqModq [L][numQ-L+1]                     16 QlQHatInvModqDivqFrac [numQ-L] (double)     17 QlHatModq [L]
+// Returns the number of 64-bit words of the table (0: no such table for this plan); copies min(that, cap) words into out.
+extern "C" size_t fhe_hps_table(const fhe_hps* h, int tableId, uint32_t level, uint64_t* out, size_t cap) {
+    if (!h)
+        return 0;
+    auto it = h->tables.find({tableId, level});
+    if (it == h->tables.end())
+        return 0;
+    if (out && cap)
+        std::memcpy(out, it->second.data(), std::min(cap, it->second.size()) * 8);
+    return it->second.size();
+}
+
+static const fhe_hps::Level* hps_level(const fhe_hps* h, uint32_t sizeQl) {
+    if (!h || sizeQl < 1 || sizeQl > h->numQ)
+        return nullptr;
+    if (h->technique != 3 && sizeQl != h->numQ)
+        return nullptr;
+    return &h->lv[h->technique == 1 ? 0 : sizeQl - 1];
+}
+extern "C" size_t fhe_bfv_eval_mult_hps_workspace_bytes(const fhe_hps* h, uint32_t sizeQl, uint32_t batch) {
+    const fhe_hps::Level* v = hps_level(h, sizeQl);
+    if (!v)
+        return 0;
+    const size_t rows = 7 * (size_t)(v->L + v->Lr) + h->numQ + std::max(h->numQ, h->numR);
+    return ((rows * batch) << h->ctx->logN) * 8;
+}
+// LeveledSHEBFVRNS::EvalMult, the three HPS branches, without relinearisation (bfvrns-leveledshe.cpp:198-439).
+extern "C" fhe_status fhe_bfv_eval_mult_hps(fhe_hps* h, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
+                                            uint64_t* d0, uint64_t* d1, uint64_t* d2, uint32_t sizeQl, int outEval, uint32_t batch,
+                                            void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(h && a0 && a1 && b0 && b1 && d0 && d1 && d2 && ws && batch >= 1, "fhe_bfv_eval_mult_hps: bad argument");
+    const fhe_hps::Level* vp = hps_level(h, sizeQl);
+    ARG_CHECK(vp, "fhe_bfv_eval_mult_hps: sizeQl must be numQ (1 ... numQ for HPSPOVERQLEVELED)");
+    ARG_CHECK(wsBytes >= fhe_bfv_eval_mult_hps_workspace_bytes(h, sizeQl, batch), "fhe_bfv_eval_mult_hps: workspace too small");
+    const fhe_hps::Level& v = *vp;
+    fhe_ctx* c = h->ctx;
+    RT_CHECK(rt::set_device(c->device));
+    const uint32_t nQ = h->numQ, L = v.L, tot = v.L + v.Lr, logN = c->logN;
+    const bool hps = h->technique == 1, dropped = L < nQ;
+    const size_t ext = ((size_t)batch * tot) << logN, qB = (((size_t)batch * nQ) << logN) * 8;
+    uint64_t* w      = (uint64_t*)ws;
+    uint64_t* e[4]   = {w, w + ext, w + 2 * ext, w + 3 * ext};
+    uint64_t* p[3]   = {w + 4 * ext, w + 5 * ext, w + 6 * ext};
+    uint64_t* coef   = w + 7 * ext;                        // [batch][numQ][N]: coefficient form of one input element
+    uint64_t* tmp    = coef + (((size_t)batch * nQ) << logN);  // [batch][max(numQ, numR)][N]
+    const uint32_t grid = coeff_grid(c, batch);
+    const uint64_t* in[4] = {a0, a1, b0, b1};
+    for (int k = 0; k < 4; ++k) {
+        fhe_status s = FHE_OK;
+        if (hps || (k < 2 && !dropped)) {  // ExpandCRTBasis Q -> QR, the EVALUATION copy of the Q limbs kept (:223-246)
+            if ((s = expand_run(v.qToR, in[k], 1, e[k], 1, 0, batch, coef, qB, st, true)))
+                return s;
+            continue;
+        }
+        if ((s = ntt_run(c, true, in[k], coef, h->qIdx.data(), nQ, batch, st)))  // SetFormat(COEFFICIENT) (:257, :275, :297)
+            return s;
+        if (k < 2) {  // ScaleAndRound Q -> Q_l, ExpandCRTBasis Q_l -> Q_lR_l (:276-286)
+            if (v.fuseHead) {
+                ScaleSwitchArgs g;
+                g.in = TowerView{coef, nQ, L}, g.own = TowerView{coef, nQ, 0};
+                g.outMid = TowerView{e[k], tot, 0}, g.outDst = TowerView{e[k], tot, L};
+                g.sr = v.scDrop, g.sw = v.swQR, g.logN = logN, g.batch = batch;
+                FHE_LAUNCH((scale_round_switch_kernel<true>), grid, st, g);
+                LAUNCH_CHECK();
+                s = fhe_ntt_fwd(c, e[k], v.idx.data(), tot, batch, st);
+            }
+            else if (!(s = fhe_scale_and_round(v.drop, coef, 1, tmp, batch, st)))
+                s = expand_run(v.qToR, tmp, 0, e[k], 1, 0, batch, nullptr, 0, st, true);
+        }
+        else {  // FastExpandCRTBasisPloverQ, SetFormat(EVALUATION) (:256-261, :296-301)
+            if (v.fuseExpand) {
+                POverQExpandArgs g;
+                g.in = TowerView{coef, nQ, 0}, g.out = TowerView{e[k], tot, 0};
+                g.hatInv = v.exHatInv, g.srcQ = v.exSrcQ, g.hatMod = v.exHatMod, g.r = v.exR, g.muR = v.exMuR;
+                g.sw = v.swRQ, g.nSrc = v.nApprox, g.logN = logN, g.batch = batch;
+                FHE_LAUNCH(p_over_q_expand_kernel, grid, st, g);
+                LAUNCH_CHECK();
+            }
+            else if ((s = conv_run<false>(v.pOverQ, coef, nQ, 0, e[k], tot, L, batch, st)) ||
+                     (s = conv_run<true>(v.rToQ, e[k], tot, L, e[k], tot, 0, batch, st)))
+                return s;
+            s = fhe_ntt_fwd(c, e[k], v.idx.data(), tot, batch, st);
+        }
+        if (s)
+            return s;
+    }
+    if (fhe_status s = fhe_tensor(c, e[0], e[1], e[2], e[3], p[0], p[1], p[2], v.idx.data(), tot, batch, st))  // :354-365
+        return s;
+    uint64_t* out[3] = {d0, d1, d2};
+    for (int k = 0; k < 3; ++k) {
+        fhe_status s;
+        if ((s = fhe_ntt_inv(c, p[k], v.idx.data(), tot, batch, st)))
+            return s;
+        if (hps) {  // ScaleAndRound QR -> R, SwitchCRTBasis R -> Q (:368-383)
+            if (v.fuseTail) {
+                ScaleSwitchArgs g;
+                g.in = TowerView{p[k], tot, 0}, g.own = TowerView{p[k], tot, L};
+                g.outMid = g.own, g.outDst = TowerView{out[k], nQ, 0};
+                g.sr = v.scTail, g.sw = v.swRQ, g.logN = logN, g.batch = batch;
+                FHE_LAUNCH((scale_round_switch_kernel<false>), grid, st, g);
+                LAUNCH_CHECK();
+            }
+            else if ((s = fhe_scale_and_round(v.tail, p[k], 0, tmp, batch, st)) ||
+                     (s = conv_run<true>(v.rToQ, tmp, v.Lr, 0, out[k], nQ, 0, batch, st)))
+                return s;
+        }
+        else if (!dropped) {  // ScaleAndRound QR -> Q (:385-395, :397-404)
+            if ((s = fhe_scale_and_round(v.tail, p[k], 1, out[k], batch, st)))
+                return s;
+        }
+        else {  // ScaleAndRound Q_lR_l -> Q_l, ExpandCRTBasisQlHat (:402-410)
+            if ((s = fhe_scale_and_round(v.tail, p[k], 1, tmp, batch, st)) ||
+                (s = fhe_expand_crt_basis_ql_hat(c, tmp, L, v.QlHatModq.data(), h->qIdx.data(), nQ, batch, out[k], st)))
+                return s;
+        }
+        if (outEval)
+            if ((s = fhe_ntt_fwd(c, out[k], h->qIdx.data(), nQ, batch, st)))
+                return s;
+    }
+    return FHE_OK;
+}
+
 // whole-tower checksums (checksum_kernel): out[row] = {sum_i w_i, sum_i (2i + 1) w_i} mod 2^64 of every limb-row of x[rows][N]; out is DEVICE memory
 extern "C" fhe_status fhe_checksum(fhe_ctx* c, const uint64_t* x, uint32_t rows, uint64_t* out, void* st) {
     ARG_CHECK(c && x && out && rows >= 1, "fhe_checksum: bad argument");

@@ -172,6 +172,12 @@ class Lib:
         S("fhe_bfv_eval_mult_behz_workspace_bytes", C.c_size_t, [vp, u32])
         S("fhe_bfv_eval_mult_behz", C.c_int, [vp] * 8 + [C.c_int, u32, vp, C.c_size_t, vp])
         S("fhe_bfv_eval_mult_relin_workspace_bytes", C.c_size_t, [vp, vp, u32])
+        S("fhe_param_hps_r", u32, [u32, u32, u64p, C.c_int, u64p, u64p])
+        S("fhe_hps_create", C.c_int, [vp, u32p, u32, u32p, u32, u64, C.c_int, C.POINTER(vp)])
+        S("fhe_hps_destroy", None, [vp])
+        S("fhe_hps_table", C.c_size_t, [vp, C.c_int, u32, u64p, C.c_size_t])
+        S("fhe_bfv_eval_mult_hps_workspace_bytes", C.c_size_t, [vp, u32, u32])
+        S("fhe_bfv_eval_mult_hps", C.c_int, [vp] * 8 + [u32, C.c_int, u32, vp, C.c_size_t, vp])
         S("fhe_bfv_eval_mult_relin_behz", C.c_int, [vp] * 9 + [u32, vp, C.c_size_t, vp])
         S("fhe_param_first_prime", u64, [u32, u64])
         S("fhe_param_last_prime", u64, [u32, u64])
@@ -239,6 +245,16 @@ class Lib:
         if n == 0:
             raise FheError("fhe_param_behz_bsk failed")
         return bsk, psi
+
+    def hps_r(self, logN, q, technique):
+        """the auxiliary basis R of BFV's HPS family (bfvrns-cryptoparameters.cpp:75, 126-139): (moduli, roots)"""
+        q = np.ascontiguousarray(q, dtype=np.uint64)
+        r = np.zeros(len(q) + 1, np.uint64)
+        psi = np.zeros(len(q) + 1, np.uint64)
+        n = self.L.fhe_param_hps_r(logN, len(q), q.ctypes.data_as(u64p), technique, r.ctypes.data_as(u64p), psi.ctypes.data_as(u64p))
+        if n == 0:
+            raise FheError("fhe_param_hps_r failed")
+        return r[:n].copy(), psi[:n].copy()
 
     def find_automorphism_index(self, index, m):
         """FindAutomorphismIndex2nComplex (nbtheory2.cpp:243-262)"""
@@ -966,6 +982,64 @@ class Behz:
         try:
             self.ctx.lib.check(L.fhe_bfv_eval_mult_behz(self.h, a0.ptr, a1.ptr, b0.ptr, b1.ptr, d[0].ptr, d[1].ptr,
                                                         d[2].ptr, 1 if out_eval else 0, B, ws, wsb, stream))
+            self.ctx.sync(stream)
+        finally:
+            self.ctx.free(ws)
+        return d
+
+
+HPS, HPSPOVERQ, HPSPOVERQLEVELED = 1, 2, 3  # MultiplicationTechnique (constants-defs.h:97)
+
+
+class Hps:
+    """BFV EvalMult of the HPS family over a context that holds the Q limbs and the R limbs (Lib.hps_r)."""
+
+    # fhe_hps_table ids
+    TABLES = ("QlHatInvModq", "QlHatModr", "alphaQlModr", "qInv", "RlHatInvModr", "RlHatModq", "alphaRlModq", "rInv",
+              "tRSHatInvModsDivsModr", "tRSHatInvModsDivsFrac", "tQlSlHatInvModsDivsModq", "tQlSlHatInvModsDivsFrac",
+              "negRlQHatInvModq", "negRlQlHatInvModq", "qInvModr", "QlQHatInvModqDivqModq", "QlQHatInvModqDivqFrac", "QlHatModq")
+
+    def __init__(self, ctx, q_idx, r_idx, t, technique):
+        self.ctx = ctx
+        self.q_idx = np.ascontiguousarray(np.asarray(q_idx, dtype=np.uint32))
+        self.r_idx = np.ascontiguousarray(np.asarray(r_idx, dtype=np.uint32))
+        self.numQ, self.numR, self.technique = len(self.q_idx), len(self.r_idx), technique
+        h = vp()
+        ctx.lib.check(ctx.lib.L.fhe_hps_create(ctx.h, self.q_idx.ctypes.data_as(u32p), self.numQ, self.r_idx.ctypes.data_as(u32p),
+                                               self.numR, t, technique, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.L.fhe_hps_destroy(self.h)
+            self.h = None
+
+    def table(self, name, level=0):
+        """a derived table as a flat uint64 array (doubles as their bit patterns: .view(np.float64)); None if absent"""
+        tid = self.TABLES.index(name) if isinstance(name, str) else int(name)
+        n = self.ctx.lib.L.fhe_hps_table(self.h, tid, level, None, 0)
+        if n == 0:
+            return None
+        out = np.zeros(n, np.uint64)
+        self.ctx.lib.L.fhe_hps_table(self.h, tid, level, out.ctypes.data_as(u64p), n)
+        return out
+
+    def workspace_bytes(self, size_ql, batch):
+        return self.ctx.lib.L.fhe_bfv_eval_mult_hps_workspace_bytes(self.h, size_ql, batch)
+
+    def EvalMultNoRelin(self, a0, a1, b0, b1, size_ql=None, out_eval=False, stream=None):
+        """LeveledSHEBFVRNS::EvalMult (HPS / HPSPOVERQ / HPSPOVERQLEVELED) on device towers [batch][numQ][N] (EVALUATION);
+        size_ql = numQ - levelsDropped (HPSPOVERQLEVELED only; default numQ); returns (d0, d1, d2)"""
+        B = a0.batch
+        size_ql = self.numQ if size_ql is None else size_ql
+        fmt = EVALUATION if out_eval else COEFFICIENT
+        d = [self.ctx.empty(B, self.numQ, self.q_idx, fmt) for _ in range(3)]
+        L = self.ctx.lib.L
+        wsb = max(L.fhe_bfv_eval_mult_hps_workspace_bytes(self.h, size_ql, B), 8)
+        ws = self.ctx.malloc(wsb)
+        try:
+            self.ctx.lib.check(L.fhe_bfv_eval_mult_hps(self.h, a0.ptr, a1.ptr, b0.ptr, b1.ptr, d[0].ptr, d[1].ptr, d[2].ptr,
+                                                       size_ql, 1 if out_eval else 0, B, ws, wsb, stream))
             self.ctx.sync(stream)
         finally:
             self.ctx.free(ws)

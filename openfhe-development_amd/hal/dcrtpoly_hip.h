@@ -502,5 +502,60 @@ private:
     fhe_behz* m_plan = nullptr;
 };
 
+// BFV multiplication in the HPS family — technique 1 = HPS, 2 = HPSPOVERQ, 3 = HPSPOVERQLEVELED (the reference's default) —
+// LeveledSHEBFVRNS::EvalMult, bfvrns-leveledshe.cpp:198-302, 354-412, with the tables of CryptoParametersBFVRNS's HPS block
+// (bfvrns-cryptoparameters.cpp:143-665) derived by the plan.  The context holds Q (qLimbs) and the auxiliary basis R (rLimbs).
+class HpsPlan {
+public:
+    // the R moduli / roots the reference picks for (N, Q, technique) (bfvrns-cryptoparameters.cpp:75, 126-139)
+    static void SelectR(uint32_t cyclotomicOrder, const std::vector<uint64_t>& q, int technique, std::vector<uint64_t>& r,
+                        std::vector<uint64_t>& psi) {
+        uint32_t logN = 0;
+        while ((2u << logN) < cyclotomicOrder)
+            ++logN;
+        r.assign(q.size() + 1, 0), psi.assign(q.size() + 1, 0);
+        const uint32_t n = fhe_param_hps_r(logN, (uint32_t)q.size(), q.data(), technique, r.data(), psi.data());
+        if (n == 0)
+            throw Error("HPS: no auxiliary basis for these parameters");
+        r.resize(n), psi.resize(n);
+    }
+    HpsPlan(std::shared_ptr<Params> params, const std::vector<uint32_t>& qLimbs, const std::vector<uint32_t>& rLimbs, uint64_t t,
+            int technique)
+        : m_params(std::move(params)), m_numQ((uint32_t)qLimbs.size()) {
+        check(fhe_hps_create(m_params->ctx(), qLimbs.data(), m_numQ, rLimbs.data(), (uint32_t)rLimbs.size(), t, technique, &m_plan));
+    }
+    ~HpsPlan() { fhe_hps_destroy(m_plan); }
+    HpsPlan(const HpsPlan&)            = delete;
+    HpsPlan& operator=(const HpsPlan&) = delete;
+    // EvalMultNoRelin: (a0, a1) x (b0, b1) -> (d0, d1, d2), inputs EVALUATION over Q; outputs COEFFICIENT like the reference's, or
+    // EVALUATION (outEval) for the relinearisation that follows.  sizeQl = numQ - levelsDropped (HPSPOVERQLEVELED; 0 = numQ).
+    std::vector<DCRTPolyHip> EvalMultNoRelin(const DCRTPolyHip& a0, const DCRTPolyHip& a1, const DCRTPolyHip& b0, const DCRTPolyHip& b1,
+                                             uint32_t sizeQl = 0, bool outEval = false) {
+        const uint32_t batch = a0.GetBatch();
+        if (sizeQl == 0)
+            sizeQl = m_numQ;
+        std::vector<DCRTPolyHip> d;
+        for (int i = 0; i < 3; ++i)
+            d.emplace_back(m_params, m_numQ, outEval ? EVALUATION : COEFFICIENT, batch);
+        const size_t need = fhe_bfv_eval_mult_hps_workspace_bytes(m_plan, sizeQl, batch);
+        if (need == 0)
+            throw Error("HPS: sizeQl does not fit the technique");
+        void* ws = nullptr;
+        check(fhe_malloc(m_params->ctx(), need, &ws));
+        const fhe_status st = fhe_bfv_eval_mult_hps(m_plan, a0.data(), a1.data(), b0.data(), b1.data(), d[0].data(), d[1].data(),
+                                                    d[2].data(), sizeQl, outEval ? 1 : 0, batch, ws, need, nullptr);
+        fhe_stream_sync(m_params->ctx(), nullptr);
+        fhe_free(m_params->ctx(), ws);
+        check(st);
+        return d;
+    }
+    fhe_hps* plan() const { return m_plan; }
+
+private:
+    std::shared_ptr<Params> m_params;
+    uint32_t m_numQ;
+    fhe_hps* m_plan = nullptr;
+};
+
 }  // namespace fhehip
 #endif
