@@ -9,6 +9,7 @@ import pytest
 import libs
 from openfhe_amd import fhe_hip as fh
 from test_parity import params
+from test_parity_edges import limit_pair, product
 
 
 def mu128(o, mods):
@@ -163,14 +164,125 @@ def test_behz_trio(backend, oracle, logN, numQ, t, B):
     o.orc_behz_destroy(hb)
 
 
-@pytest.mark.parametrize("logN,numQ,t,B", [(4, 2, 65537, 2), (10, 3, 65537, 3), (12, 4, 786433, 1), (6, 20, 65537, 2)])
-def test_bfv_eval_mult_behz(backend, oracle, logN, numQ, t, B):
-    """fhe_bfv_eval_mult_behz vs the oracle's composite (itself pinned to the reference's scheme-layer EvalMultNoRelin)"""
+# ---- BEHZ below 60 bits, limit operands, the exact branch thresholds ---------------------------------------------------------------
+# (bits, numQ, logN): 3 and 15 limbs take the register-resident kernels, 16 and 20 the wide ones; every limb count at both rings
+BEHZ_EDGE_CASES = [(30, 3, 10), (30, 15, 5), (30, 16, 10), (30, 20, 5), (36, 3, 5), (36, 15, 10), (36, 16, 5), (36, 20, 10),
+                   (45, 3, 10), (45, 15, 5), (45, 16, 10), (45, 20, 5)]
+MTILDE = 1 << 16
+
+
+def montgomery_remainder(col, q):
+    """Python integers, one coefficient of FastBaseConvqToBskMontgomery (dcrtpoly-impl.h:1731-1774): (rm, [y_i]) of the residues col"""
+    Q = product(q)
+    y = [x * (MTILDE * pow((Q // s) % s, -1, s) % s) % s for x, s in zip(col, q)]
+    rm = (sum(yi * ((Q // s) % MTILDE) for yi, s in zip(y, q)) % MTILDE) * (-pow(Q, -1, MTILDE) % MTILDE) % MTILDE
+    return rm, y
+
+
+def residue_for_remainder(col, q, limb, target, rng):
+    """the residue of limb `limb` that, with the other residues of col, makes rm = target: y_limb is fixed modulo 2^16 ([Q/q_i] and
+    [-Q^-1] are odd), its upper bits are drawn"""
+    Q, s = product(q), q[limb]
+    rest = list(col)
+    rest[limb] = 0
+    _, y = montgomery_remainder(rest, q)
+    need = target * pow(-pow(Q, -1, MTILDE) % MTILDE, -1, MTILDE) - sum(yi * ((Q // m) % MTILDE) for yi, m in zip(y, q))
+    low = need * pow((Q // s) % MTILDE, -1, MTILDE) % MTILDE
+    yl = low + MTILDE * int(rng.integers(0, (s - 1 - low) // MTILDE + 1))
+    assert yl < s
+    return yl * pow(MTILDE * pow((Q // s) % s, -1, s) % s, -1, s) % s
+
+
+def sk_correction(col, bsk):
+    """Python integers, one coefficient of FastBaseConvSK (:1845-1929): (alpha, [y_i], the sum alpha is taken from) of the residues
+    col over Bsk = B u {msk}"""
+    B, msk = bsk[:-1], bsk[-1]
+    Bp = product(B)
+    y = [x * pow((Bp // b) % b, -1, b) % b for x, b in zip(col, B)]
+    S = sum((yi % msk) * ((Bp // b) % msk) for yi, b in zip(y, B)) % msk
+    return (S - col[-1]) * pow(Bp, -1, msk) % msk, y, S
+
+
+@pytest.mark.parametrize("bits,numQ,logN", BEHZ_EDGE_CASES)
+def test_behz_trio_small_moduli_limit_operands_and_thresholds(backend, oracle, bits, numQ, logN):
+    """the three BEHZ members below 60 bits on towers all q-1 (tower 0) and `mix` (tower 1), with the branch decisions of
+    behz_q_to_bsk*_kernel (rm >= 2^15) and behz_conv_sk*_kernel (alpha > mskHalf) planted ON their thresholds: rm = 0, 2^15 - 1,
+    2^15, 2^16 - 1 by one limb's residue, alpha = 0, mskHalf, mskHalf + 1, msk - 1 by the free row x_sk; that each occurs, and what the
+    member returns there, is computed with Python integers"""
     o = oracle
-    rng = np.random.default_rng(29)
-    N, q, psiQ, bsk, psiB, hb, ctx, plan = behz_setup(backend, o, logN, numQ, t)
+    rng = np.random.default_rng(24)
+    t, B = (65537, 786433)[numQ % 2], 2
+    N, q, psiQ, bsk, psiB, hb, ctx, plan = behz_setup(backend, o, logN, numQ, t, bits)
+    assert all(int(v).bit_length() == bits for v in q)
+    nb = len(bsk)
+    qi, bi = [int(v) for v in q], [int(v) for v in bsk]
+    Q, Bp, msk = product(qi), product(bi[:-1]), bi[-1]
+    wide = "_wide_kernel" if numQ > 15 else "_kernel"
+    names = ["behz_q_to_bsk" + wide, "behz_floorq" + wide, "behz_conv_sk" + wide]
+    before = [backend.launch_count(k) for k in names]
+    octxQ = o.orc_ctx_create(N, numQ, q, psiQ)
+    octxB = o.orc_ctx_create(N, nb, bsk, psiB)
+    # FastBaseConvqToBskMontgomery: coefficient k of tower 1 gets the k-th remainder, planted through limb k mod numQ
+    x = limit_pair(rng, q, N)
+    remainders = (0, MTILDE // 2 - 1, MTILDE // 2, MTILDE - 1)
+    for k, target in enumerate(remainders):
+        col = [int(v) for v in x[1, :, k]]
+        x[1, k % numQ, k] = residue_for_remainder(col, qi, k % numQ, target, rng)
+    want_c = np.zeros((B, nb, N), np.uint64)
+    for b in range(B):
+        o.orc_behz_q_to_bsk_montgomery(hb, x[b], want_c[b])
+    for k, target in enumerate(remainders):
+        rm, y = montgomery_remainder([int(v) for v in x[1, :, k]], qi)
+        assert rm == target, "the planted remainder occurs"
+        lift = (rm if rm < MTILDE // 2 else rm - MTILDE) * Q + sum(yi * (Q // s) for yi, s in zip(y, qi))
+        assert [int(v) for v in want_c[1, :, k]] == [lift * pow(MTILDE, -1, bj) % bj for bj in bi], f"oracle at rm = {target}"
+    xe = x.copy()
+    o.orc_ntt_fwd_tower(octxQ, xe, None, numQ, B, 1)
+    want_b = want_c.copy()
+    o.orc_ntt_fwd_tower(octxB, want_b, None, nb, B, 1)
+    for eval_fmt in (False, True):
+        got = plan.FastBaseConvqToBskMontgomery(xe if eval_fmt else x, eval_fmt).to_host()
+        assert np.array_equal(got[:, :numQ], xe) and np.array_equal(got[:, numQ:], want_b), f"q->Bsk eval={eval_fmt}"
+    allm = np.concatenate([q, bsk])
+    y = limit_pair(rng, allm, N)
+    wy = y.copy()
+    for b in range(B):
+        o.orc_behz_fast_rns_floorq(hb, wy[b])
+    ty = ctx.tower(y, limb_idx=np.arange(numQ + nb), fmt=fh.COEFFICIENT)
+    assert np.array_equal(plan.FastRNSFloorq(ty).to_host(), wy), "FastRNSFloorq"
+    # FastBaseConvSK: alpha is affine in x_sk
+    z = limit_pair(rng, allm, N)
+    alphas = (0, msk // 2, msk // 2 + 1, msk - 1)
+    for k, target in enumerate(alphas):
+        _, _, S = sk_correction([int(v) for v in z[1, numQ:, k]], bi)
+        z[1, numQ + nb - 1, k] = (S - target * Bp) % msk
+    wz = np.zeros((B, numQ, N), np.uint64)
+    for b in range(B):
+        o.orc_behz_fast_base_conv_sk(hb, z[b], wz[b])
+    for k, target in enumerate(alphas):
+        alpha, yb, _ = sk_correction([int(v) for v in z[1, numQ:, k]], bi)
+        assert alpha == target, "the planted alpha occurs"
+        v = sum(yi * (Bp // b) for yi, b in zip(yb, bi))
+        # above mskHalf the reference subtracts msk with ModSubFast modulo q_j: alpha + q_j - msk in 64-bit words, which wraps when
+        # msk exceeds alpha + q_j
+        a = [alpha if alpha <= msk // 2 else (alpha + s - msk) % (1 << 64) for s in qi]
+        assert [int(w) for w in wz[1, :, k]] == [(v - aj * (Bp % s)) % s for aj, s in zip(a, qi)], f"oracle at alpha = {target}"
+    tz = ctx.tower(z, limb_idx=np.arange(numQ + nb), fmt=fh.COEFFICIENT)
+    assert np.array_equal(plan.FastBaseConvSK(tz).to_host(), wz), "FastBaseConvSK"
+    assert all(backend.launch_count(k) > n for k, n in zip(names, before)), names
+    plan.close()
+    ctx.close()
+    o.orc_ctx_destroy(octxQ)
+    o.orc_ctx_destroy(octxB)
+    o.orc_behz_destroy(hb)
+
+
+def check_eval_mult_behz(backend, o, logN, numQ, t, B, bits, operands):
+    """fhe_bfv_eval_mult_behz on the four towers operands(q, N) against the oracle's composite, both output formats"""
+    N, q, psiQ, bsk, psiB, hb, ctx, plan = behz_setup(backend, o, logN, numQ, t, bits)
+    assert all(int(v).bit_length() == bits for v in q)
     call = o.orc_ctx_create(N, numQ + len(bsk), np.concatenate([q, bsk]), np.concatenate([psiQ, psiB]))
-    X = [libs.rand_tower(rng, q, N, B) for _ in range(4)]
+    X = operands(q, N)
     want = np.zeros((3, B, numQ, N), np.uint64)
     for b in range(B):
         o.orc_bfv_eval_mult_behz(hb, call, X[0][b], X[1][b], X[2][b], X[3][b], want[0, b], want[1, b], want[2, b])
@@ -189,6 +301,25 @@ def test_bfv_eval_mult_behz(backend, oracle, logN, numQ, t, B):
     o.orc_ctx_destroy(call)
     o.orc_ctx_destroy(octxQ)
     o.orc_behz_destroy(hb)
+
+
+@pytest.mark.parametrize("logN,numQ,t,B", [(4, 2, 65537, 2), (10, 3, 65537, 3), (12, 4, 786433, 1), (6, 20, 65537, 2)])
+def test_bfv_eval_mult_behz(backend, oracle, logN, numQ, t, B):
+    """fhe_bfv_eval_mult_behz vs the oracle's composite (itself pinned to the reference's scheme-layer EvalMultNoRelin)"""
+    rng = np.random.default_rng(29)
+    check_eval_mult_behz(backend, oracle, logN, numQ, t, B, 60, lambda q, N: [libs.rand_tower(rng, q, N, B) for _ in range(4)])
+
+
+@pytest.mark.parametrize("bits,numQ,logN", [(30, 3, 10), (36, 15, 5), (45, 16, 5), (30, 20, 10), (36, 16, 10), (45, 3, 5)])
+def test_bfv_eval_mult_behz_small_moduli_limit_operands(backend, oracle, bits, numQ, logN):
+    """the composite below 60 bits, every element with tower 0 all q-1 and tower 1 `mix` (limit_pair): the column sums of the
+    conversions carry the largest residues in every chunk of 8; 3 and 15 limbs: the register-resident kernels, 16 and 20: the wide ones"""
+    rng = np.random.default_rng(30)
+    names = [k + w for k in ("behz_q_to_bsk", "behz_floorq", "behz_conv_sk") for w in ("_kernel", "_wide_kernel")]
+    before = {k: backend.launch_count(k) for k in names}
+    check_eval_mult_behz(backend, oracle, logN, numQ, (65537, 786433)[numQ % 2], 2, bits, lambda q, N: [limit_pair(rng, q, N) for _ in range(4)])
+    for k in names:
+        assert (backend.launch_count(k) > before[k]) == (k.endswith("_wide_kernel") == (numQ > 15)), k
 
 
 @pytest.mark.parametrize("ring", [64, 1024])
