@@ -720,10 +720,38 @@ static bool row8_x1_regions(uint32_t P) {
     }();
     return forced >= 0 ? forced == 1 : (P == 2 ? kRow8X1RegionsP2 : kRow8X1RegionsP4);
 }
+// Hand-over between the two passes of an INVERSE 4 + 12-stage transform (ntt_row8.h / ntt_static.h, HAND): the column pass does the
+// twiddle products of the row pass's last stage.  The pair runs for exactly the part of a transform that the batched 12-stage row kernel takes:
+// ntt_run asks for it (handP = that kernel's P) only for a plain transform with canonical output, and both passes are then launched in the
+// same two parts, the P-aligned one with hand-over and the remainder on the kernels every other consumer of the intermediate tower uses.
+// FHE_NTT_HANDOVER = 0 / 1 forces it off / on (measurements, tests); read once per process; any other value is reported and means off.
+constexpr bool kHandoverDefault = true;
+constexpr bool kHandOver        = true;  // (the launch sites spell the template argument by this name: fhe_launch_stats lists them as <HAND>)
+static bool ntt_handover_enabled() {
+    static const bool on = [] {
+        const char* v = std::getenv("FHE_NTT_HANDOVER");
+        if (!v)
+            return kHandoverDefault;
+        if ((v[0] == '0' || v[0] == '1') && !v[1])
+            return v[0] == '1';
+        fprintf(stderr, "fhe_hip: FHE_NTT_HANDOVER=%s is neither 0 nor 1: hand-over is off\n", v);
+        return false;
+    }();
+    return on;
+}
+// THE decision, per pass: may this pass of a transform run its hand-over instance for groups of handP polynomials?  ntt_run asks it for both
+// passes before it launches either, launch_pass asks it again for the pass it launches: the two cannot disagree.
+static bool handover_pass_ok(const fhe_ctx* c, const PassPlan& pp, bool inverse, uint32_t batch, uint32_t handP) {
+    if (!inverse || !handP || handP < 2 || batch < handP || c->logN <= (uint32_t)kTileLog)
+        return false;
+    const int mode = static_mode(c, pp, inverse);
+    return pp.layoutA ? (pp.T == 4 && mode == 1) : (pp.T == 12 && mode == 0 && row8_batch_for(pp.T) == handP);
+}
 static fhe_status launch_pass(const fhe_ctx* c, const PassPlan& pp, bool inverse, const uint64_t* xin, uint64_t* xout,
                               const LimbSel& sel, uint32_t nLimbs, uint32_t batch, bool canonOut, void* stream,
                               uint32_t inStride = 0, uint32_t inFirst = 0, uint32_t outStride = 0, uint32_t outFirst = 0,
-                              const NttEpilogue* epi = nullptr, const uint32_t* proSrcLimb = nullptr, int64_t inDelta = 0) {
+                              const NttEpilogue* epi = nullptr, const uint32_t* proSrcLimb = nullptr, int64_t inDelta = 0,
+                              uint32_t handP = 0) {
     NttPassArgs a;
     uint32_t grid = fill_pass_args(c, pp, inverse, xin, xout, sel, nLimbs, batch, canonOut, inStride, inFirst, outStride,
                                    outFirst, a);
@@ -776,6 +804,25 @@ static fhe_status launch_pass(const fhe_ctx* c, const PassPlan& pp, bool inverse
         // 12-stage row passes, several polynomials per workgroup (ntt_row8.h, batched): the P-aligned part of the batch; what is left of
         // the batch follows below on the same stream, as the same pass over a view that starts at its first polynomial
         const uint32_t P = (!pp.layoutA && c->logN > (uint32_t)kTileLog && mode == (inverse ? 0 : 9)) ? row8_batch_for(pp.T) : 1u;
+        // a transform with hand-over: both passes must land on the hand-over instances, or the intermediate tower is misread
+        if (handP && !(handover_pass_ok(c, pp, inverse, batch, handP) && (pp.layoutA || P == handP)))
+            return fail(FHE_ERR_UNSUPPORTED, "ntt: no hand-over kernel for this pass shape");  // (ntt_run has asked the same question)
+        if (handP && pp.layoutA) {
+            // the column pass of the part of the batch that the batched row kernel takes; the remainder follows below on the plain kernel
+            NttPassArgs h = a;
+            h.batch = batch / handP * handP;
+            h.rows  = h.batch * nLimbs;
+            FHE_LAUNCH_BARRIER((ntt_static_kernel<true, true, 4, 1, false, false, kHandOver>), tiles_for(c, h.rows), stream, h);
+            if (h.batch == batch) {
+                LAUNCH_CHECK();
+                return FHE_OK;
+            }
+            a.xin += a.inDelta ? (int64_t)h.batch * a.inDelta : (int64_t)(((uint64_t)h.batch * (a.inStride ? a.inStride : nLimbs)) << c->logN);
+            a.x += ((uint64_t)h.batch * (a.outStride ? a.outStride : nLimbs)) << c->logN;
+            a.batch = batch - h.batch;
+            a.rows  = a.batch * nLimbs;
+            grid    = tiles_for(c, a.rows);
+        }
         if (P > 1 && batch >= P) {
             NttPassArgs g = a;
             g.batch      = batch / P;  // groups of P polynomials: the batch-fastest XCD order, in units of P
@@ -786,7 +833,10 @@ static fhe_status launch_pass(const fhe_ctx* c, const PassPlan& pp, bool inverse
             bool batched         = false;
 #define FHE_ROW8B_CASE(INV, MODE, PP, X1P) \
     if (!batched && inverse == INV && P == PP && x1p == X1P) { \
-        FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P>), ggrid, 512u, stream, g); \
+        if (INV && handP) /* (handP is never set for a forward pass: the instance named for INV = false is the plain one) */ \
+            FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P, (INV && kHandOver)>), ggrid, 512u, stream, g); \
+        else \
+            FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P>), ggrid, 512u, stream, g); \
         batched = true; \
     }
             FHE_ROW8B_CASE(false, 9, 2, false) FHE_ROW8B_CASE(true, 0, 2, false) FHE_ROW8B_CASE(false, 9, 2, true) FHE_ROW8B_CASE(true, 0, 2, true)
@@ -927,10 +977,19 @@ static fhe_status ntt_run(fhe_ctx* c, bool inverse, const uint64_t* xin, uint64_
     // the column pass of one chunk and the row pass of another on two streams (the queues split a CU's four workgroup slots: the
     // pair takes the sum of its parts) or as one grid of alternating roles (6 % slower); persistent pass kernels (11 % slower: a
     // fresh workgroup's loads overlap the drain of its predecessor's stores); 5 + 11 stages instead of 4 + 12 (1 % slower).
+    // hand-over (launch_pass): the plain inverse 4 + 12 transform with canonical output, for the part of the batch the batched row kernel takes.  A
+    // transform whose output stays lazy keeps the parent's words (another representative of the boundary product would show in them), and
+    // the epilogue and prologue instances keep the plain intermediate tower.
+    const uint32_t rowP  = row8_batch_for(T2);
+    const uint32_t handP = (canonOut && !(epi && epi->mode) && !proSrcLimb && ntt_handover_enabled() &&
+                            handover_pass_ok(c, p1, inverse, batch, rowP) && handover_pass_ok(c, p2, inverse, batch, rowP))
+                               ? rowP
+                               : 0u;
     if (fhe_status s = launch_pass(c, p1, inverse, xin, xout, sel, nLimbs, batch, false, stream, inStride, inFirst, outStride, outFirst,
-                                   nullptr, proSrcLimb, inDelta))
+                                   nullptr, proSrcLimb, inDelta, handP))
         return s;
-    return launch_pass(c, p2, inverse, xout, xout, sel, nLimbs, batch, canonOut, stream, outStride, outFirst, outStride, outFirst, epi);
+    return launch_pass(c, p2, inverse, xout, xout, sel, nLimbs, batch, canonOut, stream, outStride, outFirst, outStride, outFirst, epi, nullptr,
+                       0, handP);
 }
 
 extern "C" fhe_status fhe_ntt_fwd(fhe_ctx* c, uint64_t* x, const uint32_t* li, uint32_t nl, uint32_t b, void* st) {
@@ -4188,9 +4247,12 @@ extern "C" size_t fhe_launch_stats(char* buf, size_t cap, uint64_t* total) {
     uint64_t sum = 0;
     for (auto* s = fhe::rt::LaunchSite::head().load(); s; s = s->next) {
         std::string k = s->kernel;
+        const bool hand = k.find("kHandOver") != std::string::npos;
         k = k.substr(0, k.find('<'));
         k.erase(std::remove(k.begin(), k.end(), '('), k.end());
         byKernel[k] += s->n.load();
+        if (hand)  // the hand-over instances of the NTT passes once more, on a line of their own (not in the total twice)
+            byKernel[k + "<HAND>"] += s->n.load();
         sum += s->n.load();
     }
     std::vector<std::pair<uint64_t, std::string>> v;

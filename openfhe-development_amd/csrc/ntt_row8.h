@@ -211,6 +211,39 @@ FHE_HD void inv_stage(uint64_t (&r)[8], const TwPair (&w)[4], const BflyConst c,
         }
 #endif
 }
+// The last stage of an inverse row pass WITH HAND-OVER (register bit 2 of the closing, lazy-out w-step; coefficient bit T2 - 1): its twiddle
+// Table[2^T1 + r] depends on the row r of the column pass that follows only, and that pass multiplies by it on its way in (ntt_static.h,
+// hand_mul16).  Here: the plan's reductions and K, the sum as ever, the difference u - v + K q stored UNMULTIPLIED (bound: that of u plus K,
+// at most 16), no twiddle load.
+template <int BK = 0>
+FHE_HD void inv_stage_hand(uint64_t (&r)[8], const BflyConst c, uint32_t (&bnd)[8]) {
+#ifdef FHE_PINNED_ASM
+    (void)bnd;
+    FHE_R8_BK(stage_invh_full_b2(r, c));
+#else
+    using P = InvPlan<3, true>;
+    for (int i = 0; i < 4; ++i)
+        apply_red_op(r, P::pre[2][i], c, bnd);
+    for (int k0 = 0; k0 < 4; ++k0) {
+        const int k1 = k0 | 4;
+        const uint32_t K = P::K[2][k0];
+        FHE_BOUND_CHECK(bnd[k1] <= K && bnd[k0] + K <= 16u, "row8 hand-over: an inverse sum / difference outside its planned bounds");
+        FHE_BOUND_CHECK((unsigned __int128)r[k0] < (unsigned __int128)bnd[k0] * c.q &&
+                            (unsigned __int128)r[k1] < (unsigned __int128)bnd[k1] * c.q,
+                        "row8 hand-over: an inverse residue above its planned bound");
+        const uint64_t u = r[k0], v = r[k1];
+        r[k0] = u + v;
+        r[k1] = u - v + (uint64_t)K * c.q;
+        const uint32_t bu = bnd[k0];
+        bnd[k0] = bu + bnd[k1];
+        bnd[k1] = bu + K;
+    }
+    for (int k = 0; k < 8; ++k) {
+        FHE_BOUND_CHECK(bnd[k] == kInvOutFullHand[k] && bnd[k] <= 16u, "row8 hand-over: a closing step outside the generated bounds");
+        FHE_BOUND_CHECK((unsigned __int128)r[k] < (unsigned __int128)bnd[k] * c.q, "row8 hand-over: a handed-over word above its bound");
+    }
+#endif
+}
 template <int NB, int BK = 0>
 FHE_HD void inv_end(uint64_t (&r)[8], const BflyConst c, uint32_t (&bnd)[8]) {
 #ifdef FHE_PINNED_ASM
@@ -577,7 +610,7 @@ FHE_HD void fwd_step_b(uint64_t (&r)[P][8], const TwPair* tw, uint32_t hi, uint3
         if constexpr (NB >= 3) fwd_stage<UNI, 0, p>(r[p], w0, c, bnd[p]);
     FHE_R8_BANKS_END
 }
-template <bool UNI, int NB, bool LAZY, int P>
+template <bool UNI, int NB, bool LAZY, int P, bool HAND = false>
 FHE_HD void inv_step_b(uint64_t (&r)[P][8], const TwPair* tw, uint32_t hi, uint32_t F, uint32_t logN, const BflyConst c) {
     uint32_t bnd[P][8];
     for (int p = 0; p < P; ++p)
@@ -590,22 +623,28 @@ FHE_HD void inv_step_b(uint64_t (&r)[P][8], const TwPair* tw, uint32_t hi, uint3
     FHE_R8_BANKS(p)
         if constexpr (NB >= 3) inv_stage<UNI, NB, 0, p>(r[p], w0, c, bnd[p]);
     FHE_R8_BANKS_END
-    if constexpr (NB >= 3) load_tw<UNI, 2>(w2, tw, hi, F, logN);
+    static_assert(!HAND || (NB == 3 && LAZY), "row8 hand-over: the boundary stage is the last of the full step that closes a lazy-out pass");
+    if constexpr (NB >= 3 && !HAND) load_tw<UNI, 2>(w2, tw, hi, F, logN);
     FHE_R8_BANKS(p)
         if constexpr (NB >= 2) inv_stage<UNI, NB, 1, p>(r[p], w1, c, bnd[p]);
     FHE_R8_BANKS_END
     FHE_R8_BANKS(p)
-        if constexpr (NB >= 1) inv_stage<UNI, NB, 2, p>(r[p], w2, c, bnd[p]);
+        if constexpr (HAND) inv_stage_hand<p>(r[p], c, bnd[p]);
+        else if constexpr (NB >= 1) inv_stage<UNI, NB, 2, p>(r[p], w2, c, bnd[p]);
         if constexpr (!LAZY && NB >= 1) inv_end<NB, p>(r[p], c, bnd[p]);
     FHE_R8_BANKS_END
 }
 
 // a.batch / a.rows count GROUPS of P polynomials (the host passes batch / P): the tile order of tile_at, in units of P polynomials
-template <bool INV, int WB, int MODE, int P, bool X1P>
+// HAND (inverse only): the pass's last stage, on coefficient bit T2 - 1, leaves its twiddle product to the column pass that follows
+// (ntt_static.h, HAND): the intermediate tower between the two is NOT the one the other kernels exchange.  (The forward counterpart was built
+// and measured, and did not clear the bar on its own: profiles/r12_handover.md.)
+template <bool INV, int WB, int MODE, int P, bool X1P, bool HAND = false>
 FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
     static_assert(WB == 3, "row8 batched: 8 waves per tile (12 stages): the banked blocks exist for full radix-8 steps only");
     static_assert(P >= 2 && P <= 4, "row8 batched: register banks 0..3");
     static_assert(!(INV && MODE != 0), "row8: the inverse pass that ends a transform is ntt_static.h's");
+    static_assert(!HAND || INV, "row8 hand-over: the inverse pass only");
     constexpr uint32_t tileLog = 9u + (uint32_t)WB;
     constexpr uint32_t threads = 64u << WB;
     constexpr int WLOW         = 3 - WB;
@@ -755,7 +794,7 @@ FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
                     FHE_LDS_LD(r[p][k], Lr[x1(k)]);
             FHE_R8_BANKS_END
             // the column pass that follows reduces on the way in: no closing reductions
-            inv_step_b<true, WB, true, P>(r, tw, at.tr, 6 + WB, logN, c);
+            inv_step_b<true, WB, true, P, HAND>(r, tw, at.tr, 6 + WB, logN, c);
             FHE_R8_BANKS(p)
                 uint64_t* d0 = dst + (int64_t)p * outStep + tq_;
 #pragma unroll
@@ -773,10 +812,10 @@ FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
 // 16 P + 48 VGPRs: P = 2 at 80 (6 waves per SIMD: 3 workgroups, 6 tiles per CU), P = 4 at no more than 128 (4 waves: 2 workgroups,
 // 8 tiles); with a set of X1 regions per polynomial LDS sets the residency (P x 36 KiB: 2 workgroups / 1 workgroup per CU)
 constexpr int batched_waves(int P, bool X1P) { return X1P ? (P == 2 ? 4 : 2) : (P == 2 ? 6 : 4); }
-template <bool INV, int WB, int MODE, int P, bool X1P>
+template <bool INV, int WB, int MODE, int P, bool X1P, bool HAND = false>
 FHE_GLOBAL void FHE_LAUNCH_BOUNDS2(64 << WB, batched_waves(P, X1P)) ntt_row8_batched_kernel(const NttPassArgs a) {
     FHE_SHARED_U64(lds, (X1P ? P : 1) * (1 << WB) * kRegion);
-    ntt_row8_batched_core<INV, WB, MODE, P, X1P>(a, lds);
+    ntt_row8_batched_core<INV, WB, MODE, P, X1P, HAND>(a, lds);
 }
 
 }  // namespace r8

@@ -338,6 +338,43 @@ FHE_HD void epi_mul2(uint64_t (&r)[16], const TwPair cw, const BflyConst c, cons
     r[I | 8] = shoup_acc(0, r[I | 8], cw, nq);
 #endif
 }
+// Hand-over (the inverse 4-stage column pass behind the batched 12-stage row pass, ntt_row8.h HAND): the row pass's last stage, on coefficient
+// bit T2 - 1, has the twiddle Table[2^T1 + row] for every pair of a row, so the column pass -- whose lanes hold one residue of every row and
+// whose time is HBM's -- multiplies the stage's difference outputs (the columns with bit T2 - 1 set: whole tiles) by it on its way in: residue
+// k times tw[k], truncated Shoup quotient (any 64-bit value in, below 3q out: what the inverse plan's first stage assumes).
+// It REPLACES the quotient-estimate reduction those residues would get at that point.  The 16 scalar pairs are loaded in four groups of
+// four (16 SGPRs), each where it is used.
+template <int G>
+FHE_HD void hand_mul_group(uint64_t (&r)[16], const TwPair* tw, const BflyConst c, const BflyZero z) {
+    const uint64_t* p = reinterpret_cast<const uint64_t*>(tw);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(p));  // (the scalar loads are issued here, not hoisted to where their SGPRs would be spilled)
+#endif
+    constexpr int k0 = 2 * G, k1 = 2 * G + 1;
+    const TwPair wa0{FHE_ULOAD64(p, 2 * k0), FHE_ULOAD64(p, 2 * k0 + 1)}, wb0{FHE_ULOAD64(p, 2 * (k0 | 8)), FHE_ULOAD64(p, 2 * (k0 | 8) + 1)};
+    const TwPair wa1{FHE_ULOAD64(p, 2 * k1), FHE_ULOAD64(p, 2 * k1 + 1)}, wb1{FHE_ULOAD64(p, 2 * (k1 | 8)), FHE_ULOAD64(p, 2 * (k1 | 8) + 1)};
+#ifdef FHE_PINNED_ASM
+    if constexpr (G == 0) mul2t_s_0(r, wa0, wb0, c, z), mul2t_s_1(r, wa1, wb1, c, z);
+    if constexpr (G == 1) mul2t_s_2(r, wa0, wb0, c, z), mul2t_s_3(r, wa1, wb1, c, z);
+    if constexpr (G == 2) mul2t_s_4(r, wa0, wb0, c, z), mul2t_s_5(r, wa1, wb1, c, z);
+    if constexpr (G == 3) mul2t_s_6(r, wa0, wb0, c, z), mul2t_s_7(r, wa1, wb1, c, z);
+#else
+    (void)z;
+    const uint64_t nq = ((uint64_t)c.nqh << 32) | c.nql;
+    const TwPair w4[4] = {wa0, wb0, wa1, wb1};
+    const int k4[4]    = {k0, k0 | 8, k1, k1 | 8};
+    for (int i = 0; i < 4; ++i) {
+        r[k4[i]] = shoup_trunc(r[k4[i]], w4[i], nq);
+        FHE_BOUND_CHECK(r[k4[i]] < c.threeq, "hand-over: a truncated Shoup product of 3q or more");
+    }
+#endif
+}
+FHE_HD void hand_mul16(uint64_t (&r)[16], const TwPair* tw, const BflyConst c, const BflyZero z) {
+    hand_mul_group<0>(r, tw, c, z);
+    hand_mul_group<1>(r, tw, c, z);
+    hand_mul_group<2>(r, tw, c, z);
+    hand_mul_group<3>(r, tw, c, z);
+}
 FHE_HD void run_csub16(uint64_t (&r)[16], uint64_t m) {
 #ifdef FHE_PINNED_ASM
     csub16(r, m);
@@ -523,9 +560,13 @@ FHE_HD void lane_geom_s(uint32_t t, uint32_t S, uint32_t& Ib, uint32_t& jrel, ui
 // row pass whose first step both act on tile bit 0 hold the same 16 consecutive residues per lane.
 // PRO: the first load takes every limb of a tower from one COEFFICIENT row modulo another limb's modulus and switches it to the
 // limb's own modulus (NttPassArgs::proMode) — forward column passes only.
-template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool RAWIN = false, bool RAWOUT = false, bool PRO = false>
+// HAND: the inverse 4-stage column pass does the twiddle products of the preceding row pass's last stage (hand_mul16) on its way in, for the
+// tiles whose columns have coefficient bit T2 - 1 set.  Its partner is ntt_row8.h's batched kernel with HAND;
+// no other kernel reads or writes that intermediate tower.
+template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool RAWIN = false, bool RAWOUT = false, bool PRO = false, bool HAND = false>
 FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, uint64_t (&r)[16]) {
     using P = SPlan<LA, INV, T>;
+    static_assert(!HAND || (LA && INV && T == 4 && MODE == 1 && !EPI && !PRO), "hand-over exists for the plain inverse 4-stage column pass only");
     static_assert(!(RAWIN || RAWOUT) || !LA, "register hand-over exists for row passes only");
     static_assert(!PRO || (LA && !INV && !RAWIN), "the load prologue exists for forward column passes only");
     const uint32_t t    = FHE_TID;
@@ -596,6 +637,10 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
     const uint64_t* src = a.inDelta ? a.xin + (int64_t)tb * a.inDelta + ((uint64_t)(a.inFirst + (PRO ? 0u : rit)) << logN) + jbase
                                     : a.xin + (inRow << logN) + jbase;
     uint64_t* dst       = a.x + (outRow << logN) + jbase;
+
+    // hand-over: this tile's columns are the boundary stage's difference outputs (one answer per workgroup: a tile's 2^logC columns are aligned)
+    const bool handTile   = HAND && ((jbase >> (logN - (uint32_t)T - 1u)) & 1u);
+    const TwPair* handTw  = ts.tw + ((size_t)1 << T);  // Table[2^T1 + row]; register k of the one step = row k
 
     uint32_t Ib, jrel;
     uint64_t ks;
@@ -703,8 +748,12 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
             _Pragma("unroll") for (int k = 0; k < 16; ++k) FHE_LDS_LD(r[k], L[lds_pad((uint32_t)k << fI)]);                  \
         }                                                                                                         \
         /* an inverse column pass takes what the lazy row pass left (anything below 16q) */                        \
-        if constexpr (I == 0 && INV && LA)                                                                        \
-            run_red16(r, c);                                                                                      \
+        if constexpr (I == 0 && INV && LA) {                                                                      \
+            if (handTile)                                                                                         \
+                hand_mul16(r, handTw, c, z); /* the row pass's last stage left its product to this pass */          \
+            else                                                                                                  \
+                run_red16(r, c);                                                                                  \
+        }                                                                                                         \
         /* lazy reduction: a forward butterfly's outputs are bounded by its `a` input + 3q whatever the `b` input  \
            (< 2^64) is, so only the 8 `a` inputs of the step's first stage go back below 2q */                      \
         if constexpr (!INV && P::sweep(I, BIN))                                                                  \
@@ -755,13 +804,13 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
     }
 }
 
-template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool PRO = false>
+template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool PRO = false, bool HAND = false>
 FHE_DEV void ntt_static_body(const NttPassArgs& a, uint32_t bid, uint64_t* lds) {
     uint64_t r[16];
-    ntt_static_core<LA, INV, T, MODE, EPI, false, false, PRO>(a, bid, lds, r);
+    ntt_static_core<LA, INV, T, MODE, EPI, false, false, PRO, HAND>(a, bid, lds, r);
 }
 
-template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool PRO = false>
+template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool PRO = false, bool HAND = false>
 FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ntt_static_kernel(const NttPassArgs a) {
     // a single-step pass without staging (the 4-stage column pass) never touches LDS: do not reserve any, so that
     // more workgroups fit on a CU
@@ -771,7 +820,7 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ntt_static_kernel(const NttPassArgs 
 #define FHE_ABL_LDSPAD 0
 #endif
     FHE_SHARED_U64(lds, needsLds ? kLdsPadWords + kSharedTwWords + FHE_ABL_LDSPAD : 1);
-    ntt_static_body<LA, INV, T, MODE, EPI, PRO>(a, FHE_BID, lds);
+    ntt_static_body<LA, INV, T, MODE, EPI, PRO, HAND>(a, FHE_BID, lds);
 }
 
 

@@ -204,6 +204,10 @@ class Lib:
                 return int(n)
         return 0
 
+    def handover_counts(self):
+        """launches of the hand-over instances since the library was loaded: (inverse row pass, inverse column pass)"""
+        return self.launch_count("ntt_row8_batched_kernel<HAND>"), self.launch_count("ntt_static_kernel<HAND>")
+
     def blake2xb_stream(self, key, counter0, n_blocks):
         """uint32[n_blocks][1024]: the 4 KiB blocks blake2xb(in = counter0 + k, key) of Blake2Engine (fhe_blake2xb_stream)"""
         if getattr(self, "_tiny", None) is None:

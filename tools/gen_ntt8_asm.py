@@ -107,6 +107,33 @@ def inv_plan(bLo=0, bHi=2, lazy_out=False, B0=3):
     return pre, K, end, bound
 
 
+def addsub_stream(i, A, B, kop):
+    """the last stage of an inverse row pass with hand-over (the column pass that follows does the stage's twiddle product):
+    a' = a + b, b' = a - b + K with K the plan's multiple of q (the bound of b) given as the scalar operand `kop`; chain i of 4,
+    temporaries and carry registers of the reduction chains"""
+    D, c = g.CSUB_TMP[i], f"s[{42 + 2 * i}:{43 + 2 * i}]"
+    return [
+        g.lshladd(p(D), p(A), 0, kop),
+        g.lshladd(p(A), p(A), 0, p(B)),
+        g.subco(v(B), c, v(D), v(B)),
+        g.subbco(v(B + 1), c, v(D + 1), v(B + 1), c),
+    ]
+
+
+def inv_plan_hand():
+    """the full lazy-out step whose LAST stage (register bit 2) hands its product to the column pass: the reductions and K of
+    inv_plan(0, 2, True); the difference output keeps the bound of u plus K (at most 16, as the plan guarantees for u - v + K)"""
+    pre, K, _, _ = inv_plan(0, 2, True)
+    bound = inv_plan(0, 1, True)[3]
+    for op in pre[2]:
+        bound[op[1]] = op[2] if op[0] == "c" else 2
+    for j, (k0, k1, _g) in enumerate(stage_pairs(2)):
+        assert bound[k1] <= K[2][j] and bound[k0] + K[2][j] <= 16
+        bound[k0], bound[k1] = bound[k0] + bound[k1], bound[k0] + K[2][j]
+    assert max(bound) <= 16
+    return pre, K, bound
+
+
 # ---- simulation ------------------------------------------------------------------------------------------------------------
 def check_blocks(iters=3000, steps=60):
     """simulates the blocks on the bank g.DATA0 points at"""
@@ -161,6 +188,47 @@ def check_blocks(iters=3000, steps=60):
         for i, x0 in enumerate(xs):
             got = S.g64(p(R(i)))
             assert got < 2 * q and got % q == x0 % q, "red (ladder)"
+    # the inverse step that closes a row pass with hand-over: stages 0, 1 of the lazy plan, then sums and UNMULTIPLIED differences
+    pre, K, final = inv_plan_hand()
+    for it in range(steps):
+        q = (1 << 60) - 16383 if it < 4 else g.rand_modulus(rnd)
+        slow = it % 5 == 4
+        S = St()
+        g.limb_ops(S, q)
+        x = [rnd.randrange(3 * q) if it else 3 * q - 1 for _ in range(8)]
+        ref = [v_ % q for v_ in x]
+        bnd = [3] * 8
+        for k in range(8):
+            S.set64(p(R(k)), x[k])
+        for b in range(3):
+            for grp in g.op_blocks(pre[b]):
+                run(sched([g.op_stream(i, op, slow) for i, op in enumerate(grp)]), S)
+                for op in grp:
+                    bnd[op[1]] = op[2] if op[0] == "c" else 2
+            prs = stage_pairs(b)
+            for (u_, v_, _g), m in zip(prs, K[b]):
+                assert S.g64(p(R(u_))) < bnd[u_] * q and S.g64(p(R(v_))) < bnd[v_] * q and bnd[v_] <= m and bnd[u_] + m <= 16
+            if b == 2:
+                run(sched([addsub_stream(j, R(u_), R(v_), f"%[k{K[2][j]}]") for j, (u_, v_, _g) in enumerate(prs)]), S)
+                for j, (u_, v_, _g) in enumerate(prs):
+                    ref[u_], ref[v_] = (ref[u_] + ref[v_]) % q, (ref[u_] - ref[v_]) % q
+                    bnd[u_], bnd[v_] = bnd[u_] + bnd[v_], bnd[u_] + K[2][j]
+                continue
+            for j in range(0, 4, 2):
+                tw = [rnd.randrange(q), rnd.randrange(q)]
+                for i in (0, 1):
+                    g.tw_ops(S, i, tw[i], q)
+                (a0, a1, _), (b0, b1, _) = prs[j], prs[j + 1]
+                run(sched([g.inv_lazy_stream(T, R(a0), R(a1), 0, f"%[k{K[b][j]}]")
+                           + g.inv_lazy_stream(T, R(b0), R(b1), 1, f"%[k{K[b][j + 1]}]")]), S)
+                for (u_, v_), w_ in (((a0, a1), tw[0]), ((b0, b1), tw[1])):
+                    ru, rv = ref[u_], ref[v_]
+                    ref[u_], ref[v_] = (ru + rv) % q, (ru - rv) * w_ % q
+                    bnd[u_], bnd[v_] = bnd[u_] + bnd[v_], g.INV_PROD
+        assert bnd == final and max(final) <= 16, (bnd, final)
+        for k in range(8):
+            got = S.g64(p(R(k)))
+            assert got < final[k] * q and got % q == ref[k], ("inverse step with hand-over", k)
     # lazy inverse steps: every stage range a pass shape can ask for, with and without the closing reductions
     for (bLo, bHi) in ((0, 2), (1, 2), (2, 2)):
         for lazy in (False, True):
@@ -267,6 +335,15 @@ def emit_reduce_fn(name, items):
     return f"__device__ __forceinline__ void {name}(uint64_t (&r)[8], const BflyConst c) {{\n    (void)c;\n{emit_ops_body(items)}}}\n"
 
 
+def emit_hand_fns():
+    """the last stage of the batched inverse row pass with hand-over: one block of four interleaved chains, no twiddle operands"""
+    prs = stage_pairs(2)
+    outs = [pin(k, f"r[{k}]") for pr in prs for k in pr[:2]]
+    K = inv_plan_hand()[1]
+    inv = asm_block(g.schedule([addsub_stream(j, R(k0), R(k1), f"%[k{K[2][j]}]") for j, (k0, k1, _g) in enumerate(prs)]), outs)
+    return (f"__device__ __forceinline__ void stage_invh_full_b2(uint64_t (&r)[8], const BflyConst c) {{\n    inv_pre_full_b2(r, c);\n{inv}}}\n")
+
+
 def emit_csub_fn(name, ks):
     block = g.schedule([g.csub_stream(i, R(k)) for i, k in enumerate(ks)])
     outs = [pin(k, f"r[{k}]") for k in ks]
@@ -323,6 +400,7 @@ def bank_text(data0):
             H.append(f"__device__ __forceinline__ void stage_invl_{cls}_full_b{b}(uint64_t (&r)[8], const TwPair (&w)[4], "
                      f"const BflyConst c) {{\n    inv_pre_full_b{b}(r, c);\n" + "".join(fn) + "}\n")
     H.append(emit_reduce_fn("inv_end_full", inv_plan(0, 2, False)[2]))
+    H.append(emit_hand_fns())
     for i in range(2):
         H.append(emit_csub_fn(f"csub4_{i}", [4 * i + j for j in range(4)]))
     H.append("""__device__ __forceinline__ void csub8(uint64_t (&r)[8], uint64_t m) {
@@ -396,6 +474,8 @@ struct RedOp {
                      f"constexpr unsigned char kInvK{tag}[3][4] = {{{k_rows}}};  // K (units of q) of u - v + K, per stage and butterfly\n"
                      f"constexpr RedOp kInvEnd{tag}[8] = {op_table(end, 8)};\n"
                      f"constexpr unsigned char kInvOut{tag}[8] = {{{', '.join(str(x) for x in final)}}};  // bounds on return (units of q)\n")
+    H.append("// the full lazy step whose last stage hands its product to the column pass (pre / K: kInvPreFullLazy / kInvKFullLazy)\n"
+             f"constexpr unsigned char kInvOutFullHand[8] = {{{', '.join(str(x) for x in inv_plan_hand()[2])}}};  // bounds on return (units of q)\n")
     H.append("}  // namespace r8\n}  // namespace fhe\n#if defined(__HIP_DEVICE_COMPILE__) && !defined(FHE_NO_BFLY_ASM)\nnamespace fhe {\nnamespace r8 {\n")
     # forward stages
     for b in range(3):
@@ -429,6 +509,8 @@ struct RedOp {
                          f"const BflyConst c) {{\n    inv_pre_{name}_b{b}(r, c);\n" + "".join(fn) + "}\n")
         _, _, end, _ = inv_plan(sel[0], sel[1], False)
         H.append(emit_reduce_fn(f"inv_end_{name}", end))
+        if name == "full":
+            H.append(emit_hand_fns())
     # exact products of residues i and i|4 (the transform's last inverse stage, the fused epilogue)
     for i in range(4):
         H.append(emit_mul_fn(f"mul2_s_{i}", i, i | 4, "s"))

@@ -249,10 +249,12 @@ def inv_lazy_stream(t, A, B, w, kop):
     return pre + head + tail
 
 
-def mul_stream(t, A, w):
+def mul_stream(t, A, w, exact=True):
     """x = shoup(x, w) in place with the EXACT quotient (< 2q): last inverse stage (the caller forms u+v / u-v+K first)
-    and the fused epilogue; x is only overwritten by the last instruction, after every read of its halves"""
-    head, tail = shoup_tail(t, v(A), v(A + 1), w, p(A), "0", exact=True)
+    and the fused epilogue; x is only overwritten by the last instruction, after every read of its halves.
+    exact=False: the truncated quotient (< 3q, any 64-bit x): the product a column pass with hand-over does for the row
+    pass's boundary stage (ntt_static.h, hand_mul16)"""
+    head, tail = shoup_tail(t, v(A), v(A + 1), w, p(A), "0", exact=exact)
     return head + tail
 
 
@@ -534,6 +536,13 @@ def check_blocks():
         run(schedule([mul_stream(t0, R(1), 0), mul_stream(t1, R(9), 1)]), S)
         for i, k in enumerate((1, 9)):
             assert S.g64(p(R(k))) == shoup_ref(x[i], w[i], wp[i], q) < 2 * q
+        # the hand-over product (truncated quotient) in place: any 64-bit input, result below 3q
+        x = [rnd.getrandbits(64), M64 if it % 5 == 0 else rnd.randrange(16 * q)]
+        S.set64(p(R(2)), x[0]), S.set64(p(R(10)), x[1])
+        run(schedule([mul_stream(t0, R(2), 0, exact=False), mul_stream(t1, R(10), 1, exact=False)]), S)
+        for i, k in enumerate((2, 10)):
+            got = S.g64(p(R(k)))
+            assert got == shoup_trunc_ref(x[i], w[i], wp[i], q) < 3 * q and got % q == x[i] * w[i] % q, "hand-over product"
         # conditional subtraction, 4 residues per block
         m = q << rnd.randrange(0, 4)
         S.ops.update({"m": m, "negm": (-m) & M64})
@@ -744,8 +753,8 @@ def emit_reduce_fn(name, items):
     return f"__device__ __forceinline__ void {name}(uint64_t (&r)[16], const BflyConst c) {{\n    (void)c;\n{emit_ops_body(items)}}}\n"
 
 
-def emit_mul_fn(name, ka, kb, cls):
-    block = schedule([mul_stream(T(0), R(ka), 0), mul_stream(T(1), R(kb), 1)])
+def emit_mul_fn(name, ka, kb, cls, exact=True):
+    block = schedule([mul_stream(T(0), R(ka), 0, exact), mul_stream(T(1), R(kb), 1, exact)])
     outs = [pin(ka, f"r[{ka}]"), pin(kb, f"r[{kb}]")]
     return f"__device__ __forceinline__ void {name}({TW_ARGS}) {{\n{TW_BODY}" + asm_block(block, outs, 2, cls) + "}\n"
 
@@ -887,6 +896,9 @@ struct BflyZero {   // two VGPRs holding 0 (high halves of the zero-extended mul
     # last inverse stage (s == 0): residues lo and lo|8 multiplied by N^-1 and w1*N^-1 (exact quotient)
     for i in range(8):
         H.append(emit_mul_fn(f"mul2_s_{i}", i, i | 8, "s"))
+    # hand-over (column pass -> row pass's boundary stage): residues i and i|8 times their own twiddle, truncated quotient (< 3q)
+    for i in range(8):
+        H.append(emit_mul_fn(f"mul2t_s_{i}", i, i | 8, "s", exact=False))
     for i in range(4):
         H.append(emit_csub_fn(f"csub4_{i}", [4 * i + j for j in range(4)]))
     fold, sh, lo, fin = reduce192_stream()
