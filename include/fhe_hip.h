@@ -329,7 +329,8 @@ fhe_status fhe_eval_automorphism(fhe_ks_plan* plan, const fhe_ks_key* key, const
  * key is its own tower.  out_e[b][i] = sum_{t < nTerms} x[t][b][i] * k_e[t][keyRow[i]] mod q_{limbIdx[i]}, e = 0 (k0 -> out0)
  * and, when k1/out1 are given, e = 1.  x[t] is [batch][rows][N], k_e[t] is a tower of at least max(keyRow)+1 rows, keyRow NULL
  * = identity (the reference's idx(i) = i < sizeQl ? i : i + sizeQ - sizeQl, :425).  x, k0, k1 are HOST arrays of device
- * pointers; all operands are canonical residues; 1 <= nTerms <= 8 (FHE_ERR_UNSUPPORTED beyond). */
+ * pointers; all operands are canonical residues; nTerms >= 1: one launch per 8 terms, each launch after the first adds its (exact) sums
+ * to what the earlier ones left in out0 / out1. */
 fhe_status fhe_inner_product(fhe_ctx* ctx, uint32_t nTerms, const uint64_t* const* x, const uint64_t* const* k0,
                              const uint64_t* const* k1, const uint32_t* keyRow, const uint32_t* limbIdx, uint32_t rows,
                              uint32_t batch, uint64_t* out0, uint64_t* out1, void* stream);
@@ -502,7 +503,8 @@ fhe_status fhe_bfv_eval_mult_relin_behz(fhe_behz* plan, fhe_ks_plan* ks, const f
  * 64-bit modular arithmetic.  numQ + numR <= 256.  fhe_hps_table reads a derived table back (ids and layouts: see the definition
  * in fhe_hip.cpp; doubles as bit patterns); it returns the table's length in 64-bit words, 0 if the plan has no such table.
  * fhe_bfv_eval_mult_hps: inputs [batch][numQ][N] EVALUATION -> outputs [batch][numQ][N], COEFFICIENT as the reference leaves
- * them, or EVALUATION when outEval != 0 (then fhe_keyswitch_hybrid_acc relinearises).  sizeQl = l + 1 is the number of Q limbs the
+ * them, or EVALUATION when outEval != 0 (then fhe_keyswitch_hybrid_acc relinearises with a HYBRID key, fhe_keyswitch_bv with accumulate != 0
+ * with a BV key; fhe_bfv_eval_mult_relin_hps_bv is the whole BV sequence).  sizeQl = l + 1 is the number of Q limbs the
  * product is computed over: numQ for HPS and HPSPOVERQ; for HPSPOVERQLEVELED the caller's numQ - levelsDropped (FindLevelsToDrop is
  * host-side noise estimation and stays in pke).  A wrong sizeQl or too small a workspace is an error and enqueues nothing.  The call
  * builds nothing lazily, allocates nothing and does not synchronise: it can be captured into a graph.
@@ -525,6 +527,55 @@ size_t     fhe_bfv_eval_mult_hps_workspace_bytes(const fhe_hps* plan, uint32_t s
 fhe_status fhe_bfv_eval_mult_hps(fhe_hps* plan, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
                                  uint64_t* d0, uint64_t* d1, uint64_t* d2, uint32_t sizeQl, int outEval, uint32_t batch,
                                  void* ws, size_t wsBytes, void* stream);
+
+/* ---- BV key switching ---------------------------------------------------------------------------------------
+ * KeySwitchBV (src/pke/lib/keyswitch/keyswitch-bv.cpp), the reference's default technique for BFV (gen-cryptocontext-params-defaults.h) and
+ * the one PRE and multiparty use.  No auxiliary basis and no ModDown: the same calls serve BFV, BGV and CKKS.  The tower uses the context's
+ * leading limbs [0, sizeQ); baseBits is the digit size r (0: one digit per limb).
+ * A key is the b and a vectors of the evaluation key (KeySwitchGenInternal, keyswitch-bv.cpp:49-103): D_0 =
+ * fhe_crt_decompose_towers(ctx, NULL, sizeQ, baseBits) towers over all sizeQ limbs each, in the order of DCRTPolyImpl::CRTDecompose (limb 0's
+ * windows, least significant first, then limb 1's ...).  The windows of a limb depend on its modulus only, so a level sizeQl <= sizeQ uses the
+ * FIRST D_l = fhe_crt_decompose_towers(ctx, NULL, sizeQl, baseBits) key towers, and of each its first sizeQl rows (DropLastElements, :264-271):
+ * output limb i meets key row i.  The key carries (ctx, sizeQ, baseBits, D_0); there is no plan object.
+ * Apart from key upload every call builds nothing lazily, allocates nothing and does not synchronise: it can be captured into a graph.  An
+ * error enqueues nothing: a null argument, sizeQl outside [1, sizeQ], too small a workspace, a key of another context, and
+ * FHE_ERR_UNSUPPORTED at key upload and at precompute for a digit size outside the device path (fhe_crt_decompose_towers == 0).
+ * Digits and key must have the same baseBits, and the CALLER pairs them: fhe_bv_fast_keyswitch receives no baseBits for the digits in ws
+ * (fhe_keyswitch_bv and fhe_bfv_eval_mult_relin_hps_bv cut them with the key's own, so they cannot mismatch).  What the call can see is
+ * the workspace size: a key of a SMALLER digit size than the precompute's needs more towers than a workspace sized for the precompute
+ * holds and is refused; a key of a LARGER digit size needs fewer, passes the check and sums towers that do not belong to it — NOT
+ * detected, the result is then meaningless (all reads stay inside ws and the key).
+ * out0 / out1 must not alias c or ws; c is only read.  Any number of host threads and streams may share one key.
+ *   fhe_bv_precompute      = EvalKeySwitchPrecomputeCore (:251-259), a.CRTDecompose(r) (dcrtpoly-impl.h:230-285): c [batch][sizeQl][N] in
+ *                            evalFormat (0: COEFFICIENT) -> digits [D_l][batch][sizeQl][N] EVALUATION, canonical residues, at the start of ws.
+ *                            Digit-major: the `batch` towers of one digit are one contiguous wide tower.  (baseBits == 0: the reference copies an
+ *                            EVALUATION input's limb i into digit i instead of transforming it, :237-251; the words are the same.)
+ *   fhe_bv_fast_keyswitch  = EvalFastKeySwitchCore (:261-278) on the digits fhe_bv_precompute left in ws (hoisting: one precompute, many keys):
+ *                            out_e[b][i] = sum_{d < D_l} digits[d][b][i] * key_e[d][i] mod q_i; accumulate != 0: out0 += ks0, out1 += ks1, the
+ *                            tail of LeveledSHEBase::EvalMult(ct, ct, key) (base-leveledshe.cpp:207-211)
+ *   fhe_keyswitch_bv       = KeySwitchCore (:245-249): the two above on c [batch][sizeQl][N] EVALUATION
+ *   fhe_bfv_eval_mult_relin_hps_bv = LeveledSHEBase::EvalMult(ct, ct, key) (base-leveledshe.cpp:201-214) on BFV ciphertexts of the HPS family
+ *                            with a BV key (HPSPOVERQLEVELED + BV is the reference's default BFV configuration): fhe_bfv_eval_mult_hps(outEval = 1)
+ *                            with d0, d1 written to c0, c1 and d2 into ws, then fhe_keyswitch_bv(accumulate = 1) at numQ limbs.  sizeQl as for
+ *                            fhe_bfv_eval_mult_hps; the plan's Q must be the context's leading limbs and the key built over them. */
+typedef struct fhe_bv_key fhe_bv_key;
+/* keyB, keyA: HOST uint64_t[D_0][sizeQ][N] each, EVALUATION */
+fhe_status fhe_bv_key_upload(fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, const uint64_t* keyB, const uint64_t* keyA, fhe_bv_key** out);
+/* adopt key vectors that already live in device memory (not owned: destroy leaves them alone) */
+fhe_status fhe_bv_key_wrap(fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint64_t* devKeyB, uint64_t* devKeyA, fhe_bv_key** out);
+void       fhe_bv_key_destroy(fhe_bv_key* key);
+/* device bytes the calls below need for `batch` towers at level sizeQl: the digits and one coefficient copy; 0 outside the device path */
+size_t     fhe_bv_workspace_bytes(const fhe_ctx* ctx, uint32_t sizeQl, uint32_t baseBits, uint32_t batch);
+fhe_status fhe_bv_precompute(fhe_ctx* ctx, const uint64_t* c, int evalFormat, uint32_t sizeQl, uint32_t baseBits, uint32_t batch,
+                             void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bv_fast_keyswitch(const fhe_bv_key* key, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1, int accumulate,
+                                 const void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_keyswitch_bv(const fhe_bv_key* key, const uint64_t* c, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1,
+                            int accumulate, void* ws, size_t wsBytes, void* stream);
+size_t     fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes(const fhe_hps* plan, uint32_t sizeQl, uint32_t baseBits, uint32_t batch);
+fhe_status fhe_bfv_eval_mult_relin_hps_bv(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
+                                          const uint64_t* b1, uint64_t* c0, uint64_t* c1, uint32_t sizeQl, uint32_t batch,
+                                          void* ws, size_t wsBytes, void* stream);
 
 /* ---- parity helper: whole-tower checksums ----------------------------------------------------------------
  * out[row] = { sum_i w_i, sum_i (2i + 1) * w_i } mod 2^64 over the row's N words, for every limb-row of x[rows][N] (rows = batch *

@@ -488,6 +488,129 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) inner_rows_kernel(const InnerRowsArg
     }
 }
 
+// ---- BV inner product ----------------------------------------------------------------------------------
+// KeySwitchBV::EvalFastKeySwitchCore (keyswitch-bv.cpp:261-278) after DropLastElements (:264-271): for every ciphertext b, output limb
+// i < sizeQl, coefficient r
+//   out0 = sum_{d < D} digits[d][b][i] * keyB[d][i],   out1 = sum_{d < D} digits[d][b][i] * keyA[d][i]      (mod q_i)
+// over the digit-major towers fhe_bv_precompute leaves ([D][batch][sizeQl][N], canonical residues) and the first D towers of a key
+// built over sizeQ >= sizeQl limbs (row i of a key tower is limb i: no index skip).  D has no bound (up to 256 limbs x 60 windows):
+// digit d and key tower d are reached by stride from one base pointer each.  A lane walks the digits in chunks of 8 -- the loads of
+// half a chunk are issued back to back, the column sums (sum8, modarith.h) of both outputs take one reduction each per chunk -- and adds
+// the chunks' residues in registers: the outputs are stored once (and, with acc, read once), where one launch per 8
+// terms re-reads and re-writes both.  Workgroup order as ks_inner_product_kernel: the `batch` workgroups that share a key tile take
+// consecutive slots of one XCD.
+struct BvInnerArgs {
+    const uint64_t* digits;  // [D][batch][sizeQl][N] EVAL, canonical
+    const uint64_t* keyB;    // [>= D][sizeQ][N]
+    const uint64_t* keyA;
+    uint64_t* out0;          // [batch][sizeQl][N]
+    uint64_t* out1;
+    const LimbConst* lc;     // [ctxLimbs]
+    const uint64_t* mu128;   // [ctxLimbs][2]
+    uint32_t logN, batch, sizeQl, sizeQ, D, acc;
+};
+template <int CPL>
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bv_inner_product_kernel(const BvInnerArgs g) {
+    const uint32_t t           = FHE_TID;
+    const uint32_t N           = 1u << g.logN;
+    const uint32_t tilesPerRow = N >> kTileLog ? (N >> kTileLog) : 1u;
+    const uint32_t xcd = FHE_BID & 7u, slot = FHE_BID >> 3;
+    const uint32_t b   = slot % g.batch;
+    const uint32_t grp = (slot / g.batch) * 8u + xcd;
+    const uint32_t tr = grp % tilesPerRow;
+    const uint32_t i  = grp / tilesPerRow;
+    if (i >= g.sizeQl)
+        return;
+    const LimbConst lc  = g.lc[i];
+    const uint64_t mulo = g.mu128[2 * i], muhi = g.mu128[2 * i + 1];
+    const uint64_t q    = lc.q;
+    const uint32_t rEnd = ((tr + 1u) << kTileLog) < N ? ((tr + 1u) << kTileLog) : N;
+    const uint64_t dStride = ((uint64_t)g.batch * g.sizeQl) << g.logN, kStride = (uint64_t)g.sizeQ << g.logN;
+    const uint64_t ooff0 = ((uint64_t)b * g.sizeQl + i) << g.logN, koff0 = (uint64_t)i << g.logN;
+    for (uint32_t r = (tr << kTileLog) + CPL * t; r < rEnd; r += CPL * kThreads) {
+        // (wave-uniform row pointers walked by stride + one lane offset: the addresses stay in scalar registers)
+        const uint64_t* dp = g.digits + ooff0;
+        const uint64_t* kb = g.keyB + koff0;
+        const uint64_t* ka = g.keyA + koff0;
+        uint64_t v0[CPL], v1[CPL];
+#pragma unroll
+        for (int u = 0; u < CPL; ++u)
+            v0[u] = v1[u] = 0;
+        uint32_t d0 = 0;
+        for (; d0 + 8u <= g.D; d0 += 8u) {  // full chunks, in two halves: the 12 loads of a half are issued back to back
+            sum8 s0[CPL], s1[CPL];
+#pragma unroll
+            for (int u = 0; u < CPL; ++u) {
+                sum8_clear(s0[u]);
+                sum8_clear(s1[u]);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                uint64_t x[4][CPL], yb[4][CPL], ya[4][CPL];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ld_cpl<CPL>(dp + (4 * h + j) * dStride + r, x[j]);
+                    ld_cpl<CPL>(kb + (4 * h + j) * kStride + r, yb[j]);
+                    ld_cpl<CPL>(ka + (4 * h + j) * kStride + r, ya[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int u = 0; u < CPL; ++u) {
+                        FHE_BOUND_CHECK(x[j][u] < q && yb[j][u] < q && ya[j][u] < q,
+                                        "BV key switch: a word of q or more enters the 64-bit column sums");
+                        sum8_add(s0[u], x[j][u], yb[j][u]);
+                        sum8_add(s1[u], x[j][u], ya[j][u]);
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < CPL; ++u) {
+                v0[u] = add_mod(v0[u], sum8_reduce(s0[u], q, lc.msb, mulo, muhi), q);
+                v1[u] = add_mod(v1[u], sum8_reduce(s1[u], q, lc.msb, mulo, muhi), q);
+            }
+            dp += 8 * dStride, kb += 8 * kStride, ka += 8 * kStride;
+        }
+        if (d0 < g.D) {  // the last, partial chunk
+            sum8 s0[CPL], s1[CPL];
+#pragma unroll
+            for (int u = 0; u < CPL; ++u) {
+                sum8_clear(s0[u]);
+                sum8_clear(s1[u]);
+            }
+            for (; d0 < g.D; ++d0) {
+                uint64_t x[CPL], yb[CPL], ya[CPL];
+                ld_cpl<CPL>(dp + r, x);
+                ld_cpl<CPL>(kb + r, yb);
+                ld_cpl<CPL>(ka + r, ya);
+#pragma unroll
+                for (int u = 0; u < CPL; ++u) {
+                    FHE_BOUND_CHECK(x[u] < q && yb[u] < q && ya[u] < q, "BV key switch: a word of q or more enters the 64-bit column sums");
+                    sum8_add(s0[u], x[u], yb[u]);
+                    sum8_add(s1[u], x[u], ya[u]);
+                }
+                dp += dStride, kb += kStride, ka += kStride;
+            }
+#pragma unroll
+            for (int u = 0; u < CPL; ++u) {
+                v0[u] = add_mod(v0[u], sum8_reduce(s0[u], q, lc.msb, mulo, muhi), q);
+                v1[u] = add_mod(v1[u], sum8_reduce(s1[u], q, lc.msb, mulo, muhi), q);
+            }
+        }
+        if (g.acc) {
+            uint64_t p0[CPL], p1[CPL];
+            ld_cpl<CPL>(g.out0 + ooff0 + r, p0);
+            ld_cpl<CPL>(g.out1 + ooff0 + r, p1);
+#pragma unroll
+            for (int u = 0; u < CPL; ++u) {
+                v0[u] = add_mod(v0[u], p0[u], q);
+                v1[u] = add_mod(v1[u], p1[u], q);
+            }
+        }
+        st_cpl<CPL>(g.out0 + ooff0 + r, v0);
+        st_cpl<CPL>(g.out1 + ooff0 + r, v1);
+    }
+}
+
 // ---- baby-step/giant-step inner sums (double hoisting) --------------------------------------------
 // inner_i[e][b][l][r] = sum_j rot_j[e][b][l][r] * diag_{i,j}[l][r]  over the extended basis Q_l u P, for ALL outer steps i
 // in one pass: the EvalMultExt / EvalAddExtInPlace chains of FHECKKSRNS::EvalLinearTransform (ckksrns-fhe.cpp:1855-1859,

@@ -390,35 +390,57 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) switch_modulus_kernel(const SwitchMo
     }
 }
 
-// ---- DCRTPolyImpl::CRTDecompose (dcrtpoly-impl.h:230-285; the digit decomposition of KeySwitchBV): the nW digits of ONE source limb,
-// each lifted (centred, PolyImpl::SwitchModulus) into every limb of its own tower; COEFFICIENT in, COEFFICIENT out (the caller
-// transforms all towers in one launch).  Digit w of a word = its bits [w * baseBits, (w + 1) * baseBits) (PolyImpl::BaseDecompose,
-// poly-impl.h:524-547 -> GetDigitAtIndexForBase, ubintnat.h:1721-1729); baseBits == 0: the word itself, one tower (:237-251).
+// ---- DCRTPolyImpl::CRTDecompose (dcrtpoly-impl.h:230-285; the digit decomposition of KeySwitchBV) of a whole batch in ONE launch: every
+// window of every source limb, each lifted (centred, PolyImpl::SwitchModulus) into every limb of its own tower; COEFFICIENT in,
+// COEFFICIENT out (the caller transforms all towers in one launch).  Digit w of a word = its bits [w * baseBits, (w + 1) * baseBits)
+// (PolyImpl::BaseDecompose, poly-impl.h:524-547 -> GetDigitAtIndexForBase, ubintnat.h:1721-1729); baseBits == 0: the word itself, one
+// tower (:237-251).  Output is digit-major, [towers][batch][nLimbs][N]: the towers of all ciphertexts transform as one batch of
+// towers * batch (rows periodic in nLimbs), and the `batch` towers of one digit are one contiguous wide tower.
+// One workgroup = one (source limb, window, ciphertext, 4096-coefficient tile): it reads its source words once and writes the nLimbs
+// rows of its tower.  The grid spans maxW windows per source limb; a workgroup whose limb has fewer windows (moduli of different
+// lengths) leaves at once.
 struct CrtDigitsArgs {
-    uint64_t* out;        // [nW][nLimbs][N]: the towers of this source limb
-    const uint64_t* src;  // [N]: the source limb
+    uint64_t* out;        // [towers][batch][nLimbs][N]
+    const uint64_t* src;  // [batch][nLimbs][N]
     const uint64_t* q;    // [ctxLimbs]
-    uint32_t logN, nLimbs, nW, baseBits, srcPos, srcCtxLimb;
+    uint32_t logN, nLimbs, batch, baseBits, maxW;
+    uint16_t first[kMaxLimbs + 1];  // first tower of source limb i (first[nLimbs] = towers); windows of limb i = first[i + 1] - first[i]
     LimbSel sel;
 };
 FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) crt_digits_kernel(const CrtDigitsArgs g) {
-    const uint32_t t          = FHE_TID;
-    const uint64_t base       = (uint64_t)FHE_BID << kTileLog;
-    const uint64_t totalWords = ((uint64_t)g.nW * g.nLimbs) << g.logN;
-    const uint32_t mask       = (1u << g.logN) - 1u;
-    const uint64_t qs = g.q[g.srcCtxLimb], halfQ = qs >> 1;
+    const uint32_t t           = FHE_TID;
+    const uint32_t N           = 1u << g.logN;
+    const uint32_t tilesPerRow = N >> kTileLog ? (N >> kTileLog) : 1u;
+    uint32_t id       = FHE_BID;
+    const uint32_t tr = id % tilesPerRow;
+    id /= tilesPerRow;
+    const uint32_t b = id % g.batch;
+    id /= g.batch;
+    const uint32_t w = id % g.maxW, i = id / g.maxW;
+    if (i >= g.nLimbs || w >= (uint32_t)g.first[i + 1] - g.first[i])
+        return;
+    const uint64_t qs = g.q[g.sel.idx[i]], halfQ = qs >> 1;
     const uint64_t dmask = g.baseBits ? (((uint64_t)1 << g.baseBits) - 1u) : ~(uint64_t)0;
-#pragma unroll 4
-    for (int m = 0; m < 16; ++m) {
-        const uint64_t off = base + (uint64_t)m * kThreads + t;
-        if (off >= totalWords)
-            continue;
-        const uint32_t row = (uint32_t)(off >> g.logN);
-        const uint32_t w = row / g.nLimbs, k = row % g.nLimbs;
-        uint64_t v = (g.src[(uint32_t)off & mask] >> (w * g.baseBits)) & dmask;  // (w * baseBits < 64: checked by the host)
-        if (k != g.srcPos)
-            v = switch_modulus_word(v, qs, halfQ, g.q[g.sel.idx[k]]);
-        g.out[off] = v;
+    const uint32_t sh    = w * g.baseBits;  // (< 64: checked by the host)
+    const uint32_t rEnd  = ((tr + 1u) << kTileLog) < N ? ((tr + 1u) << kTileLog) : N;
+    const uint64_t* src  = g.src + (((uint64_t)b * g.nLimbs + i) << g.logN);
+    uint64_t* out        = g.out + ((((uint64_t)(g.first[i] + w) * g.batch + b) * g.nLimbs) << g.logN);
+    for (uint32_t r0 = (tr << kTileLog) + t; r0 < rEnd; r0 += 4u * kThreads) {
+        uint64_t v[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t r = r0 + (uint32_t)m * kThreads;
+            v[m]             = r < rEnd ? (src[r] >> sh) & dmask : 0;
+        }
+        for (uint32_t k = 0; k < g.nLimbs; ++k) {
+            const uint64_t qn = g.q[g.sel.idx[k]];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const uint32_t r = r0 + (uint32_t)m * kThreads;
+                if (r < rEnd)
+                    out[((uint64_t)k << g.logN) + r] = k == i ? v[m] : switch_modulus_word(v[m], qs, halfQ, qn);
+            }
+        }
     }
 }
 

@@ -1489,7 +1489,8 @@ extern "C" fhe_status fhe_switch_modulus(fhe_ctx* c, uint64_t* out, const uint32
 }
 
 // DCRTPolyImpl::CRTDecompose(baseBits) (dcrtpoly-impl.h:230-285): x [nLimbs][N] COEFFICIENT -> out [towers][nLimbs][N] EVALUATION, towers in the
-// reference's order (limb 0's digits, least significant first, then limb 1's ...).  One launch per source limb, ONE transform over all towers.
+// reference's order (limb 0's digits, least significant first, then limb 1's ...).  ONE launch cuts every source limb (crt_digits_kernel), ONE
+// transform covers all towers.
 static uint32_t crt_windows(const fhe_ctx* c, uint32_t limb, uint32_t baseBits) {
     if (baseBits == 0)
         return 1;
@@ -1511,25 +1512,37 @@ extern "C" uint32_t fhe_crt_decompose_towers(const fhe_ctx* c, const uint32_t* l
     }
     return towers;
 }
+// every window of every limb of `batch` COEFFICIENT towers src [batch][nl][N] -> dst [towers][batch][nl][N], still COEFFICIENT (digit-major:
+// crt_digits_kernel); the table of first towers travels in the kernel argument
+static fhe_status crt_digits_run(fhe_ctx* c, const uint64_t* src, const uint32_t* li, uint32_t nl, uint32_t baseBits, uint32_t batch,
+                                 uint64_t* dst, void* st, const char* who) {
+    CrtDigitsArgs g;
+    if (fhe_status s = make_sel(c, li, nl, &g.sel, who))
+        return s;
+    uint32_t t0 = 0, maxW = 0;
+    for (uint32_t i = 0; i <= (uint32_t)kMaxLimbs; ++i) {
+        g.first[i] = (uint16_t)t0;  // (at most 256 limbs x 60 windows)
+        if (i < nl) {
+            const uint32_t nW = crt_windows(c, li ? li[i] : i, baseBits);
+            maxW = std::max(maxW, nW), t0 += nW;
+        }
+    }
+    const uint32_t tilesPerRow = c->N >= (uint32_t)kTile ? (c->N >> kTileLog) : 1u;
+    const uint64_t grid        = (uint64_t)tilesPerRow * batch * maxW * nl;
+    ARG_CHECK(grid < ((uint64_t)1 << 31), std::string(who) + ": batch too large for one launch");
+    g.out = dst, g.src = src, g.q = c->d_q, g.logN = c->logN, g.nLimbs = nl, g.batch = batch, g.baseBits = baseBits, g.maxW = maxW;
+    FHE_LAUNCH(crt_digits_kernel, grid, st, g);
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
 extern "C" fhe_status fhe_crt_decompose(fhe_ctx* c, const uint64_t* x, const uint32_t* li, uint32_t nl, uint32_t baseBits, uint64_t* out,
                                         void* st) {
     ARG_CHECK(c && x && out, "fhe_crt_decompose: null argument");
     const uint32_t towers = fhe_crt_decompose_towers(c, li, nl, baseBits);
     ARG_CHECK(towers >= 1, "fhe_crt_decompose: limb selection or digit size outside the device path (baseBits <= 31, every window inside the word)");
-    CrtDigitsArgs g;
-    if (fhe_status s = make_sel(c, li, nl, &g.sel, "fhe_crt_decompose"))
-        return s;
     RT_CHECK(rt::set_device(c->device));
-    g.q = c->d_q, g.logN = c->logN, g.nLimbs = nl, g.baseBits = baseBits;
-    uint32_t t0 = 0;
-    for (uint32_t i = 0; i < nl; ++i) {
-        const uint32_t l = li ? li[i] : i;
-        g.nW = crt_windows(c, l, baseBits), g.srcPos = i, g.srcCtxLimb = l;
-        g.src = x + ((size_t)i << c->logN), g.out = out + (((size_t)t0 * nl) << c->logN);
-        FHE_LAUNCH(crt_digits_kernel, tiles_for(c, (uint64_t)g.nW * nl), st, g);
-        LAUNCH_CHECK();
-        t0 += g.nW;
-    }
+    if (fhe_status s = crt_digits_run(c, x, li, nl, baseBits, 1, out, st, "fhe_crt_decompose"))
+        return s;
     return fhe_ntt_fwd(c, out, li, nl, towers, st);
 }
 
@@ -4227,6 +4240,170 @@ extern "C" fhe_status fhe_bfv_eval_mult_hps(fhe_hps* h, const uint64_t* a0, cons
                 return s;
     }
     return FHE_OK;
+}
+
+// ---- BV key switching (keyswitch-bv.cpp) --------------------------------------------------------------------------------------------
+// KeySwitchBV::KeySwitchCore (:245-259) = EvalFastKeySwitchCore(EvalKeySwitchPrecomputeCore(a), ek): digits = a.CRTDecompose(r) (:254), then
+// for both key vectors the sum over the digits of digit * key tower, the key towers cut to the level's limbs (:261-278).  No auxiliary
+// basis, no ModDown: the same calls serve BFV, BGV and CKKS.  The windows of a limb depend on its modulus only, so the digits of level sizeQl
+// meet the FIRST D_l towers of a key generated over sizeQ limbs (KeySwitchGenInternal, :49-103), row i of a key tower is limb i.
+struct fhe_bv_key {
+    fhe_ctx* ctx;
+    uint32_t sizeQ, baseBits, D0;
+    uint64_t *d_b = nullptr, *d_a = nullptr;  // [D0][sizeQ][N] EVALUATION
+    bool owned = true;
+};
+static fhe_status bv_key_new(fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, const char* who, fhe_bv_key** out) {
+    ARG_CHECK(sizeQ >= 1 && sizeQ <= c->L, std::string(who) + ": sizeQ must be in [1, limbs of the context]");
+    const uint32_t D0 = fhe_crt_decompose_towers(c, nullptr, sizeQ, baseBits);
+    if (D0 == 0)
+        return fail(FHE_ERR_UNSUPPORTED, std::string(who) + ": digit size outside the device path (baseBits <= 31, every window inside the word)");
+    fhe_bv_key* k = new fhe_bv_key;
+    k->ctx = c, k->sizeQ = sizeQ, k->baseBits = baseBits, k->D0 = D0;
+    *out = k;
+    return FHE_OK;
+}
+extern "C" fhe_status fhe_bv_key_upload(fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, const uint64_t* keyB, const uint64_t* keyA,
+                                        fhe_bv_key** out) {
+    ARG_CHECK(c && keyB && keyA && out, "fhe_bv_key_upload: null argument");
+    fhe_bv_key* k = nullptr;
+    if (fhe_status s = bv_key_new(c, sizeQ, baseBits, "fhe_bv_key_upload", &k))
+        return s;
+    const size_t bytes = (((size_t)k->D0 * sizeQ) << c->logN) * 8;
+    if (rt::set_device(c->device) || rt::dmalloc((void**)&k->d_b, bytes) || rt::dmalloc((void**)&k->d_a, bytes)) {
+        fhe_bv_key_destroy(k);
+        return fail(FHE_ERR_ALLOC, "fhe_bv_key_upload: device allocation failed");
+    }
+    const char* e = rt::h2d(k->d_b, keyB, bytes, nullptr);
+    if (!e)
+        e = rt::h2d(k->d_a, keyA, bytes, nullptr);
+    if (!e)
+        e = rt::sync(nullptr);
+    if (e) {
+        fhe_bv_key_destroy(k);
+        return fail(FHE_ERR_DEVICE, std::string("fhe_bv_key_upload: ") + e);
+    }
+    *out = k;
+    return FHE_OK;
+}
+extern "C" fhe_status fhe_bv_key_wrap(fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint64_t* devB, uint64_t* devA, fhe_bv_key** out) {
+    ARG_CHECK(c && devB && devA && out, "fhe_bv_key_wrap: null argument");
+    fhe_bv_key* k = nullptr;
+    if (fhe_status s = bv_key_new(c, sizeQ, baseBits, "fhe_bv_key_wrap", &k))
+        return s;
+    k->d_b = devB, k->d_a = devA, k->owned = false;
+    *out = k;
+    return FHE_OK;
+}
+extern "C" void fhe_bv_key_destroy(fhe_bv_key* k) {
+    if (!k)
+        return;
+    if (k->owned && k->d_b)
+        rt::dfree(k->d_b);
+    if (k->owned && k->d_a)
+        rt::dfree(k->d_a);
+    delete k;
+}
+// workspace (words): digits [D_l][batch][sizeQl][N] | coef [batch][sizeQl][N] (the coefficient copy of an EVALUATION input, dcrtpoly-impl.h:231-233)
+extern "C" size_t fhe_bv_workspace_bytes(const fhe_ctx* c, uint32_t sizeQl, uint32_t baseBits, uint32_t batch) {
+    const uint32_t D = fhe_crt_decompose_towers(c, nullptr, sizeQl, baseBits);
+    if (D == 0 || sizeQl > c->L || batch < 1)
+        return 0;
+    return ((((size_t)D + 1) * batch * sizeQl) << c->logN) * 8;
+}
+extern "C" fhe_status fhe_bv_precompute(fhe_ctx* c, const uint64_t* cin, int evalFormat, uint32_t sizeQl, uint32_t baseBits, uint32_t batch,
+                                        void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(c && cin && ws, "fhe_bv_precompute: null argument");
+    ARG_CHECK(sizeQl >= 1 && sizeQl <= c->L && batch >= 1, "fhe_bv_precompute: sizeQl must be in [1, sizeQ], batch >= 1");
+    const uint32_t D = fhe_crt_decompose_towers(c, nullptr, sizeQl, baseBits);
+    if (D == 0)
+        return fail(FHE_ERR_UNSUPPORTED, "fhe_bv_precompute: digit size outside the device path (baseBits <= 31, every window inside the word)");
+    ARG_CHECK((uint64_t)D * batch < ((uint64_t)1 << 31), "fhe_bv_precompute: batch too large");
+    ARG_CHECK(wsBytes >= fhe_bv_workspace_bytes(c, sizeQl, baseBits, batch), "fhe_bv_precompute: workspace too small");
+    RT_CHECK(rt::set_device(c->device));
+    uint64_t* dig = (uint64_t*)ws;
+    const uint64_t* coef = cin;
+    if (evalFormat) {
+        uint64_t* cf = dig + (((size_t)D * batch * sizeQl) << c->logN);
+        if (fhe_status s = fhe_ntt_inv_oop(c, cin, cf, nullptr, sizeQl, batch, st))
+            return s;
+        coef = cf;
+    }
+    if (fhe_status s = crt_digits_run(c, coef, nullptr, sizeQl, baseBits, batch, dig, st, "fhe_bv_precompute"))
+        return s;
+    // canonical output: the digits a hoisting caller finds in ws are the words of DCRTPolyImpl::CRTDecompose
+    return fhe_ntt_fwd(c, dig, nullptr, sizeQl, D * batch, st);
+}
+static fhe_status bv_fast_check(const fhe_bv_key* k, uint32_t sizeQl, uint32_t batch, const void* out0, const void* out1, const void* ws,
+                                size_t wsBytes, const char* who) {
+    ARG_CHECK(k && out0 && out1 && ws, std::string(who) + ": null argument");
+    ARG_CHECK(sizeQl >= 1 && sizeQl <= k->sizeQ && batch >= 1, std::string(who) + ": sizeQl must be in [1, sizeQ], batch >= 1");
+    ARG_CHECK(wsBytes >= fhe_bv_workspace_bytes(k->ctx, sizeQl, k->baseBits, batch), std::string(who) + ": workspace too small for the digits of this key (sizeQl, batch, or digits cut for another baseBits)");
+    return FHE_OK;
+}
+static fhe_status bv_fast_run(const fhe_bv_key* k, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1, int accumulate,
+                              const uint64_t* dig, void* st) {
+    fhe_ctx* c = k->ctx;
+    RT_CHECK(rt::set_device(c->device));
+    BvInnerArgs g;
+    g.digits = dig, g.keyB = k->d_b, g.keyA = k->d_a, g.out0 = out0, g.out1 = out1, g.lc = c->d_lc, g.mu128 = c->d_mu128;
+    g.logN = c->logN, g.batch = batch, g.sizeQl = sizeQl, g.sizeQ = k->sizeQ, g.acc = accumulate != 0;
+    g.D = fhe_crt_decompose_towers(c, nullptr, sizeQl, k->baseBits);  // the key's first D_l towers
+    const uint32_t tilesPerRow = c->N >= (uint32_t)kTile ? (c->N >> kTileLog) : 1u;
+    const uint64_t grid        = (((uint64_t)tilesPerRow * sizeQl + 7) / 8) * 8 * batch;
+    ARG_CHECK(grid < ((uint64_t)1 << 31), "fhe_bv_fast_keyswitch: batch too large for one launch");
+    // two adjacent coefficients per lane need 16-byte aligned towers (any device allocation is) and N >= 2
+    const uintptr_t bits = (uintptr_t)dig | (uintptr_t)k->d_b | (uintptr_t)k->d_a | (uintptr_t)out0 | (uintptr_t)out1;
+    if ((bits & 15u) == 0 && c->N >= 2)
+        FHE_LAUNCH((bv_inner_product_kernel<2>), grid, st, g);
+    else
+        FHE_LAUNCH((bv_inner_product_kernel<1>), grid, st, g);
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+extern "C" fhe_status fhe_bv_fast_keyswitch(const fhe_bv_key* k, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1,
+                                            int accumulate, const void* ws, size_t wsBytes, void* st) {
+    if (fhe_status s = bv_fast_check(k, sizeQl, batch, out0, out1, ws, wsBytes, "fhe_bv_fast_keyswitch"))
+        return s;
+    return bv_fast_run(k, sizeQl, batch, out0, out1, accumulate, (const uint64_t*)ws, st);
+}
+extern "C" fhe_status fhe_keyswitch_bv(const fhe_bv_key* k, const uint64_t* cin, uint32_t sizeQl, uint32_t batch, uint64_t* out0,
+                                       uint64_t* out1, int accumulate, void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(cin, "fhe_keyswitch_bv: null argument");
+    if (fhe_status s = bv_fast_check(k, sizeQl, batch, out0, out1, ws, wsBytes, "fhe_keyswitch_bv"))
+        return s;
+    if (fhe_status s = fhe_bv_precompute(k->ctx, cin, 1, sizeQl, k->baseBits, batch, ws, wsBytes, st))
+        return s;
+    return bv_fast_run(k, sizeQl, batch, out0, out1, accumulate, (const uint64_t*)ws, st);
+}
+// LeveledSHEBase::EvalMult(ct, ct, key) (base-leveledshe.cpp:201-214) on BFV ciphertexts of the HPS family with a BV key: EvalMultNoRelin with
+// d0, d1 written to c0, c1, SetFormat(EVALUATION) (fhe_bfv_eval_mult_hps, outEval), KeySwitchCore on d2 at numQ limbs, c0 += ks0, c1 += ks1.
+// workspace (bytes): d2 [batch][numQ][N] | max(the product's, the key switch's)
+extern "C" size_t fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes(const fhe_hps* h, uint32_t sizeQl, uint32_t baseBits, uint32_t batch) {
+    const size_t mul = fhe_bfv_eval_mult_hps_workspace_bytes(h, sizeQl, batch);
+    if (!mul)
+        return 0;
+    const size_t ks = fhe_bv_workspace_bytes(h->ctx, h->numQ, baseBits, batch);
+    if (!ks)
+        return 0;
+    return ((((size_t)batch * h->numQ) << h->ctx->logN) * 8) + std::max(mul, ks);
+}
+extern "C" fhe_status fhe_bfv_eval_mult_relin_hps_bv(fhe_hps* h, const fhe_bv_key* k, const uint64_t* a0, const uint64_t* a1,
+                                                     const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1, uint32_t sizeQl,
+                                                     uint32_t batch, void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(h && k && a0 && a1 && b0 && b1 && c0 && c1 && ws && batch >= 1, "fhe_bfv_eval_mult_relin_hps_bv: bad argument");
+    ARG_CHECK(k->ctx == h->ctx && k->sizeQ == h->numQ, "fhe_bfv_eval_mult_relin_hps_bv: the key was built for another context or another Q");
+    for (uint32_t i = 0; i < h->numQ; ++i)
+        ARG_CHECK(h->qIdx[i] == i, "fhe_bfv_eval_mult_relin_hps_bv: Q must be the context's leading limbs");
+    ARG_CHECK(hps_level(h, sizeQl), "fhe_bfv_eval_mult_relin_hps_bv: sizeQl must be numQ (1 ... numQ for HPSPOVERQLEVELED)");
+    const size_t need = fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes(h, sizeQl, k->baseBits, batch);
+    ARG_CHECK(need && wsBytes >= need, "fhe_bfv_eval_mult_relin_hps_bv: workspace too small");
+    const size_t d2Bytes = (((size_t)batch * h->numQ) << h->ctx->logN) * 8;
+    uint64_t* d2 = (uint64_t*)ws;
+    void* rest   = (char*)ws + d2Bytes;
+    if (fhe_status s = fhe_bfv_eval_mult_hps(h, a0, a1, b0, b1, c0, c1, d2, sizeQl, 1, batch, rest, wsBytes - d2Bytes, st))
+        return s;
+    return fhe_keyswitch_bv(k, d2, h->numQ, batch, c0, c1, 1, rest, wsBytes - d2Bytes, st);
 }
 
 // whole-tower checksums (checksum_kernel): out[row] = {sum_i w_i, sum_i (2i + 1) w_i} mod 2^64 of every limb-row of x[rows][N]; out is DEVICE memory

@@ -39,7 +39,9 @@ def _np_u32(a):
 class Lib:
     """Loads libfhe_hip.so (or an explicitly given build, e.g. the test-only lane emulator)."""
 
-    def __init__(self, path=None):
+    def __init__(self, path=None, may_lack=()):
+        """may_lack: name prefixes of entry points that `path` — an older build kept as a baseline by a measuring tool — is known not to
+        have; those stay unbound, every other missing symbol is an error as always"""
         path = path or os.environ.get("FHE_HIP_LIB") or DEFAULT_SO
         if not os.path.exists(path):
             raise FheError(
@@ -49,7 +51,12 @@ class Lib:
         L = self.L = C.CDLL(path)
 
         def S(name, res, args):
-            f = getattr(L, name)
+            try:
+                f = getattr(L, name)
+            except AttributeError:
+                if name.startswith(tuple(may_lack)) and may_lack:
+                    return
+                raise
             f.restype, f.argtypes = res, args
 
         S("fhe_last_error", C.c_char_p, [])
@@ -179,6 +186,15 @@ class Lib:
         S("fhe_bfv_eval_mult_hps_workspace_bytes", C.c_size_t, [vp, u32, u32])
         S("fhe_bfv_eval_mult_hps", C.c_int, [vp] * 8 + [u32, C.c_int, u32, vp, C.c_size_t, vp])
         S("fhe_bfv_eval_mult_relin_behz", C.c_int, [vp] * 9 + [u32, vp, C.c_size_t, vp])
+        S("fhe_bv_key_upload", C.c_int, [vp, u32, u32, u64p, u64p, C.POINTER(vp)])
+        S("fhe_bv_key_wrap", C.c_int, [vp, u32, u32, vp, vp, C.POINTER(vp)])
+        S("fhe_bv_key_destroy", None, [vp])
+        S("fhe_bv_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_bv_precompute", C.c_int, [vp, vp, C.c_int, u32, u32, u32, vp, C.c_size_t, vp])
+        S("fhe_bv_fast_keyswitch", C.c_int, [vp, u32, u32, vp, vp, C.c_int, vp, C.c_size_t, vp])
+        S("fhe_keyswitch_bv", C.c_int, [vp, vp, u32, u32, vp, vp, C.c_int, vp, C.c_size_t, vp])
+        S("fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_bfv_eval_mult_relin_hps_bv", C.c_int, [vp] * 8 + [u32, u32, vp, C.c_size_t, vp])
         S("fhe_param_first_prime", u64, [u32, u64])
         S("fhe_param_last_prime", u64, [u32, u64])
         S("fhe_param_next_prime", u64, [u64, u64])
@@ -760,6 +776,71 @@ class KeySwitchPlan:
         return out
 
 
+class BvKey:
+    """A BV evaluation key (KeySwitchBV, keyswitch-bv.cpp) over the context's leading sizeQ limbs with digit size base_bits: keyB / keyA
+    are the key's b / a vectors, uint64 [D_0][sizeQ][N] in EVALUATION format, D_0 = digits(sizeQ).  The digits of the last Precompute stay
+    in the key object's workspace (hoisting: one Precompute, FastKeySwitch with any key of the same base_bits via `ws_of`)."""
+
+    def __init__(self, ctx, sizeQ, base_bits, keyB, keyA):
+        self.ctx, self.sizeQ, self.base_bits = ctx, sizeQ, base_bits
+        keyB = np.ascontiguousarray(keyB, dtype=np.uint64)
+        keyA = np.ascontiguousarray(keyA, dtype=np.uint64)
+        d0 = ctx.lib.L.fhe_crt_decompose_towers(ctx.h, None, sizeQ, base_bits)
+        if d0 and (keyB.size != d0 * sizeQ * ctx.N or keyA.size != keyB.size):
+            raise ValueError(f"a BV key of digit size {base_bits} over {sizeQ} limbs is uint64[{d0}][{sizeQ}][{ctx.N}] per vector")
+        h = vp()
+        ctx.lib.check(ctx.lib.L.fhe_bv_key_upload(ctx.h, sizeQ, base_bits, keyB.ctypes.data_as(u64p), keyA.ctypes.data_as(u64p),
+                                                  C.byref(h)))
+        self.h = h
+        self._ws = None
+        self._ws_bytes = 0
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.L.fhe_bv_key_destroy(self.h)
+            self.h = None
+        if self._ws is not None and self.ctx.h:
+            self.ctx.free(self._ws)
+        self._ws = None
+
+    def digits(self, sizeQl):
+        """D_l: towers of CRTDecompose(base_bits) at level sizeQl (the first D_l towers of the key)"""
+        return self.ctx.lib.L.fhe_crt_decompose_towers(self.ctx.h, None, sizeQl, self.base_bits)
+
+    def workspace(self, sizeQl, batch):
+        need = self.ctx.lib.L.fhe_bv_workspace_bytes(self.ctx.h, sizeQl, self.base_bits, batch)
+        if need > self._ws_bytes:
+            if self._ws is not None:
+                self.ctx.free(self._ws)
+            self._ws = self.ctx.malloc(need)
+            self._ws_bytes = need
+        return self._ws, self._ws_bytes
+
+    def Precompute(self, c, stream=None):  # keyswitch-bv.cpp:251-259: the digits [D_l][batch][sizeQl][N] at the start of the workspace
+        ws, wsb = self.workspace(c.n_limbs, c.batch)
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bv_precompute(self.ctx.h, c.ptr, 1 if c.fmt == EVALUATION else 0, c.n_limbs, self.base_bits,
+                                                            c.batch, ws, wsb, stream))
+        return ws, wsb
+
+    def FastKeySwitch(self, sizeQl, batch, acc0=None, acc1=None, ws_of=None, stream=None):  # keyswitch-bv.cpp:261-278
+        """on the digits of the last Precompute of `ws_of` (default: this key); acc0 / acc1 given: acc += result, in place"""
+        ws, wsb = (ws_of or self).workspace(sizeQl, batch)
+        acc = acc0 is not None
+        o0 = acc0 if acc else self.ctx.empty(batch, sizeQl)
+        o1 = acc1 if acc else self.ctx.empty(batch, sizeQl)
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bv_fast_keyswitch(self.h, sizeQl, batch, o0.ptr, o1.ptr, 1 if acc else 0, ws, wsb, stream))
+        return o0, o1
+
+    def KeySwitchCore(self, c, acc0=None, acc1=None, stream=None):  # keyswitch-bv.cpp:245-249 (+ base-leveledshe.cpp:207-211 with acc)
+        ws, wsb = self.workspace(c.n_limbs, c.batch)
+        acc = acc0 is not None
+        o0 = acc0 if acc else c.like()
+        o1 = acc1 if acc else c.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_keyswitch_bv(self.h, c.ptr, c.n_limbs, c.batch, o0.ptr, o1.ptr, 1 if acc else 0, ws, wsb,
+                                                           stream))
+        return o0, o1
+
+
 def rescale(ctx, x, stream=None):
     """DCRTPoly::DropLastElementAndScale on a Tower over context limbs [0, sizeQl) (dcrtpoly-impl.h:693-712)."""
     sizeQl = x.n_limbs
@@ -1048,3 +1129,20 @@ class Hps:
         finally:
             self.ctx.free(ws)
         return d
+
+    def EvalMult(self, bv_key, a0, a1, b0, b1, size_ql=None, stream=None):
+        """LeveledSHEBase::EvalMult(ct, ct, key) with a BV key (base-leveledshe.cpp:201-214): the product above, then KeySwitchCore on its
+        third element at numQ limbs added to the first two; returns (c0, c1), EVALUATION"""
+        B = a0.batch
+        size_ql = self.numQ if size_ql is None else size_ql
+        c0, c1 = (self.ctx.empty(B, self.numQ, self.q_idx, EVALUATION) for _ in range(2))
+        L = self.ctx.lib.L
+        wsb = max(L.fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes(self.h, size_ql, bv_key.base_bits, B), 8)
+        ws = self.ctx.malloc(wsb)
+        try:
+            self.ctx.lib.check(L.fhe_bfv_eval_mult_relin_hps_bv(self.h, bv_key.h, a0.ptr, a1.ptr, b0.ptr, b1.ptr, c0.ptr, c1.ptr, size_ql, B,
+                                                                ws, wsb, stream))
+            self.ctx.sync(stream)
+        finally:
+            self.ctx.free(ws)
+        return c0, c1
