@@ -557,7 +557,8 @@ fhe_status fhe_bfv_eval_mult_hps(fhe_hps* plan, const uint64_t* a0, const uint64
  *   fhe_bfv_eval_mult_relin_hps_bv = LeveledSHEBase::EvalMult(ct, ct, key) (base-leveledshe.cpp:201-214) on BFV ciphertexts of the HPS family
  *                            with a BV key (HPSPOVERQLEVELED + BV is the reference's default BFV configuration): fhe_bfv_eval_mult_hps(outEval = 1)
  *                            with d0, d1 written to c0, c1 and d2 into ws, then fhe_keyswitch_bv(accumulate = 1) at numQ limbs.  sizeQl as for
- *                            fhe_bfv_eval_mult_hps; the plan's Q must be the context's leading limbs and the key built over them. */
+ *                            fhe_bfv_eval_mult_hps; the plan's Q must be the context's leading limbs and the key built over them.  It is the
+ *                            sizeQlRelin == numQ case of fhe_bfv_eval_mult_relin_hps_bv_leveled below. */
 typedef struct fhe_bv_key fhe_bv_key;
 /* keyB, keyA: HOST uint64_t[D_0][sizeQ][N] each, EVALUATION */
 fhe_status fhe_bv_key_upload(fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, const uint64_t* keyB, const uint64_t* keyA, fhe_bv_key** out);
@@ -576,6 +577,64 @@ size_t     fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes(const fhe_hps* plan, u
 fhe_status fhe_bfv_eval_mult_relin_hps_bv(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
                                           const uint64_t* b1, uint64_t* c0, uint64_t* c1, uint32_t sizeQl, uint32_t batch,
                                           void* ws, size_t wsBytes, void* stream);
+
+/* ---- rotations and leveled relinearisation on a BV key ------------------------------------------------------------
+ * The rules of "BV key switching" carry over: after key upload a call builds nothing lazily, allocates nothing and does not synchronise (it can
+ * be captured); an error enqueues nothing: a null argument, an even k ("Automorphism index not odd", as fhe_eval_fast_rotation), sizeQl out of
+ * range for the technique, too small a workspace, a key of another context or another Q, FHE_ERR_UNSUPPORTED for a digit size outside the
+ * device path.  Outputs must not alias inputs or ws unless stated otherwise.  k is the automorphism index (FindAutomorphismIndex is host
+ * arithmetic: fhe_param_find_automorphism_index_2n_complex or the caller's own).
+ * The inner product, the basis expansion, the additions and the automorphism of both elements are ONE kernel (the output-stage instance of bv_inner_product_kernel):
+ * the two key-switch results never travel through device memory on their own.
+ *
+ * Any scheme (LeveledSHEBase; the tower has sizeQl limbs, the context's leading ones):
+ *   fhe_bv_eval_fast_rotation  = LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:432-463) on the digits fhe_bv_precompute(c1) left in ws
+ *                                (hoisting: one precompute, many keys): out0 = Auto_k(c0 + ks0), out1 = Auto_k(ks1).  ws is only read.
+ *                                Digits and key must have the same baseBits and the CALLER pairs them, exactly as for fhe_bv_fast_keyswitch:
+ *                                a key of a smaller digit size is refused by the workspace check, one of a larger digit size is NOT detected.
+ *   fhe_bv_eval_automorphism   = LeveledSHEBase::EvalAutomorphism (base-leveledshe.cpp:381-422): fhe_bv_precompute(c1, EVALUATION) + the above.
+ *
+ * BFV, HPS family, with the fhe_hps plan.  The plan's Q must be the context's leading limbs and the key's sizeQ == numQ (checked as
+ * fhe_bfv_eval_mult_relin_hps_bv checks them).  All towers are [batch][numQ][N].  sizeQl = l + 1 is the caller's numQ - levelsDropped for
+ * the KEY SWITCH (FindLevelsToDrop(..., keySwitch) is host-side noise estimation and stays in pke): 1 ... numQ for HPSPOVERQLEVELED, numQ
+ * only for HPS and HPSPOVERQ (the reference's condition, bfvrns-leveledshe.cpp:795, :859, :903, is false there: no scaling, no expansion).
+ * Below numQ the element to be switched is scaled from Q down to Q_l (ScaleAndRound with QlQHatInvModqDivqModq(l) / ...Frac(l)), the key
+ * switch runs at sizeQl limbs and both results return to Q (ExpandCRTBasisQlHat with QlHatModq(l)) before anything is added.
+ * At sizeQl == numQ under HPSPOVERQLEVELED the reference still calls both members with the level-(numQ-1) tables; they are the identity
+ * there (Q_l = Q: the integer table is the CRT reconstruction, every fraction is 0, QlHatModq is all ones) and are SKIPPED.  The words are
+ * the reference's: tests/test_bv_rot_golden.py compares with cc->EvalRotate / EvalFastRotation / EvalMult on fresh ciphertexts.
+ *   fhe_bfv_bv_workspace_bytes           covers every call below but the last (0: sizeQl or baseBits outside the device path)
+ *   fhe_bfv_fast_rotation_precompute_bv  = LeveledSHEBFVRNS::EvalFastRotationPrecompute (bfvrns-leveledshe.cpp:782-813): c1 EVALUATION ->
+ *                                COEFFICIENT -> ScaleAndRound Q -> Q_l -> digits at sizeQl limbs, EVALUATION, digit-major at the start of ws
+ *                                (the layout of fhe_bv_precompute)
+ *   fhe_bfv_eval_fast_rotation_bv        = LeveledSHEBFVRNS::EvalFastRotation (:815-882): inner product at sizeQl, ExpandCRTBasisQlHat to numQ,
+ *                                += c0, the automorphism of both.  ws is only read; the caveat about pairing digits and key by baseBits
+ *                                applies as above.
+ *   fhe_bfv_eval_automorphism_bv         = LeveledSHEBFVRNS::EvalAutomorphism (:767-780): RelinearizeCore on two elements, both through the
+ *                                automorphism = the two calls above
+ *   fhe_bfv_relinearize_bv               = LeveledSHEBFVRNS::RelinearizeCore on three elements (:888-938): c_e = d_e + Expand(ks_e(d2)), EVALUATION.
+ *                                inEval == 0: d0, d1, d2 are COEFFICIENT as EvalMultNoRelin leaves them (d2 goes straight into ScaleAndRound,
+ *                                d0 / d1 are transformed once); otherwise EVALUATION.  c_e may be d_e (in place).
+ *   fhe_bfv_eval_mult_relin_hps_bv_leveled = LeveledSHEBFVRNS::EvalMult(ct, ct, key) (:735-741): fhe_bfv_eval_mult_hps(outEval = 0) at sizeQlMult,
+ *                                then fhe_bfv_relinearize_bv(inEval = 0) at sizeQlRelin.  Its own _workspace_bytes. */
+fhe_status fhe_bv_eval_fast_rotation(const fhe_bv_key* key, const uint64_t* c0, uint32_t k, uint32_t sizeQl, uint32_t batch, uint64_t* out0,
+                                     uint64_t* out1, const void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bv_eval_automorphism(const fhe_bv_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k, uint32_t sizeQl, uint32_t batch,
+                                    uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes, void* stream);
+size_t     fhe_bfv_bv_workspace_bytes(const fhe_hps* plan, uint32_t sizeQl, uint32_t baseBits, uint32_t batch);
+fhe_status fhe_bfv_fast_rotation_precompute_bv(fhe_hps* plan, const uint64_t* c1, uint32_t sizeQl, uint32_t baseBits, uint32_t batch, void* ws,
+                                               size_t wsBytes, void* stream);
+fhe_status fhe_bfv_eval_fast_rotation_bv(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* c0, uint32_t k, uint32_t sizeQl, uint32_t batch,
+                                         uint64_t* out0, uint64_t* out1, const void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bfv_eval_automorphism_bv(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k,
+                                        uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bfv_relinearize_bv(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* d0, const uint64_t* d1, const uint64_t* d2, int inEval,
+                                  uint32_t sizeQl, uint32_t batch, uint64_t* c0, uint64_t* c1, void* ws, size_t wsBytes, void* stream);
+size_t     fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes(const fhe_hps* plan, uint32_t sizeQlMult, uint32_t sizeQlRelin,
+                                                                  uint32_t baseBits, uint32_t batch);
+fhe_status fhe_bfv_eval_mult_relin_hps_bv_leveled(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* a0, const uint64_t* a1,
+                                                  const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1, uint32_t sizeQlMult,
+                                                  uint32_t sizeQlRelin, uint32_t batch, void* ws, size_t wsBytes, void* stream);
 
 /* ---- parity helper: whole-tower checksums ----------------------------------------------------------------
  * out[row] = { sum_i w_i, sum_i (2i + 1) * w_i } mod 2^64 over the row's N words, for every limb-row of x[rows][N] (rows = batch *

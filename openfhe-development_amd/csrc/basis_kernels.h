@@ -15,6 +15,8 @@
 // wave-uniform and come through the scalar cache.
 #ifndef FHE_BASIS_KERNELS_H
 #define FHE_BASIS_KERNELS_H
+#include <type_traits>
+
 #include "modarith.h"
 #include "launch.h"
 #include "ntt_kernels.h"
@@ -509,8 +511,35 @@ struct BvInnerArgs {
     const uint64_t* mu128;   // [ctxLimbs][2]
     uint32_t logN, batch, sizeQl, sizeQ, D, acc;
 };
-template <int CPL>
-FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bv_inner_product_kernel(const BvInnerArgs g) {
+// The output stage (OUT = true), an instance of the same kernel.
+// The tail of a rotation or a relinearisation on a BV key in the launch that forms the sums: LeveledSHEBase::EvalFastRotation
+// (base-leveledshe.cpp:456-460) and, for BFV in HPSPOVERQLEVELED, LeveledSHEBFVRNS::EvalFastRotation / RelinearizeCore
+// (bfvrns-leveledshe.cpp:864-877, 918-935): ExpandCRTBasisQlHat of both sums from the sizeQl limbs of Q_l to the outRows limbs of Q
+// (times QlHatModq(l)[i] below sizeQl, zero above), += the ciphertext's own elements, AutomorphismTransform of both.  Per output word
+//   i <  sizeQl : v_e = hat[i] * ks_e (+ add_e[b][i][r])          i >= sizeQl : v_e = add_e[b][i][r] (or 0)
+//   out_e[b][i][dst(r)] = v_e
+// where dst is the EVALUATION-format automorphism as a SCATTER: out[jr] = in[source_k(jr)] (automorph_kernel) is out[source_kInv(r)] =
+// in[r] with kInv = k^-1 mod 2N, which the host computes.  The 3 D input streams are read as in the plain kernel; only the two
+// output streams are permuted, and every output word is stored once.
+// Tile property: position p holds the coefficient index j = bitrev(p), and j' = ((2j + 1) k mod 2N) >> 1.  The low m bits of j' are a
+// function of the low m bits of j alone (2j' + 1 = (2j + 1) k mod 2^(m+1) needs nothing above bit m of 2j + 1), and the low m bits of j
+// are the HIGH m bits of p.  So the map sends every aligned block of 2^(logN - m) positions onto one aligned block: the 4096 words of a
+// workgroup's tile land in exactly one 4096-word tile of the same output row, 32 KiB that no other workgroup of the launch touches.
+// The words are stored straight from the registers (8-byte stores; the partial lines of one tile merge in L2 before they leave it).
+// k = 1 is the identity: 16-byte stores, and an addend may then be the output itself (each lane reads the words it writes).
+// Rows i >= sizeQl form no sums: their workgroups move the addend (or zero) through the permutation and leave.
+struct BvOutStage {
+    const uint64_t* add0;  // [batch][outRows][N] or null
+    const uint64_t* add1;
+    uint32_t outRows;      // >= sizeQl; out0 / out1 of BvInnerArgs are [batch][outRows][N] here
+    uint32_t kInv;         // k^-1 mod 2N
+    uint32_t useHat;       // 0: factor 1 (then outRows == sizeQl)
+    ConstVec hat;          // QlHatModq(l), by value like the other constant vectors
+};
+struct BvNoStage {};
+template <int CPL, bool OUT>
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads)
+    bv_inner_product_kernel(const BvInnerArgs g, const typename std::conditional<OUT, BvOutStage, BvNoStage>::type e) {
     const uint32_t t           = FHE_TID;
     const uint32_t N           = 1u << g.logN;
     const uint32_t tilesPerRow = N >> kTileLog ? (N >> kTileLog) : 1u;
@@ -519,7 +548,11 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bv_inner_product_kernel(const BvInne
     const uint32_t grp = (slot / g.batch) * 8u + xcd;
     const uint32_t tr = grp % tilesPerRow;
     const uint32_t i  = grp / tilesPerRow;
-    if (i >= g.sizeQl)
+    if constexpr (OUT) {
+        if (i >= e.outRows)
+            return;
+    }
+    else if (i >= g.sizeQl)
         return;
     const LimbConst lc  = g.lc[i];
     const uint64_t mulo = g.mu128[2 * i], muhi = g.mu128[2 * i + 1];
@@ -527,6 +560,16 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bv_inner_product_kernel(const BvInne
     const uint32_t rEnd = ((tr + 1u) << kTileLog) < N ? ((tr + 1u) << kTileLog) : N;
     const uint64_t dStride = ((uint64_t)g.batch * g.sizeQl) << g.logN, kStride = (uint64_t)g.sizeQ << g.logN;
     const uint64_t ooff0 = ((uint64_t)b * g.sizeQl + i) << g.logN, koff0 = (uint64_t)i << g.logN;
+    uint32_t D    = g.D;
+    uint64_t ooff = ooff0;  // the output row (ooff0: the digits' row)
+    TwPair hat    = {0, 0};
+    if constexpr (OUT) {
+        ooff = ((uint64_t)b * e.outRows + i) << g.logN;
+        if (i >= g.sizeQl)
+            D = 0;  // the rows above Q_l have no sums to form
+        else if (e.useHat)
+            hat = e.hat.c[i];
+    }
     for (uint32_t r = (tr << kTileLog) + CPL * t; r < rEnd; r += CPL * kThreads) {
         // (wave-uniform row pointers walked by stride + one lane offset: the addresses stay in scalar registers)
         const uint64_t* dp = g.digits + ooff0;
@@ -537,7 +580,7 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bv_inner_product_kernel(const BvInne
         for (int u = 0; u < CPL; ++u)
             v0[u] = v1[u] = 0;
         uint32_t d0 = 0;
-        for (; d0 + 8u <= g.D; d0 += 8u) {  // full chunks, in two halves: the 12 loads of a half are issued back to back
+        for (; d0 + 8u <= D; d0 += 8u) {  // full chunks, in two halves: the 12 loads of a half are issued back to back
             sum8 s0[CPL], s1[CPL];
 #pragma unroll
             for (int u = 0; u < CPL; ++u) {
@@ -570,14 +613,14 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bv_inner_product_kernel(const BvInne
             }
             dp += 8 * dStride, kb += 8 * kStride, ka += 8 * kStride;
         }
-        if (d0 < g.D) {  // the last, partial chunk
+        if (d0 < D) {  // the last, partial chunk
             sum8 s0[CPL], s1[CPL];
 #pragma unroll
             for (int u = 0; u < CPL; ++u) {
                 sum8_clear(s0[u]);
                 sum8_clear(s1[u]);
             }
-            for (; d0 < g.D; ++d0) {
+            for (; d0 < D; ++d0) {
                 uint64_t x[CPL], yb[CPL], ya[CPL];
                 ld_cpl<CPL>(dp + r, x);
                 ld_cpl<CPL>(kb + r, yb);
@@ -596,18 +639,55 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bv_inner_product_kernel(const BvInne
                 v1[u] = add_mod(v1[u], sum8_reduce(s1[u], q, lc.msb, mulo, muhi), q);
             }
         }
-        if (g.acc) {
-            uint64_t p0[CPL], p1[CPL];
-            ld_cpl<CPL>(g.out0 + ooff0 + r, p0);
-            ld_cpl<CPL>(g.out1 + ooff0 + r, p1);
+        if constexpr (OUT) {
+            if (e.useHat && i < g.sizeQl) {
 #pragma unroll
-            for (int u = 0; u < CPL; ++u) {
-                v0[u] = add_mod(v0[u], p0[u], q);
-                v1[u] = add_mod(v1[u], p1[u], q);
+                for (int u = 0; u < CPL; ++u) {
+                    v0[u] = mul_shoup(v0[u], hat.w, hat.wp, q);
+                    v1[u] = mul_shoup(v1[u], hat.w, hat.wp, q);
+                }
+            }
+            if (e.add0) {
+                uint64_t p[CPL];
+                ld_cpl<CPL>(e.add0 + ooff + r, p);
+#pragma unroll
+                for (int u = 0; u < CPL; ++u)
+                    v0[u] = add_mod(v0[u], p[u], q);
+            }
+            if (e.add1) {
+                uint64_t p[CPL];
+                ld_cpl<CPL>(e.add1 + ooff + r, p);
+#pragma unroll
+                for (int u = 0; u < CPL; ++u)
+                    v1[u] = add_mod(v1[u], p[u], q);
+            }
+            if (e.kInv == 1u) {
+                st_cpl<CPL>(g.out0 + ooff + r, v0);
+                st_cpl<CPL>(g.out1 + ooff + r, v1);
+            }
+            else {
+#pragma unroll
+                for (int u = 0; u < CPL; ++u) {
+                    const uint32_t dst = automorph_source(bitrev32(r + u, g.logN), e.kInv, g.logN);
+                    g.out0[ooff + dst] = v0[u];
+                    g.out1[ooff + dst] = v1[u];
+                }
             }
         }
-        st_cpl<CPL>(g.out0 + ooff0 + r, v0);
-        st_cpl<CPL>(g.out1 + ooff0 + r, v1);
+        else {
+            if (g.acc) {
+                uint64_t p0[CPL], p1[CPL];
+                ld_cpl<CPL>(g.out0 + ooff0 + r, p0);
+                ld_cpl<CPL>(g.out1 + ooff0 + r, p1);
+#pragma unroll
+                for (int u = 0; u < CPL; ++u) {
+                    v0[u] = add_mod(v0[u], p0[u], q);
+                    v1[u] = add_mod(v1[u], p1[u], q);
+                }
+            }
+            st_cpl<CPL>(g.out0 + ooff0 + r, v0);
+            st_cpl<CPL>(g.out1 + ooff0 + r, v1);
+        }
     }
 }
 

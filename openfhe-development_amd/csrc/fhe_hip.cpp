@@ -4355,9 +4355,9 @@ static fhe_status bv_fast_run(const fhe_bv_key* k, uint32_t sizeQl, uint32_t bat
     // two adjacent coefficients per lane need 16-byte aligned towers (any device allocation is) and N >= 2
     const uintptr_t bits = (uintptr_t)dig | (uintptr_t)k->d_b | (uintptr_t)k->d_a | (uintptr_t)out0 | (uintptr_t)out1;
     if ((bits & 15u) == 0 && c->N >= 2)
-        FHE_LAUNCH((bv_inner_product_kernel<2>), grid, st, g);
+        FHE_LAUNCH((bv_inner_product_kernel<2, false>), grid, st, g, BvNoStage{});
     else
-        FHE_LAUNCH((bv_inner_product_kernel<1>), grid, st, g);
+        FHE_LAUNCH((bv_inner_product_kernel<1, false>), grid, st, g, BvNoStage{});
     LAUNCH_CHECK();
     return FHE_OK;
 }
@@ -4404,6 +4404,205 @@ extern "C" fhe_status fhe_bfv_eval_mult_relin_hps_bv(fhe_hps* h, const fhe_bv_ke
     if (fhe_status s = fhe_bfv_eval_mult_hps(h, a0, a1, b0, b1, c0, c1, d2, sizeQl, 1, batch, rest, wsBytes - d2Bytes, st))
         return s;
     return fhe_keyswitch_bv(k, d2, h->numQ, batch, c0, c1, 1, rest, wsBytes - d2Bytes, st);
+}
+
+// ---- rotations and leveled relinearisation on a BV key ---------------------------------------------------------------------------------
+// One launch of bv_inner_product_kernel's output-stage instance takes the digits in `dig` through the key's first D_l towers and the tail
+// of the reference's member: ExpandCRTBasisQlHat with hat (HOST, QlHatModq(l), [sizeQl]; null: none, outRows == sizeQl), += add0 / add1
+// (null: none), the EVALUATION automorphism k of both.
+static fhe_status bv_out_run(const fhe_bv_key* k, uint32_t sizeQl, uint32_t outRows, uint32_t batch, const uint64_t* dig, const uint64_t* hat,
+                             const uint64_t* add0, const uint64_t* add1, uint32_t kAuto, uint64_t* out0, uint64_t* out1, void* st,
+                             const char* who) {
+    fhe_ctx* c = k->ctx;
+    ARG_CHECK(outRows >= sizeQl && outRows <= c->L && (hat || outRows == sizeQl), std::string(who) + ": bad output rows");
+    ARG_CHECK(!hat || sizeQl <= (uint32_t)kConstVecLimbs, std::string(who) + ": more limbs than the constant vector of one launch holds");
+    ARG_CHECK(kAuto % 2 == 1, "Automorphism index not odd");
+    const uint32_t twoNmask = (2u << c->logN) - 1u;
+    uint32_t kInv = kAuto;  // Newton: the inverse of an odd k modulo 2^32, then modulo 2N
+    for (int it = 0; it < 5; ++it)
+        kInv *= 2u - kAuto * kInv;
+    kInv &= twoNmask;
+    ARG_CHECK(((kAuto & twoNmask) == 1u) || (out0 != add0 && out1 != add1 && out0 != add1 && out1 != add0),
+              std::string(who) + ": an output may be its own addend only when k = 1");
+    RT_CHECK(rt::set_device(c->device));
+    BvInnerArgs g;
+    g.digits = dig, g.keyB = k->d_b, g.keyA = k->d_a, g.out0 = out0, g.out1 = out1, g.lc = c->d_lc, g.mu128 = c->d_mu128;
+    g.logN = c->logN, g.batch = batch, g.sizeQl = sizeQl, g.sizeQ = k->sizeQ, g.acc = 0;
+    g.D = fhe_crt_decompose_towers(c, nullptr, sizeQl, k->baseBits);  // the key's first D_l towers
+    BvOutStage e;
+    e.add0 = add0, e.add1 = add1, e.outRows = outRows, e.kInv = kInv, e.useHat = hat != nullptr;
+    for (uint32_t i = 0; i < (uint32_t)kConstVecLimbs; ++i) {
+        const uint64_t v = hat && i < sizeQl ? hat[i] % c->q[i] : 0;
+        e.hat.c[i]       = TwPair{v, hat && i < sizeQl ? host::shoup(v, c->q[i]) : 0};
+    }
+    const uint32_t tilesPerRow = c->N >= (uint32_t)kTile ? (c->N >> kTileLog) : 1u;
+    const uint64_t grid        = (((uint64_t)tilesPerRow * outRows + 7) / 8) * 8 * batch;
+    ARG_CHECK(grid < ((uint64_t)1 << 31), std::string(who) + ": batch too large for one launch");
+    // two adjacent coefficients per lane need 16-byte aligned towers (any device allocation is) and N >= 2
+    const uintptr_t bits = (uintptr_t)dig | (uintptr_t)k->d_b | (uintptr_t)k->d_a | (uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)add0 | (uintptr_t)add1;
+    if ((bits & 15u) == 0 && c->N >= 2)
+        FHE_LAUNCH((bv_inner_product_kernel<2, true>), grid, st, g, e);
+    else
+        FHE_LAUNCH((bv_inner_product_kernel<1, true>), grid, st, g, e);
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+// LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:432-463) with a BV key, on the digits fhe_bv_precompute(c1) left in ws
+extern "C" fhe_status fhe_bv_eval_fast_rotation(const fhe_bv_key* k, const uint64_t* c0, uint32_t kAuto, uint32_t sizeQl, uint32_t batch,
+                                                uint64_t* out0, uint64_t* out1, const void* ws, size_t wsBytes, void* st) {
+    if (fhe_status s = bv_fast_check(k, sizeQl, batch, out0, out1, ws, wsBytes, "fhe_bv_eval_fast_rotation"))
+        return s;
+    ARG_CHECK(c0, "fhe_bv_eval_fast_rotation: null argument");
+    ARG_CHECK(out0 != c0 && out1 != c0, "fhe_bv_eval_fast_rotation: the outputs must not alias c0");
+    ARG_CHECK(kAuto % 2 == 1, "Automorphism index not odd");
+    return bv_out_run(k, sizeQl, sizeQl, batch, (const uint64_t*)ws, nullptr, c0, nullptr, kAuto, out0, out1, st, "fhe_bv_eval_fast_rotation");
+}
+// LeveledSHEBase::EvalAutomorphism (base-leveledshe.cpp:381-422) with a BV key = precompute + fast rotation
+extern "C" fhe_status fhe_bv_eval_automorphism(const fhe_bv_key* k, const uint64_t* c0, const uint64_t* c1, uint32_t kAuto, uint32_t sizeQl,
+                                               uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes, void* st) {
+    if (fhe_status s = bv_fast_check(k, sizeQl, batch, out0, out1, ws, wsBytes, "fhe_bv_eval_automorphism"))
+        return s;
+    ARG_CHECK(c0 && c1, "fhe_bv_eval_automorphism: null argument");
+    ARG_CHECK(out0 != c0 && out1 != c0, "fhe_bv_eval_automorphism: the outputs must not alias c0");
+    ARG_CHECK(kAuto % 2 == 1, "Automorphism index not odd");
+    if (fhe_status s = fhe_bv_precompute(k->ctx, c1, 1, sizeQl, k->baseBits, batch, ws, wsBytes, st))
+        return s;
+    return bv_out_run(k, sizeQl, sizeQl, batch, (const uint64_t*)ws, nullptr, c0, nullptr, kAuto, out0, out1, st, "fhe_bv_eval_automorphism");
+}
+
+// BFV, HPS family (bfvrns-leveledshe.cpp:767-938).  In HPSPOVERQLEVELED the element to be switched goes from Q down to Q_l first
+// (ScaleAndRound, :806-808, :910-912), the key switch runs at sizeQl = l + 1 limbs and both results come back to Q (ExpandCRTBasisQlHat,
+// :864-867, :920-923) before they are added.  At sizeQl == numQ both steps are the identity (Q_l = Q: the scaling tables are the CRT
+// reconstruction with zero fractions, QlHatModq is all ones) and are skipped; HPS and HPSPOVERQ never take them (:795, :859, :903).
+// workspace (words): digits [D_l][batch][sizeQl][N] | scaled / coefficient copy [batch][sizeQl][N] (the layout of fhe_bv_workspace_bytes) |
+// coefficient copy over Q [batch][numQ][N]
+static size_t bfv_bv_ws_words(const fhe_hps* h, uint32_t sizeQl, uint32_t baseBits, uint32_t batch) {
+    if (!hps_level(h, sizeQl) || batch < 1 || sizeQl > h->ctx->L)
+        return 0;
+    const uint32_t D = fhe_crt_decompose_towers(h->ctx, nullptr, sizeQl, baseBits);
+    if (D == 0)
+        return 0;
+    return (((size_t)D + 1) * batch * sizeQl + (size_t)batch * h->numQ) << h->ctx->logN;
+}
+extern "C" size_t fhe_bfv_bv_workspace_bytes(const fhe_hps* h, uint32_t sizeQl, uint32_t baseBits, uint32_t batch) {
+    return bfv_bv_ws_words(h, sizeQl, baseBits, batch) * 8;
+}
+// everything a call below checks before it enqueues; key may be null (the precompute takes baseBits instead)
+static fhe_status bfv_bv_check(const fhe_hps* h, const fhe_bv_key* k, uint32_t sizeQl, uint32_t baseBits, uint32_t batch, const void* ws,
+                               size_t wsBytes, const char* who) {
+    ARG_CHECK(h && ws && batch >= 1, std::string(who) + ": null argument");
+    if (k)
+        ARG_CHECK(k->ctx == h->ctx && k->sizeQ == h->numQ, std::string(who) + ": the key was built for another context or another Q");
+    for (uint32_t i = 0; i < h->numQ; ++i)
+        ARG_CHECK(h->qIdx[i] == i, std::string(who) + ": Q must be the context's leading limbs");
+    ARG_CHECK(hps_level(h, sizeQl), std::string(who) + ": sizeQl must be numQ (1 ... numQ for HPSPOVERQLEVELED)");
+    if (fhe_crt_decompose_towers(h->ctx, nullptr, sizeQl, baseBits) == 0)
+        return fail(FHE_ERR_UNSUPPORTED, std::string(who) + ": digit size outside the device path (baseBits <= 31, every window inside the word)");
+    const size_t need = fhe_bfv_bv_workspace_bytes(h, sizeQl, baseBits, batch);
+    ARG_CHECK(need && wsBytes >= need, std::string(who) + ": workspace too small");
+    return FHE_OK;
+}
+// x [batch][numQ][N] in evalFormat -> digits at sizeQl limbs at the start of ws (checked by the caller)
+static fhe_status bfv_bv_digits(fhe_hps* h, const uint64_t* x, int evalFormat, uint32_t sizeQl, uint32_t baseBits, uint32_t batch, void* ws,
+                                size_t wsBytes, void* st) {
+    fhe_ctx* c = h->ctx;
+    if (sizeQl == h->numQ)
+        return fhe_bv_precompute(c, x, evalFormat, sizeQl, baseBits, batch, ws, wsBytes, st);
+    const uint32_t D = fhe_crt_decompose_towers(c, nullptr, sizeQl, baseBits);
+    uint64_t* scaled = (uint64_t*)ws + (((size_t)D * batch * sizeQl) << c->logN);
+    uint64_t* coef   = scaled + (((size_t)batch * sizeQl) << c->logN);
+    if (evalFormat) {
+        if (fhe_status s = fhe_ntt_inv_oop(c, x, coef, nullptr, h->numQ, batch, st))
+            return s;
+        x = coef;
+    }
+    if (fhe_status s = fhe_scale_and_round(hps_level(h, sizeQl)->drop, x, 1, scaled, batch, st))
+        return s;
+    return fhe_bv_precompute(c, scaled, 0, sizeQl, baseBits, batch, ws, wsBytes, st);
+}
+static const uint64_t* bfv_bv_hat(const fhe_hps* h, uint32_t sizeQl) {
+    return sizeQl == h->numQ ? nullptr : hps_level(h, sizeQl)->QlHatModq.data();
+}
+// LeveledSHEBFVRNS::EvalFastRotationPrecompute (bfvrns-leveledshe.cpp:782-813)
+extern "C" fhe_status fhe_bfv_fast_rotation_precompute_bv(fhe_hps* h, const uint64_t* c1, uint32_t sizeQl, uint32_t baseBits, uint32_t batch,
+                                                          void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(c1, "fhe_bfv_fast_rotation_precompute_bv: null argument");
+    if (fhe_status s = bfv_bv_check(h, nullptr, sizeQl, baseBits, batch, ws, wsBytes, "fhe_bfv_fast_rotation_precompute_bv"))
+        return s;
+    return bfv_bv_digits(h, c1, 1, sizeQl, baseBits, batch, ws, wsBytes, st);
+}
+// LeveledSHEBFVRNS::EvalFastRotation (bfvrns-leveledshe.cpp:815-882) on the digits the precompute left in ws
+extern "C" fhe_status fhe_bfv_eval_fast_rotation_bv(fhe_hps* h, const fhe_bv_key* k, const uint64_t* c0, uint32_t kAuto, uint32_t sizeQl,
+                                                    uint32_t batch, uint64_t* out0, uint64_t* out1, const void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(k && c0 && out0 && out1, "fhe_bfv_eval_fast_rotation_bv: null argument");
+    ARG_CHECK(out0 != c0 && out1 != c0, "fhe_bfv_eval_fast_rotation_bv: the outputs must not alias c0");
+    ARG_CHECK(kAuto % 2 == 1, "Automorphism index not odd");
+    if (fhe_status s = bfv_bv_check(h, k, sizeQl, k->baseBits, batch, ws, wsBytes, "fhe_bfv_eval_fast_rotation_bv"))
+        return s;
+    return bv_out_run(k, sizeQl, h->numQ, batch, (const uint64_t*)ws, bfv_bv_hat(h, sizeQl), c0, nullptr, kAuto, out0, out1, st,
+                      "fhe_bfv_eval_fast_rotation_bv");
+}
+// LeveledSHEBFVRNS::EvalAutomorphism (bfvrns-leveledshe.cpp:767-780): RelinearizeCore on two elements, then both through the automorphism
+extern "C" fhe_status fhe_bfv_eval_automorphism_bv(fhe_hps* h, const fhe_bv_key* k, const uint64_t* c0, const uint64_t* c1, uint32_t kAuto,
+                                                   uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes,
+                                                   void* st) {
+    ARG_CHECK(k && c0 && c1 && out0 && out1, "fhe_bfv_eval_automorphism_bv: null argument");
+    ARG_CHECK(out0 != c0 && out1 != c0, "fhe_bfv_eval_automorphism_bv: the outputs must not alias c0");
+    ARG_CHECK(kAuto % 2 == 1, "Automorphism index not odd");
+    if (fhe_status s = bfv_bv_check(h, k, sizeQl, k->baseBits, batch, ws, wsBytes, "fhe_bfv_eval_automorphism_bv"))
+        return s;
+    if (fhe_status s = bfv_bv_digits(h, c1, 1, sizeQl, k->baseBits, batch, ws, wsBytes, st))
+        return s;
+    return bv_out_run(k, sizeQl, h->numQ, batch, (const uint64_t*)ws, bfv_bv_hat(h, sizeQl), c0, nullptr, kAuto, out0, out1, st,
+                      "fhe_bfv_eval_automorphism_bv");
+}
+// LeveledSHEBFVRNS::RelinearizeCore on three elements (bfvrns-leveledshe.cpp:888-938).  inEval == 0: d2 goes straight into ScaleAndRound (the
+// reference's SetFormat(COEFFICIENT), :910, finds it there already), d0 / d1 are transformed once, into c0 / c1, and the kernel adds in place.
+extern "C" fhe_status fhe_bfv_relinearize_bv(fhe_hps* h, const fhe_bv_key* k, const uint64_t* d0, const uint64_t* d1, const uint64_t* d2,
+                                             int inEval, uint32_t sizeQl, uint32_t batch, uint64_t* c0, uint64_t* c1, void* ws, size_t wsBytes,
+                                             void* st) {
+    ARG_CHECK(k && d0 && d1 && d2 && c0 && c1, "fhe_bfv_relinearize_bv: null argument");
+    if (fhe_status s = bfv_bv_check(h, k, sizeQl, k->baseBits, batch, ws, wsBytes, "fhe_bfv_relinearize_bv"))
+        return s;
+    fhe_ctx* c = h->ctx;
+    if (fhe_status s = bfv_bv_digits(h, d2, inEval, sizeQl, k->baseBits, batch, ws, wsBytes, st))
+        return s;
+    if (!inEval) {
+        if (fhe_status s = fhe_ntt_fwd_oop(c, d0, c0, nullptr, h->numQ, batch, st))
+            return s;
+        if (fhe_status s = fhe_ntt_fwd_oop(c, d1, c1, nullptr, h->numQ, batch, st))
+            return s;
+        d0 = c0, d1 = c1;
+    }
+    return bv_out_run(k, sizeQl, h->numQ, batch, (const uint64_t*)ws, bfv_bv_hat(h, sizeQl), d0, d1, 1, c0, c1, st, "fhe_bfv_relinearize_bv");
+}
+// LeveledSHEBFVRNS::EvalMult(ct, ct, key) (bfvrns-leveledshe.cpp:735-741): the product at sizeQlMult with d0, d1 left in c0, c1 and d2 in ws,
+// COEFFICIENT as the reference leaves them, then the relinearisation at sizeQlRelin.
+// workspace (bytes): d2 [batch][numQ][N] | max(the product's, the relinearisation's)
+extern "C" size_t fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes(const fhe_hps* h, uint32_t sizeQlMult, uint32_t sizeQlRelin,
+                                                                         uint32_t baseBits, uint32_t batch) {
+    const size_t mul = fhe_bfv_eval_mult_hps_workspace_bytes(h, sizeQlMult, batch);
+    const size_t ks  = fhe_bfv_bv_workspace_bytes(h, sizeQlRelin, baseBits, batch);
+    if (!mul || !ks)
+        return 0;
+    return ((((size_t)batch * h->numQ) << h->ctx->logN) * 8) + std::max(mul, ks);
+}
+extern "C" fhe_status fhe_bfv_eval_mult_relin_hps_bv_leveled(fhe_hps* h, const fhe_bv_key* k, const uint64_t* a0, const uint64_t* a1,
+                                                             const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1,
+                                                             uint32_t sizeQlMult, uint32_t sizeQlRelin, uint32_t batch, void* ws,
+                                                             size_t wsBytes, void* st) {
+    ARG_CHECK(h && k && a0 && a1 && b0 && b1 && c0 && c1 && ws && batch >= 1, "fhe_bfv_eval_mult_relin_hps_bv_leveled: null argument");
+    ARG_CHECK(hps_level(h, sizeQlMult), "fhe_bfv_eval_mult_relin_hps_bv_leveled: sizeQlMult must be numQ (1 ... numQ for HPSPOVERQLEVELED)");
+    const size_t d2Bytes = (((size_t)batch * h->numQ) << h->ctx->logN) * 8;
+    if (fhe_status s = bfv_bv_check(h, k, sizeQlRelin, k->baseBits, batch, ws, ~(size_t)0, "fhe_bfv_eval_mult_relin_hps_bv_leveled"))
+        return s;  // (everything but the size, which is this call's own)
+    const size_t need = fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes(h, sizeQlMult, sizeQlRelin, k->baseBits, batch);
+    ARG_CHECK(need && wsBytes >= need, "fhe_bfv_eval_mult_relin_hps_bv_leveled: workspace too small");
+    uint64_t* d2 = (uint64_t*)ws;
+    void* rest   = (char*)ws + d2Bytes;
+    if (fhe_status s = fhe_bfv_eval_mult_hps(h, a0, a1, b0, b1, c0, c1, d2, sizeQlMult, 0, batch, rest, wsBytes - d2Bytes, st))
+        return s;
+    return fhe_bfv_relinearize_bv(h, k, c0, c1, d2, 0, sizeQlRelin, batch, c0, c1, rest, wsBytes - d2Bytes, st);
 }
 
 // whole-tower checksums (checksum_kernel): out[row] = {sum_i w_i, sum_i (2i + 1) w_i} mod 2^64 of every limb-row of x[rows][N]; out is DEVICE memory

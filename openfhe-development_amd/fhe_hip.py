@@ -195,6 +195,15 @@ class Lib:
         S("fhe_keyswitch_bv", C.c_int, [vp, vp, u32, u32, vp, vp, C.c_int, vp, C.c_size_t, vp])
         S("fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
         S("fhe_bfv_eval_mult_relin_hps_bv", C.c_int, [vp] * 8 + [u32, u32, vp, C.c_size_t, vp])
+        S("fhe_bv_eval_fast_rotation", C.c_int, [vp, vp, u32, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bv_eval_automorphism", C.c_int, [vp, vp, vp, u32, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_bv_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_bfv_fast_rotation_precompute_bv", C.c_int, [vp, vp, u32, u32, u32, vp, C.c_size_t, vp])
+        S("fhe_bfv_eval_fast_rotation_bv", C.c_int, [vp, vp, vp, u32, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_eval_automorphism_bv", C.c_int, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_relinearize_bv", C.c_int, [vp] * 5 + [C.c_int, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes", C.c_size_t, [vp, u32, u32, u32, u32])
+        S("fhe_bfv_eval_mult_relin_hps_bv_leveled", C.c_int, [vp] * 8 + [u32, u32, u32, vp, C.c_size_t, vp])
         S("fhe_param_first_prime", u64, [u32, u64])
         S("fhe_param_last_prime", u64, [u32, u64])
         S("fhe_param_next_prime", u64, [u64, u64])
@@ -840,6 +849,20 @@ class BvKey:
                                                            stream))
         return o0, o1
 
+    def FastRotation(self, c0, k, ws_of=None, stream=None):  # base-leveledshe.cpp:432-463
+        """(Auto_k(c0 + ks0), Auto_k(ks1)) on the digits the last Precompute(c1) of `ws_of` (default: this key) left; k = automorphism index"""
+        ws, wsb = (ws_of or self).workspace(c0.n_limbs, c0.batch)
+        o0, o1 = c0.like(), c0.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bv_eval_fast_rotation(self.h, c0.ptr, k, c0.n_limbs, c0.batch, o0.ptr, o1.ptr, ws, wsb, stream))
+        return o0, o1
+
+    def Automorphism(self, c0, c1, k, stream=None):  # base-leveledshe.cpp:381-422
+        ws, wsb = self.workspace(c0.n_limbs, c0.batch)
+        o0, o1 = c0.like(), c0.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bv_eval_automorphism(self.h, c0.ptr, c1.ptr, k, c0.n_limbs, c0.batch, o0.ptr, o1.ptr, ws, wsb,
+                                                                   stream))
+        return o0, o1
+
 
 def rescale(ctx, x, stream=None):
     """DCRTPoly::DropLastElementAndScale on a Tower over context limbs [0, sizeQl) (dcrtpoly-impl.h:693-712)."""
@@ -1093,11 +1116,16 @@ class Hps:
         ctx.lib.check(ctx.lib.L.fhe_hps_create(ctx.h, self.q_idx.ctypes.data_as(u32p), self.numQ, self.r_idx.ctypes.data_as(u32p),
                                                self.numR, t, technique, C.byref(h)))
         self.h = h
+        self._ws = None  # rotations and relinearisation on a BV key: the digits of the last FastRotationPrecompute stay here (hoisting)
+        self._ws_bytes = 0
 
     def close(self):
         if self.h:
             self.ctx.lib.L.fhe_hps_destroy(self.h)
             self.h = None
+        if self._ws is not None and self.ctx.h:
+            self.ctx.free(self._ws)
+        self._ws = None
 
     def table(self, name, level=0):
         """a derived table as a flat uint64 array (doubles as their bit patterns: .view(np.float64)); None if absent"""
@@ -1130,13 +1158,67 @@ class Hps:
             self.ctx.free(ws)
         return d
 
-    def EvalMult(self, bv_key, a0, a1, b0, b1, size_ql=None, stream=None):
+    def bv_workspace(self, size_ql, base_bits, batch):
+        need = self.ctx.lib.L.fhe_bfv_bv_workspace_bytes(self.h, size_ql, base_bits, batch)
+        if need > self._ws_bytes:
+            if self._ws is not None:
+                self.ctx.free(self._ws)
+            self._ws = self.ctx.malloc(need)
+            self._ws_bytes = need
+        return self._ws, self._ws_bytes
+
+    def FastRotationPrecompute(self, c1, base_bits, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:782-813
+        """the digits of c1 (EVALUATION) at size_ql = numQ - levelsDropped limbs, left at the start of the plan's workspace"""
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.bv_workspace(size_ql, base_bits, c1.batch)
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_fast_rotation_precompute_bv(self.h, c1.ptr, size_ql, base_bits, c1.batch, ws, wsb, stream))
+        return ws, wsb
+
+    def FastRotation(self, bv_key, c0, k, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:815-882
+        """on the digits of the last FastRotationPrecompute (same size_ql, the key's base_bits); k = automorphism index"""
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.bv_workspace(size_ql, bv_key.base_bits, c0.batch)
+        o0, o1 = c0.like(), c0.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_eval_fast_rotation_bv(self.h, bv_key.h, c0.ptr, k, size_ql, c0.batch, o0.ptr, o1.ptr, ws, wsb,
+                                                                        stream))
+        return o0, o1
+
+    def Automorphism(self, bv_key, c0, c1, k, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:767-780
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.bv_workspace(size_ql, bv_key.base_bits, c0.batch)
+        o0, o1 = c0.like(), c0.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_eval_automorphism_bv(self.h, bv_key.h, c0.ptr, c1.ptr, k, size_ql, c0.batch, o0.ptr, o1.ptr,
+                                                                       ws, wsb, stream))
+        return o0, o1
+
+    def Relinearize(self, bv_key, d0, d1, d2, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:888-938
+        """(d0 + Expand(ks0(d2)), d1 + Expand(ks1(d2))), EVALUATION; the three inputs share one format (COEFFICIENT as EvalMultNoRelin
+        leaves them, or EVALUATION)"""
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.bv_workspace(size_ql, bv_key.base_bits, d0.batch)
+        c0, c1 = (self.ctx.empty(d0.batch, self.numQ, self.q_idx, EVALUATION) for _ in range(2))
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_relinearize_bv(self.h, bv_key.h, d0.ptr, d1.ptr, d2.ptr, 1 if d2.fmt == EVALUATION else 0,
+                                                                 size_ql, d0.batch, c0.ptr, c1.ptr, ws, wsb, stream))
+        return c0, c1
+
+    def EvalMult(self, bv_key, a0, a1, b0, b1, size_ql=None, size_ql_relin=None, stream=None):
         """LeveledSHEBase::EvalMult(ct, ct, key) with a BV key (base-leveledshe.cpp:201-214): the product above, then KeySwitchCore on its
-        third element at numQ limbs added to the first two; returns (c0, c1), EVALUATION"""
+        third element at numQ limbs added to the first two; returns (c0, c1), EVALUATION.  size_ql_relin given: LeveledSHEBFVRNS::EvalMult
+        (bfvrns-leveledshe.cpp:735-741) with the relinearisation at size_ql_relin = numQ - levelsDropped(key switch) limbs"""
         B = a0.batch
         size_ql = self.numQ if size_ql is None else size_ql
         c0, c1 = (self.ctx.empty(B, self.numQ, self.q_idx, EVALUATION) for _ in range(2))
         L = self.ctx.lib.L
+        if size_ql_relin is not None:
+            wsb = max(L.fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes(self.h, size_ql, size_ql_relin, bv_key.base_bits, B), 8)
+            ws = self.ctx.malloc(wsb)
+            try:
+                self.ctx.lib.check(L.fhe_bfv_eval_mult_relin_hps_bv_leveled(self.h, bv_key.h, a0.ptr, a1.ptr, b0.ptr, b1.ptr, c0.ptr, c1.ptr,
+                                                                            size_ql, size_ql_relin, B, ws, wsb, stream))
+                self.ctx.sync(stream)
+            finally:
+                self.ctx.free(ws)
+            return c0, c1
         wsb = max(L.fhe_bfv_eval_mult_relin_hps_bv_workspace_bytes(self.h, size_ql, bv_key.base_bits, B), 8)
         ws = self.ctx.malloc(wsb)
         try:
