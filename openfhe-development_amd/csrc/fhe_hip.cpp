@@ -1,6 +1,6 @@
 // fhe_hip.cpp — implementation of the C ABI in include/fhe_hip.h (compiled by hipcc for gfx950).
 //
-// Host logic only: contexts (device twiddle tables), pass planning for the NTT, conversion / key-switch
+// Host logic only: contexts (device twiddle tables), the passes of the NTT and their kernels, conversion / key-switch
 // plans (tables as CryptoParametersRNS::PrecomputeCRTTables builds them,
 // src/pke/lib/schemerns/rns-cryptoparameters.cpp:80-350) and the launch sequences that replace
 // KeySwitchHYBRID (src/pke/lib/keyswitch/keyswitch-hybrid.cpp:308-435), ApproxModDown
@@ -538,22 +538,129 @@ static inline uint32_t tiles_for(const fhe_ctx* c, uint64_t rows) {
 #define LAUNCH_CHECK() RT_CHECK(rt::last_launch_error())
 
 // ------------------------------------------------------------------------------------------------
-// NTT planning
+// NTT: passes, kernel instances, launches
 // ------------------------------------------------------------------------------------------------
-struct PassPlan {
-    bool layoutA;
-    uint32_t T;
-    uint32_t inBound  = 1;   // forward: bound (units of q) of the pass input ...
-    uint32_t outBound = 16;  // ... and of the pass output under the lazy schedule
-    uint32_t nSteps;
-    NttStep steps[6];
+static uint32_t env_u32(const char* name, uint32_t dflt) {
+    const char* v = std::getenv(name);
+    return v ? (uint32_t)std::strtoul(v, nullptr, 10) : dflt;
+}
+// The measurement switches of the NTT host path, read once per process (measurements, tests).
+//   FHE_NTT_ROW8 = 0 / 1        forces the 16- / the 8-residues-per-lane row kernel for every stage count (default: row8_for)
+//   FHE_NTT_ROW8_BATCH = 1/2/4  forces the polynomials per workgroup of the 12-stage row pass (default: row8_batch_for)
+//   FHE_NTT_ROW8_X1 = 0 / 1     forces the exchange between the waves of the batched kernel: 0 one set of LDS regions and a barrier
+//                               between the polynomials, 1 a set per polynomial (default: row8_x1_regions)
+//   FHE_NTT_HANDOVER = 0 / 1    forces the hand-over between the passes of an inverse transform off / on; any other value is
+//                               reported and means off
+//   FHE_NTT_T1 = 4 / 5          another split of a two-pass ring (ntt_t1)
+constexpr bool kHandoverDefault = true;
+struct NttSwitches {
+    int row8 = -1, row8X1 = -1;  // -1: not forced
+    uint32_t row8Batch = 0, t1 = 0;  // 0: not forced
+    bool handover = kHandoverDefault;
+};
+static const NttSwitches& ntt_switches() {
+    static const NttSwitches sw = [] {
+        NttSwitches s;
+        auto flag = [](const char* name) {
+            const char* v = std::getenv(name);
+            return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : -1;
+        };
+        s.row8   = flag("FHE_NTT_ROW8");
+        s.row8X1 = flag("FHE_NTT_ROW8_X1");
+        if (const char* v = std::getenv("FHE_NTT_ROW8_BATCH"))
+            s.row8Batch = (v[0] == '1' || v[0] == '2' || v[0] == '4') && !v[1] ? (uint32_t)(v[0] - '0') : 0u;
+        if (const char* v = std::getenv("FHE_NTT_HANDOVER")) {
+            s.handover = v[0] == '1' && !v[1];
+            if (!s.handover && !(v[0] == '0' && !v[1]))
+                fprintf(stderr, "fhe_hip: FHE_NTT_HANDOVER=%s is neither 0 nor 1: hand-over is off\n", v);
+        }
+        s.t1 = env_u32("FHE_NTT_T1", 0);
+        return s;
+    }();
+    return sw;
+}
+// Which row pass runs (both are bit-exact; profiles/r06_sweeps.md section 4): ntt_row8.h for 9..11 stages (rings 2^13..2^15: 2-10 % faster),
+// ntt_static.h's 16-residues-per-lane kernel for 12 stages (1-3 % faster there) -- for what row8_batch_for leaves of a 12-stage batch: its
+// P-aligned part runs ntt_row8.h's batched kernel.
+static bool row8_for(uint32_t T) { return ntt_switches().row8 >= 0 ? ntt_switches().row8 == 1 : T <= 11u; }
+// Polynomials per workgroup of the 12-stage row pass (ntt_row8.h, the batched kernel: one twiddle fetch serves P polynomials): the
+// measured winner per stage count (profiles/r09_sweeps.md: P = 2 with one set of X1 regions, 27.33 against 27.92 ms per headline step;
+// P = 4 27.37, a set of regions per polynomial 28.4 / 32.7); 1 = the kernel row8_for names
+constexpr uint32_t kRow8BatchDefault = 2;
+constexpr bool kRow8X1RegionsP2 = false, kRow8X1RegionsP4 = false;
+static uint32_t row8_batch_for(uint32_t T) {
+    if (T != 12u)
+        return 1u;
+    // (a forced unbatched kernel, FHE_NTT_ROW8, takes the whole batch unless P is forced as well)
+    return ntt_switches().row8Batch ? ntt_switches().row8Batch : ntt_switches().row8 >= 0 ? 1u : kRow8BatchDefault;
+}
+static bool row8_x1_regions(uint32_t P) {
+    return ntt_switches().row8X1 >= 0 ? ntt_switches().row8X1 == 1 : (P == 2 ? kRow8X1RegionsP2 : kRow8X1RegionsP4);
+}
+// stages of the strided column pass of a two-pass ring: as few as possible (>= 4), so that the column pass reads rows of
+// 2^(12-T1) consecutive words and, at T1 = 4, is a pure register radix-16 step; the other splits were measured slower
+// (profiles/r01_sweeps.md) and their kernel instances are gone.  FHE_NTT_T1 names another split where both passes have kernel
+// instances (column 4..5, row 9..12)
+static uint32_t ntt_t1(uint32_t logN) {
+    const uint32_t forced = ntt_switches().t1;
+    if (forced >= 4 && forced <= 5 && logN > (uint32_t)kTileLog && logN - forced >= 9 && logN - forced <= 12)
+        return forced;
+    return std::max(4u, logN - (uint32_t)kTileLog);
+}
+
+// One pass of a transform, as far as the choice of its kernel goes.  The single pass of a ring of at most one tile; of a larger ring the
+// strided column pass of T1 stages (the coefficient index's top bits) and the contiguous row pass of the other T2 = logN - T1.
+struct NttPass {
+    enum Kind { Single, Column, Row };
+    bool inverse = false;
+    Kind kind    = Single;
+    uint32_t T   = 0;  // stages
+    // MODE of the static kernels (ntt_static.h).  Forward: the bound class of the pass's input, 1 = canonical, 9 = at most 9q: what a
+    // row pass sees, since a column pass leaves its residues below 2q.  Inverse: 1 = the pass ends the transform, 0 = it does not.
+    int mode = 1;
+    NttPass() = default;
+    NttPass(bool inv, Kind k, uint32_t stages) : inverse(inv), kind(k), T(stages), mode(k == Row ? (inv ? 0 : 9) : 1) {}
+    bool layoutA() const { return kind == Column; }
+};
+// the passes of a transform of this context, in the order they run: forward column then row, inverse row then column
+struct NttPasses {
+    uint32_t n;
+    NttPass p[2];
+};
+static NttPasses ntt_passes(const fhe_ctx* c, bool inverse) {
+    if (c->logN <= (uint32_t)kTileLog)
+        return {1, {NttPass(inverse, NttPass::Single, c->logN), NttPass()}};
+    const uint32_t T1 = ntt_t1(c->logN);
+    const NttPass col(inverse, NttPass::Column, T1), row(inverse, NttPass::Row, c->logN - T1);
+    return inverse ? NttPasses{2, {row, col}} : NttPasses{2, {col, row}};
+}
+
+// fused epilogue of a forward transform's last pass (NttPassArgs::epi*)
+struct NttEpilogue {
+    uint32_t mode = 0, split = 0, aStride = 0, aFirst = 0;
+    int64_t aDelta = 0;  // != 0: towers of A are this many words apart (NttPassArgs::epiADelta)
+    const uint64_t* A = nullptr;
+    const TwPair* C   = nullptr;
+    uint64_t *out0 = nullptr, *out1 = nullptr;
+};
+// What a transform (ntt_run) or a pass (launch_pass) does besides the plain dense, canonical one.
+struct NttView {
+    uint32_t stride = 0;  // 0: dense [batch][nLimbs][N]; else a [batch][stride][N] view ...
+    uint32_t first  = 0;  // ... whose rows first.. of every tower are the transform's
+};
+struct NttOpts {
+    NttView src, dst;
+    int64_t srcDelta = 0;            // != 0: towers of the source are this many words apart (allocated on their own); overrides src.stride
+    const NttEpilogue* epi = nullptr;
+    bool canonOut = true;            // false: the output may stay lazy (forward: below the bound of the last step)
+    const uint32_t* proSrcLimb = nullptr;  // forward: every limb is loaded from row src.first, a limb modulo q[*proSrcLimb] (NttPassArgs::proMode)
 };
 
+// ---- the small-ring kernel (N < 4096): ntt_pass_kernel reads its plan from the arguments (steps, nSteps, canonLevels, canonStep) ----
 // stages of one pass act on the T bits of the in-tile point index p (bit T-1 first for the forward
 // transform, bit 0 first for the inverse); they are grouped into register-resident steps of <= 4 stages.
-static void plan_pass(bool inverse, bool layoutA, uint32_t logN, uint32_t T, PassPlan* pp) {
-    pp->layoutA     = layoutA;
-    pp->T           = T;
+static void plan_pass(bool inverse, bool layoutA, NttPassArgs& a) {
+    const uint32_t logN = a.logN, T = a.T;
     const int logC  = kTileLog - (int)T;
     const int jsh   = layoutA ? (int)(logN - T) : 0;  // p bit b  <->  j bit b + jsh
     const int ish   = layoutA ? logC : 0;             // p bit b  <->  tile-index bit b + ish
@@ -583,413 +690,302 @@ static void plan_pass(bool inverse, bool layoutA, uint32_t logN, uint32_t T, Pas
     uint32_t n = 0;
     const NttStep stage{8, 0, -1, 0, 0, 0, 0, 0};
     if (!layoutA && real[0].fI < 4)
-        pp->steps[n++] = stage;
+        a.steps[n++] = stage;
     for (int i = 0; i < nst; ++i)
-        pp->steps[n++] = real[i];
+        a.steps[n++] = real[i];
     if (!layoutA && real[nst - 1].fI < 4)
-        pp->steps[n++] = stage;
-    pp->nSteps = n;
+        a.steps[n++] = stage;
+    a.nSteps = n;
 }
-
 // lazy-reduction schedule of a forward pass (the static kernels derive the same at compile time, ntt_static.h SPlan): a
 // butterfly with the truncated quotient adds at most 3q to the bound of its operands and 16q < 2^64, so a step of r
-// stages needs a correction (the `a` inputs of its first stage below 2q) only when bound + 3r would exceed 16.  A column
-// pass of a two-pass ring ends by bringing its residues below 2q (it is HBM-bound: the reduction is free there).
-// `bound` (in units of q) is the bound of the pass input on entry and of its output on return.
-static void schedule_fwd(PassPlan& pp, uint32_t logN, uint32_t* bound) {
-    pp.inBound = *bound;
-    for (uint32_t i = 0; i < pp.nSteps; ++i) {
-        NttStep& st = pp.steps[i];
+// stages needs a correction (the `a` inputs of its first stage below 2q) only when bound + 3r would exceed 16.
+// `bound` (in units of q) is the bound of the pass input; returns that of its output.
+static uint32_t schedule_fwd(NttPassArgs& a, uint32_t bound) {
+    for (uint32_t i = 0; i < a.nSteps; ++i) {
+        NttStep& st = a.steps[i];
         if (st.bHi < st.bLo)
             continue;
         const uint32_t r = (uint32_t)(st.bHi - st.bLo + 1);
-        if (*bound + 3 * r <= 16) {
-            st.mode = 0;
-            *bound += 3 * r;
-        }
-        else {
-            st.mode = 1;
-            *bound  = 2 + 3 * r;
-        }
+        st.mode          = bound + 3 * r <= 16 ? 0 : 1;
+        bound            = (st.mode ? 2 : bound) + 3 * r;
     }
-    if (pp.layoutA && logN >= (uint32_t)kTileLog)
-        *bound = 2;
-    (void)logN;
+    return bound;
 }
 // twiddle index = 2^s + (j >> (Fj+4))...: lane-independent iff no lane-dependent bit of j lies above the field
-static void mark_uniform(PassPlan& pp, uint32_t logN) {
-    for (uint32_t i = 0; i < pp.nSteps; ++i) {
-        NttStep& st = pp.steps[i];
-        if (st.bHi < st.bLo)
-            continue;
-        st.uniformTw = pp.layoutA ? ((uint32_t)st.Fj + 4 == logN) : ((uint32_t)st.Fj + 4 >= (uint32_t)kTileLog);
+static void mark_uniform(NttPassArgs& a, bool layoutA) {
+    for (uint32_t i = 0; i < a.nSteps; ++i) {
+        NttStep& st = a.steps[i];
+        if (st.bHi >= st.bLo)
+            st.uniformTw = layoutA ? ((uint32_t)st.Fj + 4 == a.logN) : ((uint32_t)st.Fj + 4 >= (uint32_t)kTileLog);
+    }
+}
+static uint32_t pass_tiles(const NttPassArgs& a) { return (uint32_t)((((uint64_t)a.rows << a.logN) + kTile - 1) >> kTileLog); }
+// plans the pass into the arguments and launches it: several limbs per workgroup.  (Every pass of a ring this small is a single one; the
+// column instances of the kernel stay named here.)
+static void launch_small(const NttPass& p, bool canonOut, NttPassArgs a, void* stream) {
+    plan_pass(p.inverse, p.layoutA(), a);
+    mark_uniform(a, p.layoutA());
+    const uint32_t outBound = p.inverse ? 16u : schedule_fwd(a, 1);  // (bound of the pass output under the lazy schedule, units of q)
+    // canonicalise right after the last step that has butterfly stages (a trailing staging step only moves data)
+    a.canonStep   = 0xffffffffu;
+    a.canonLevels = 1;
+    while ((1u << a.canonLevels) < outBound)
+        ++a.canonLevels;
+    for (uint32_t i = 0; canonOut && i < a.nSteps; ++i)
+        if (a.steps[i].bHi >= a.steps[i].bLo)
+            a.canonStep = i;
+    if (p.layoutA()) {
+        if (p.inverse)
+            FHE_LAUNCH_BARRIER((ntt_pass_kernel<true, true>), pass_tiles(a), stream, a);
+        else
+            FHE_LAUNCH_BARRIER((ntt_pass_kernel<true, false>), pass_tiles(a), stream, a);
+    }
+    else {
+        if (p.inverse)
+            FHE_LAUNCH_BARRIER((ntt_pass_kernel<false, true>), pass_tiles(a), stream, a);
+        else
+            FHE_LAUNCH_BARRIER((ntt_pass_kernel<false, false>), pass_tiles(a), stream, a);
     }
 }
 
-static uint32_t ntt_t1(uint32_t logN);
-static int static_mode(const fhe_ctx* c, const struct PassPlan& pp, bool inverse);
-// fused epilogue of a forward transform's last pass (NttPassArgs::epi*)
-struct NttEpilogue {
-    uint32_t mode = 0, split = 0, aStride = 0, aFirst = 0;
-    int64_t aDelta = 0;  // != 0: towers of A are this many words apart (NttPassArgs::epiADelta)
-    const uint64_t* A = nullptr;
-    const TwPair* C   = nullptr;
-    uint64_t *out0 = nullptr, *out1 = nullptr;
-};
-static uint32_t fill_pass_args(const fhe_ctx* c, const PassPlan& pp, bool inverse, const uint64_t* xin, uint64_t* xout,
-                               const LimbSel& sel, uint32_t nLimbs, uint32_t batch, bool canonOut, uint32_t inStride,
-                               uint32_t inFirst, uint32_t outStride, uint32_t outFirst, NttPassArgs& a) {
-    a.outStride = outStride;
-    a.outFirst  = outFirst;
-    a.inStride = inStride;
-    a.inFirst  = inFirst;
-    a.xin      = xin;
-    a.x        = xout;
-    a.tw       = inverse ? c->d_twInv : c->d_tw;
-    a.twRow    = inverse ? c->d_twRowInv : c->d_twRow;
-    a.q        = c->d_q;
-    a.red      = c->d_red;
-    a.fin      = c->d_fin;
-    a.logN     = c->logN;
-    a.T        = pp.T;
-    a.nLimbs   = nLimbs;
-    a.rows     = batch * nLimbs;
-    a.batch    = batch;
-    a.nSteps   = pp.nSteps;
-    // canonicalise right after the last step that has butterfly stages (a trailing staging step only moves data)
-    a.canonStep = 0xffffffffu;
-    a.canonLevels = 1;
-    while ((1u << a.canonLevels) < pp.outBound)
-        ++a.canonLevels;
-    if (canonOut)
-        for (uint32_t i = 0; i < pp.nSteps; ++i)
-            if (pp.steps[i].bHi >= pp.steps[i].bLo)
-                a.canonStep = i;
-    for (uint32_t i = 0; i < 6; ++i)
-        a.steps[i] = i < pp.nSteps ? pp.steps[i] : NttStep{0, 0, -1, 0, 0, 0, 0, 0};
+// ---- kernel instances (N >= 4096): one function per family, THE list of its instances.  Each answers whether the family has an
+// instance for the pass and, given arguments (a != nullptr), launches it on the rows of *a.  Whatever the host wants to know about the
+// kernel a pass can land on -- the *_supported questions, the hand-over decision, the "no kernel" failures -- it asks here.
+#define FHE_PASS_IS(LA, INV, TT, MODE) (p.layoutA() == LA && p.inverse == INV && p.T == TT && p.mode == MODE)
+#define FHE_INSTANCE(COND, LAUNCH) \
+    if (COND) {                    \
+        if (a) {                   \
+            LAUNCH;                \
+        }                          \
+        return true;               \
+    }
+// ntt_static.h, 16 residues per lane: column passes of logN = 13..16 (T1 = 4) and 17 (T1 = 5); row passes T2 = logN - T1; the single
+// pass of logN = 12
+static bool static_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
+#define FHE_CASE(LA, INV, TT, MODE) \
+    FHE_INSTANCE(FHE_PASS_IS(LA, INV, TT, MODE), FHE_LAUNCH_BARRIER((ntt_static_kernel<LA, INV, TT, MODE>), pass_tiles(*a), stream, *a))
+    FHE_CASE(true, false, 4, 1) FHE_CASE(true, true, 4, 1) FHE_CASE(true, false, 5, 1) FHE_CASE(true, true, 5, 1)
+    FHE_CASE(false, false, 12, 9) FHE_CASE(false, true, 12, 0) FHE_CASE(false, false, 11, 9) FHE_CASE(false, true, 11, 0)
+    FHE_CASE(false, false, 10, 9) FHE_CASE(false, true, 10, 0) FHE_CASE(false, false, 9, 9) FHE_CASE(false, true, 9, 0)
+    FHE_CASE(false, false, 12, 1) FHE_CASE(false, true, 12, 1)
+#undef FHE_CASE
+    return false;
+}
+// ... with the fused epilogue (NttPassArgs::epi*): the forward row passes and the single pass
+static bool static_epilogue_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
+#define FHE_CASE(TT, MODE) \
+    FHE_INSTANCE(FHE_PASS_IS(false, false, TT, MODE), FHE_LAUNCH_BARRIER((ntt_static_kernel<false, false, TT, MODE, true>), pass_tiles(*a), stream, *a))
+    FHE_CASE(12, 9) FHE_CASE(11, 9) FHE_CASE(10, 9) FHE_CASE(9, 9) FHE_CASE(12, 1)
+#undef FHE_CASE
+    return false;
+}
+// ... with the load prologue (NttPassArgs::proMode): the forward column passes
+static bool static_prologue_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
+#define FHE_CASE(TT) \
+    FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1), FHE_LAUNCH_BARRIER((ntt_static_kernel<true, false, TT, 1, false, true>), pass_tiles(*a), stream, *a))
+    FHE_CASE(4) FHE_CASE(5)
+#undef FHE_CASE
+    return false;
+}
+// ... the inverse 4-stage column pass that takes the hand-over (below)
+static bool static_handover_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
+    FHE_INSTANCE(FHE_PASS_IS(true, true, 4, 1), FHE_LAUNCH_AS("HAND", (ntt_static_kernel<true, true, 4, 1, false, false, true>), pass_tiles(*a),
+                                                              kThreads, true, stream, *a))
+    return false;
+}
+// ntt_row8.h: tiles of 2^T words on 2^(T-9) waves, groups of P polynomials.  Its instances take the arguments in this form: rows and XCD order
+// for that tile size
+static NttPassArgs row8_args(const NttPassArgs& a, uint32_t P) {
+    NttPassArgs r = a;
+    r.batch       = a.batch / P;  // groups of P polynomials: the batch-fastest XCD order, in units of P
+    r.rows        = r.batch * a.nLimbs;
+    r.xcdSwizzle  = ((a.nLimbs << (a.logN - a.T)) % 8u == 0) ? 1u : 0u;
+    return r;
+}
+// row passes of two-pass rings at 8 residues per lane (8 waves per SIMD, one barrier per tile)
+static bool row8_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
+#define FHE_CASE(INV, TT, MODE)                                                                                                       \
+    FHE_INSTANCE(FHE_PASS_IS(false, INV, TT, MODE), FHE_LAUNCH_BARRIER_N((r8::ntt_row8_kernel<INV, TT - 9, MODE>), a->rows << (a->logN - TT), \
+                                                                         64u << (TT - 9), stream, *a))
+    FHE_CASE(false, 12, 9) FHE_CASE(true, 12, 0) FHE_CASE(false, 11, 9) FHE_CASE(true, 11, 0)
+    FHE_CASE(false, 10, 9) FHE_CASE(true, 10, 0) FHE_CASE(false, 9, 9) FHE_CASE(true, 9, 0)
+#undef FHE_CASE
+    return false;
+}
+// 12-stage row passes, P polynomials per workgroup; hand: the inverse instances that hand the last stage's twiddle products over
+static bool row8_batched_instance(const NttPass& p, uint32_t P, bool hand, const NttPassArgs* a, void* stream) {
+    const bool x1p = row8_x1_regions(P);
+#define FHE_CASE(INV, MODE, PP, X1P)                                                                                                  \
+    FHE_INSTANCE(FHE_PASS_IS(false, INV, 12, MODE) && P == PP && x1p == X1P && !hand,                                                 \
+                 FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P>), a->rows << (a->logN - 12), 512u, stream, *a))      \
+    FHE_INSTANCE(INV && FHE_PASS_IS(false, INV, 12, MODE) && P == PP && x1p == X1P && hand,                                           \
+                 FHE_LAUNCH_AS("HAND", (r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P, INV>), a->rows << (a->logN - 12), 512u, true, stream, \
+                               *a))
+    FHE_CASE(false, 9, 2, false) FHE_CASE(true, 0, 2, false) FHE_CASE(false, 9, 2, true) FHE_CASE(true, 0, 2, true)
+    FHE_CASE(false, 9, 4, false) FHE_CASE(true, 0, 4, false) FHE_CASE(false, 9, 4, true) FHE_CASE(true, 0, 4, true)
+#undef FHE_CASE
+    return false;
+}
+// ntt_static.h, the fused rows of fhe_poly_mul: p is the forward row pass; second = false: poly_mul_row_a, true: poly_mul_row_b
+static bool poly_mul_instance(const NttPass& p, bool second, const PolyMulArgs* a, void* stream) {
+#define FHE_CASE(TT)                                                                                                                \
+    FHE_INSTANCE(FHE_PASS_IS(false, false, TT, 9) && !second, FHE_LAUNCH_BARRIER((poly_mul_row_a_kernel<TT>), pass_tiles(a->fwd), stream, *a)) \
+    FHE_INSTANCE(FHE_PASS_IS(false, false, TT, 9) && second, FHE_LAUNCH_BARRIER((poly_mul_row_b_kernel<TT>), pass_tiles(a->fwd), stream, *a))
+    FHE_CASE(12) FHE_CASE(11) FHE_CASE(10) FHE_CASE(9)
+#undef FHE_CASE
+    return false;
+}
+#undef FHE_INSTANCE
+#undef FHE_PASS_IS
+
+// does a forward transform of this ring end in a kernel that can carry the fused epilogue?
+static bool ntt_epilogue_supported(const fhe_ctx* c) {
+    const NttPasses f = ntt_passes(c, false);
+    return static_epilogue_instance(f.p[f.n - 1], nullptr, nullptr);
+}
+// a two-pass forward transform whose column pass can carry the load prologue (NttPassArgs::proMode)
+static bool ntt_prologue_supported(const fhe_ctx* c) {
+    const NttPasses f = ntt_passes(c, false);
+    return f.n == 2 && static_prologue_instance(f.p[0], nullptr, nullptr);
+}
+
+static void fill_pass_args(const fhe_ctx* c, const NttPass& p, const uint64_t* xin, uint64_t* xout, const LimbSel& sel, uint32_t nLimbs,
+                           uint32_t batch, const NttOpts& o, NttPassArgs& a) {
+    a.outStride = o.dst.stride;
+    a.outFirst  = o.dst.first;
+    a.inStride  = o.src.stride;
+    a.inFirst   = o.src.first;
+    a.inDelta   = o.srcDelta;
+    a.xin       = xin;
+    a.x         = xout;
+    a.tw        = p.inverse ? c->d_twInv : c->d_tw;
+    a.twRow     = p.inverse ? c->d_twRowInv : c->d_twRow;
+    a.q         = c->d_q;
+    a.red       = c->d_red;
+    a.fin       = c->d_fin;
+    a.logN      = c->logN;
+    a.T         = p.T;
+    a.nLimbs    = nLimbs;
+    a.rows      = batch * nLimbs;
+    a.batch     = batch;
+    // the plan of ntt_pass_kernel (launch_small fills it in): every other kernel has its own and only asks whether canonStep is set
+    a.nSteps = a.canonLevels = 0;
+    a.canonStep              = o.canonOut ? 0u : 0xffffffffu;
+    for (NttStep& st : a.steps)
+        st = NttStep{0, 0, -1, 0, 0, 0, 0, 0};
     a.sel = sel;
-    const uint32_t grid        = tiles_for(c, a.rows);
     const uint32_t tilesPerRow = c->N >= (uint32_t)kTile ? (c->N >> kTileLog) : 1u;
     a.xcdSwizzle = (c->N >= (uint32_t)kTile && ((nLimbs * tilesPerRow) % 8u == 0)) ? 1u : 0u;
-    a.epiMode = 0, a.epiSplit = 0, a.epiAStride = 0, a.epiAFirst = 0;
-    a.epiA = nullptr, a.epiC = nullptr, a.epiOut0 = a.epiOut1 = nullptr;
-    a.proMode = 0, a.proSrcLimb = 0;
-    a.inDelta = 0, a.epiADelta = 0;
-    return grid;
+    static const NttEpilogue noEpi;
+    const NttEpilogue& e = o.epi && o.epi->mode ? *o.epi : noEpi;
+    a.epiMode = e.mode, a.epiSplit = e.split, a.epiAStride = e.aStride, a.epiAFirst = e.aFirst;
+    a.epiA = e.A, a.epiC = e.C, a.epiOut0 = e.out0, a.epiOut1 = e.out1, a.epiADelta = e.aDelta;
+    a.proMode = o.proSrcLimb ? 1 : 0, a.proSrcLimb = o.proSrcLimb ? *o.proSrcLimb : 0;
 }
-// forward: bound class of a static pass's input; inverse: does the pass end the transform (ntt_static.h MODE)
-static int static_mode(const fhe_ctx* c, const PassPlan& pp, bool inverse) {
-    const bool twoPass = c->logN > (uint32_t)kTileLog;
-    // (forward classes: 1 = canonical input, 9 = at most 9q, 16 = anything below 16q; a 4-stage first step sweeps
-    // for every class above 1, so T = 12 has one instance for both)
-    const int fclass = pp.inBound <= 1 ? 1 : 9;  // (9 = what a column pass leaves: below 2q since round 4)
-    return inverse ? ((pp.layoutA || !twoPass) ? 1 : 0) : fclass;
-}
-// Which row pass runs (both are bit-exact; profiles/r06_sweeps.md section 4): ntt_row8.h for 9..11 stages (rings 2^13..2^15: 2-10 % faster),
-// ntt_static.h's 16-residues-per-lane kernel for 12 stages (1-3 % faster there) -- for what row8_batch_for leaves of a 12-stage batch: its
-// P-aligned part runs ntt_row8.h's batched kernel.  FHE_NTT_ROW8 = 0 / 1 forces one of them (measurements).
-constexpr uint32_t kRow8BatchDefault = 2;
-constexpr bool kRow8X1RegionsP2 = false, kRow8X1RegionsP4 = false;
-static int row8_forced() {
-    static const int forced = [] {
-        const char* v = std::getenv("FHE_NTT_ROW8");
-        return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : -1;
-    }();
-    return forced;
-}
-static bool row8_for(uint32_t T) { return row8_forced() >= 0 ? row8_forced() == 1 : T <= 11u; }
-// Polynomials per workgroup of the 12-stage row pass (ntt_row8.h, the batched kernel: one twiddle fetch serves P polynomials): the
-// measured winner per stage count (profiles/r09_sweeps.md: P = 2 with one set of X1 regions, 27.33 against 27.92 ms per headline step;
-// P = 4 27.37, a set of regions per polynomial 28.4 / 32.7); 1 = the kernel row8_for names.  FHE_NTT_ROW8_BATCH = 1 / 2 / 4 forces P for
-// the stage counts that have an instance (12), FHE_NTT_ROW8_X1 = 0 / 1 the form of the exchange between waves (0: one set of LDS regions
-// and a barrier between the polynomials, 1: a set per polynomial).  Both are read once per process (measurements, tests).
-static uint32_t row8_batch_for(uint32_t T) {
-    static const uint32_t forced = [] {
-        const char* v = std::getenv("FHE_NTT_ROW8_BATCH");
-        return v && (v[0] == '1' || v[0] == '2' || v[0] == '4') && !v[1] ? (uint32_t)(v[0] - '0') : 0u;
-    }();
-    if (T != 12u)
-        return 1u;
-    // (a forced unbatched kernel, FHE_NTT_ROW8, takes the whole batch unless P is forced as well)
-    return forced ? forced : row8_forced() >= 0 ? 1u : kRow8BatchDefault;
-}
-static bool row8_x1_regions(uint32_t P) {
-    static const int forced = [] {
-        const char* v = std::getenv("FHE_NTT_ROW8_X1");
-        return v && (v[0] == '0' || v[0] == '1') ? v[0] - '0' : -1;
-    }();
-    return forced >= 0 ? forced == 1 : (P == 2 ? kRow8X1RegionsP2 : kRow8X1RegionsP4);
+// the first n polynomials of the pass's batch as a pass of their own; `a` goes on with the rest, on the same stream, as the same pass over a
+// view that starts at its first polynomial
+static NttPassArgs split_head(NttPassArgs& a, uint32_t n) {
+    NttPassArgs h = a;
+    h.batch       = n;
+    h.rows        = n * a.nLimbs;
+    a.xin += a.inDelta ? (int64_t)n * a.inDelta : (int64_t)(((uint64_t)n * (a.inStride ? a.inStride : a.nLimbs)) << a.logN);
+    a.x += ((uint64_t)n * (a.outStride ? a.outStride : a.nLimbs)) << a.logN;
+    a.batch -= n;
+    a.rows = a.batch * a.nLimbs;
+    return h;
 }
 // Hand-over between the two passes of an INVERSE 4 + 12-stage transform (ntt_row8.h / ntt_static.h, HAND): the column pass does the
 // twiddle products of the row pass's last stage.  The pair runs for exactly the part of a transform that the batched 12-stage row kernel takes:
-// ntt_run asks for it (handP = that kernel's P) only for a plain transform with canonical output, and both passes are then launched in the
+// ntt_run decides it once (handP = that kernel's P) and only for a plain transform with canonical output, and both passes are then launched in the
 // same two parts, the P-aligned one with hand-over and the remainder on the kernels every other consumer of the intermediate tower uses.
-// FHE_NTT_HANDOVER = 0 / 1 forces it off / on (measurements, tests); read once per process; any other value is reported and means off.
-constexpr bool kHandoverDefault = true;
-constexpr bool kHandOver        = true;  // (the launch sites spell the template argument by this name: fhe_launch_stats lists them as <HAND>)
-static bool ntt_handover_enabled() {
-    static const bool on = [] {
-        const char* v = std::getenv("FHE_NTT_HANDOVER");
-        if (!v)
-            return kHandoverDefault;
-        if ((v[0] == '0' || v[0] == '1') && !v[1])
-            return v[0] == '1';
-        fprintf(stderr, "fhe_hip: FHE_NTT_HANDOVER=%s is neither 0 nor 1: hand-over is off\n", v);
-        return false;
-    }();
-    return on;
-}
-// THE decision, per pass: may this pass of a transform run its hand-over instance for groups of handP polynomials?  ntt_run asks it for both
-// passes before it launches either, launch_pass asks it again for the pass it launches: the two cannot disagree.
-static bool handover_pass_ok(const fhe_ctx* c, const PassPlan& pp, bool inverse, uint32_t batch, uint32_t handP) {
-    if (!inverse || !handP || handP < 2 || batch < handP || c->logN <= (uint32_t)kTileLog)
-        return false;
-    const int mode = static_mode(c, pp, inverse);
-    return pp.layoutA ? (pp.T == 4 && mode == 1) : (pp.T == 12 && mode == 0 && row8_batch_for(pp.T) == handP);
-}
-static fhe_status launch_pass(const fhe_ctx* c, const PassPlan& pp, bool inverse, const uint64_t* xin, uint64_t* xout,
-                              const LimbSel& sel, uint32_t nLimbs, uint32_t batch, bool canonOut, void* stream,
-                              uint32_t inStride = 0, uint32_t inFirst = 0, uint32_t outStride = 0, uint32_t outFirst = 0,
-                              const NttEpilogue* epi = nullptr, const uint32_t* proSrcLimb = nullptr, int64_t inDelta = 0,
-                              uint32_t handP = 0) {
+static fhe_status launch_pass(const fhe_ctx* c, const NttPass& p, const uint64_t* xin, uint64_t* xout, const LimbSel& sel, uint32_t nLimbs,
+                              uint32_t batch, void* stream, const NttOpts& o = NttOpts(), uint32_t handP = 0) {
     NttPassArgs a;
-    uint32_t grid = fill_pass_args(c, pp, inverse, xin, xout, sel, nLimbs, batch, canonOut, inStride, inFirst, outStride,
-                                   outFirst, a);
-    if (inDelta) {  // (the static and row8 kernels only)
-        if (c->logN < (uint32_t)kTileLog)
-            return fail(FHE_ERR_UNSUPPORTED, "ntt: separately allocated towers need a ring of at least 4096");
-        a.inDelta = inDelta;
-    }
-    if (proSrcLimb) {
-        // the forward column pass that loads every limb from one row modulo q[*proSrcLimb] (ntt_prologue_supported)
-        a.proMode = 1, a.proSrcLimb = *proSrcLimb;
-        const int mode = static_mode(c, pp, inverse);
-        if (pp.layoutA && !inverse && mode == 1 && pp.T == 4)
-            FHE_LAUNCH_BARRIER((ntt_static_kernel<true, false, 4, 1, false, true>), grid, stream, a);
-        else if (pp.layoutA && !inverse && mode == 1 && pp.T == 5)
-            FHE_LAUNCH_BARRIER((ntt_static_kernel<true, false, 5, 1, false, true>), grid, stream, a);
-        else
+    fill_pass_args(c, p, xin, xout, sel, nLimbs, batch, o, a);
+    // the route of this pass for this batch: a head of whole groups of headP polynomials on a kernel of its own, the rest on another
+    enum { Small, Static, Epilogue, Prologue, Row8 } rest = c->logN < (uint32_t)kTileLog ? Small : Static;
+    uint32_t headP = 0;
+    if (o.srcDelta && rest == Small)  // (the static and row8 kernels only)
+        return fail(FHE_ERR_UNSUPPORTED, "ntt: separately allocated towers need a ring of at least 4096");
+    if (o.proSrcLimb) {
+        rest = Prologue;
+        if (!static_prologue_instance(p, nullptr, nullptr))
             return fail(FHE_ERR_UNSUPPORTED, "ntt: no prologue kernel for this pass shape");
-        LAUNCH_CHECK();
-        return FHE_OK;
     }
-    if (epi && epi->mode) {
-        // only the static forward row / single pass kernels carry the epilogue (ntt_epilogue_supported)
-        a.epiMode = epi->mode, a.epiSplit = epi->split, a.epiAStride = epi->aStride, a.epiAFirst = epi->aFirst;
-        a.epiA = epi->A, a.epiC = epi->C, a.epiOut0 = epi->out0, a.epiOut1 = epi->out1;
-        a.epiADelta = epi->aDelta;
-        const int mode = static_mode(c, pp, inverse);
-        bool launched  = false;
-#define FHE_EPI_CASE(TT, MODE) \
-    if (!launched && !pp.layoutA && !inverse && pp.T == TT && mode == MODE) { \
-        FHE_LAUNCH_BARRIER((ntt_static_kernel<false, false, TT, MODE, true>), grid, stream, a); \
-        launched = true; \
-    }
-        FHE_EPI_CASE(12, 9) FHE_EPI_CASE(11, 9) FHE_EPI_CASE(10, 9) FHE_EPI_CASE(9, 9) FHE_EPI_CASE(12, 1)
-#undef FHE_EPI_CASE
-        if (!launched)
+    else if (a.epiMode) {
+        rest = Epilogue;
+        if (!static_epilogue_instance(p, nullptr, nullptr))
             return fail(FHE_ERR_UNSUPPORTED, "ntt: no epilogue kernel for this pass shape");
-        LAUNCH_CHECK();
-        return FHE_OK;
     }
-    if (c->logN >= (uint32_t)kTileLog) {
-        // compile-time pass plans (ntt_static.h): in-place pinned-register butterflies, immediate-offset LDS exchange
-        const int mode = static_mode(c, pp, inverse);
-        bool launched  = false;
-#define FHE_STATIC_CASE(LA, INV, TT, MODE) \
-    if (!launched && pp.layoutA == LA && inverse == INV && pp.T == TT && mode == MODE) { \
-        FHE_LAUNCH_BARRIER((ntt_static_kernel<LA, INV, TT, MODE>), grid, stream, a); \
-        launched = true; \
-    }
-        // 12-stage row passes, several polynomials per workgroup (ntt_row8.h, batched): the P-aligned part of the batch; what is left of
-        // the batch follows below on the same stream, as the same pass over a view that starts at its first polynomial
-        const uint32_t P = (!pp.layoutA && c->logN > (uint32_t)kTileLog && mode == (inverse ? 0 : 9)) ? row8_batch_for(pp.T) : 1u;
+    else if (rest != Small) {
+        const uint32_t P = p.kind == NttPass::Row ? row8_batch_for(p.T) : 1u;
         // a transform with hand-over: both passes must land on the hand-over instances, or the intermediate tower is misread
-        if (handP && !(handover_pass_ok(c, pp, inverse, batch, handP) && (pp.layoutA || P == handP)))
-            return fail(FHE_ERR_UNSUPPORTED, "ntt: no hand-over kernel for this pass shape");  // (ntt_run has asked the same question)
-        if (handP && pp.layoutA) {
-            // the column pass of the part of the batch that the batched row kernel takes; the remainder follows below on the plain kernel
-            NttPassArgs h = a;
-            h.batch = batch / handP * handP;
-            h.rows  = h.batch * nLimbs;
-            FHE_LAUNCH_BARRIER((ntt_static_kernel<true, true, 4, 1, false, false, kHandOver>), tiles_for(c, h.rows), stream, h);
-            if (h.batch == batch) {
-                LAUNCH_CHECK();
-                return FHE_OK;
-            }
-            a.xin += a.inDelta ? (int64_t)h.batch * a.inDelta : (int64_t)(((uint64_t)h.batch * (a.inStride ? a.inStride : nLimbs)) << c->logN);
-            a.x += ((uint64_t)h.batch * (a.outStride ? a.outStride : nLimbs)) << c->logN;
-            a.batch = batch - h.batch;
-            a.rows  = a.batch * nLimbs;
-            grid    = tiles_for(c, a.rows);
-        }
-        if (P > 1 && batch >= P) {
-            NttPassArgs g = a;
-            g.batch      = batch / P;  // groups of P polynomials: the batch-fastest XCD order, in units of P
-            g.rows       = g.batch * nLimbs;
-            g.xcdSwizzle = ((nLimbs << (c->logN - pp.T)) % 8u == 0) ? 1u : 0u;
-            const uint32_t ggrid = g.rows << (c->logN - pp.T);
-            const bool x1p       = row8_x1_regions(P);
-            bool batched         = false;
-#define FHE_ROW8B_CASE(INV, MODE, PP, X1P) \
-    if (!batched && inverse == INV && P == PP && x1p == X1P) { \
-        if (INV && handP) /* (handP is never set for a forward pass: the instance named for INV = false is the plain one) */ \
-            FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P, (INV && kHandOver)>), ggrid, 512u, stream, g); \
-        else \
-            FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P>), ggrid, 512u, stream, g); \
-        batched = true; \
-    }
-            FHE_ROW8B_CASE(false, 9, 2, false) FHE_ROW8B_CASE(true, 0, 2, false) FHE_ROW8B_CASE(false, 9, 2, true) FHE_ROW8B_CASE(true, 0, 2, true)
-            FHE_ROW8B_CASE(false, 9, 4, false) FHE_ROW8B_CASE(true, 0, 4, false) FHE_ROW8B_CASE(false, 9, 4, true) FHE_ROW8B_CASE(true, 0, 4, true)
-#undef FHE_ROW8B_CASE
-            const uint32_t done = g.batch * P;
-            if (done == batch) {
-                LAUNCH_CHECK();
-                return FHE_OK;
-            }
-            a.xin += a.inDelta ? (int64_t)done * a.inDelta : (int64_t)(((uint64_t)done * (a.inStride ? a.inStride : nLimbs)) << c->logN);
-            a.x += ((uint64_t)done * (a.outStride ? a.outStride : nLimbs)) << c->logN;
-            a.batch = batch - done;
-            a.rows  = a.batch * nLimbs;
-            grid    = tiles_for(c, a.rows);
-        }
-        // row passes of two-pass rings at 8 residues per lane (ntt_row8.h: 8 waves per SIMD, one barrier per tile)
-        if (!pp.layoutA && c->logN > (uint32_t)kTileLog && row8_for(pp.T)) {
-            // tiles of 2^T words on 2^(T-9) waves: grid and XCD order for that tile size (in a copy: a kernel below keeps its own)
-            NttPassArgs r = a;
-            const uint32_t rgrid = r.rows << (c->logN - pp.T);
-            r.xcdSwizzle         = ((nLimbs << (c->logN - pp.T)) % 8u == 0) ? 1u : 0u;
-#define FHE_ROW8_CASE(INV, TT, MODE) \
-    if (!launched && inverse == INV && pp.T == TT && mode == MODE) { \
-        FHE_LAUNCH_BARRIER_N((r8::ntt_row8_kernel<INV, TT - 9, MODE>), rgrid, 64u << (TT - 9), stream, r); \
-        launched = true; \
-    }
-            FHE_ROW8_CASE(false, 12, 9) FHE_ROW8_CASE(true, 12, 0) FHE_ROW8_CASE(false, 11, 9) FHE_ROW8_CASE(true, 11, 0)
-            FHE_ROW8_CASE(false, 10, 9) FHE_ROW8_CASE(true, 10, 0) FHE_ROW8_CASE(false, 9, 9) FHE_ROW8_CASE(true, 9, 0)
-#undef FHE_ROW8_CASE
-        }
-        // column passes of logN = 13..16 (T1 = 4) and 17 (T1 = 5); row passes T2 = logN - T1; the single pass of logN = 12
-        FHE_STATIC_CASE(true, false, 4, 1) FHE_STATIC_CASE(true, true, 4, 1)
-        FHE_STATIC_CASE(true, false, 5, 1) FHE_STATIC_CASE(true, true, 5, 1)
-        FHE_STATIC_CASE(false, false, 12, 9) FHE_STATIC_CASE(false, true, 12, 0)
-        FHE_STATIC_CASE(false, false, 11, 9) FHE_STATIC_CASE(false, true, 11, 0)
-        FHE_STATIC_CASE(false, false, 10, 9) FHE_STATIC_CASE(false, true, 10, 0)
-        FHE_STATIC_CASE(false, false, 9, 9) FHE_STATIC_CASE(false, true, 9, 0)
-        FHE_STATIC_CASE(false, false, 12, 1) FHE_STATIC_CASE(false, true, 12, 1)
-#undef FHE_STATIC_CASE
-        if (!launched)
+        if (handP && !(batch >= handP && (p.layoutA() ? static_handover_instance(p, nullptr, nullptr)
+                                                      : P == handP && row8_batched_instance(p, P, true, nullptr, nullptr))))
+            return fail(FHE_ERR_UNSUPPORTED, "ntt: no hand-over kernel for this pass shape");
+        if (handP && p.layoutA())
+            headP = handP;  // the column pass of the part of the batch that the batched row kernel takes
+        else if (P > 1 && batch >= P && row8_batched_instance(p, P, handP != 0, nullptr, nullptr))
+            headP = P;
+        if (p.kind == NttPass::Row && row8_for(p.T) && row8_instance(p, nullptr, nullptr))
+            rest = Row8;
+        else if (!static_instance(p, nullptr, nullptr))
             return fail(FHE_ERR_UNSUPPORTED, "ntt: no kernel instance for this pass shape");
-        LAUNCH_CHECK();
-        return FHE_OK;
     }
-    // rings below one tile (N < 4096): the generic small-ring kernel, several limbs per workgroup
-    if (pp.layoutA) {
-        if (inverse)
-            FHE_LAUNCH_BARRIER((ntt_pass_kernel<true, true>), grid, stream, a);
+    if (headP) {
+        NttPassArgs h = split_head(a, batch / headP * headP);
+        if (p.layoutA())
+            static_handover_instance(p, &h, stream);
         else
-            FHE_LAUNCH_BARRIER((ntt_pass_kernel<true, false>), grid, stream, a);
+            h = row8_args(h, headP), row8_batched_instance(p, headP, handP != 0, &h, stream);
     }
-    else {
-        if (inverse)
-            FHE_LAUNCH_BARRIER((ntt_pass_kernel<false, true>), grid, stream, a);
-        else
-            FHE_LAUNCH_BARRIER((ntt_pass_kernel<false, false>), grid, stream, a);
-    }
+    if (a.batch)
+        switch (rest) {
+            case Static: static_instance(p, &a, stream); break;
+            case Epilogue: static_epilogue_instance(p, &a, stream); break;
+            case Prologue: static_prologue_instance(p, &a, stream); break;
+            case Row8: a = row8_args(a, 1), row8_instance(p, &a, stream); break;
+            case Small: launch_small(p, o.canonOut, a, stream); break;
+        }
     LAUNCH_CHECK();
     return FHE_OK;
 }
 
-static uint32_t env_u32(const char* name, uint32_t dflt) {
-    const char* v = std::getenv(name);
-    return v ? (uint32_t)std::strtoul(v, nullptr, 10) : dflt;
-}
-// stages of the strided column pass of a two-pass ring: as few as possible (>= 4), so that the column pass reads rows of
-// 2^(12-T1) consecutive words and, at T1 = 4, is a pure register radix-16 step; the other splits were measured slower
-// (profiles/r01_sweeps.md) and their kernel instances are gone
-static uint32_t ntt_t1(uint32_t logN) {
-    const uint32_t dflt = std::max(4u, logN - (uint32_t)kTileLog);
-    // FHE_NTT_T1 (measurements): another split of a two-pass ring, where both passes have kernel instances (column 4..5, row 9..12)
-    static const uint32_t forced = env_u32("FHE_NTT_T1", 0);
-    if (forced >= 4 && forced <= 5 && logN > (uint32_t)kTileLog && logN - forced >= 9 && logN - forced <= 12)
-        return forced;
-    return dflt;
-}
-
-// inStride != 0: xin is a [batch][inStride][N] view whose rows inFirst.. are transformed into the dense xout
-// outStride != 0: xout is a [batch][outStride][N] view as well (rows outFirst..)
-// does a forward transform of this ring end in a kernel that can carry the fused epilogue?
-static bool ntt_epilogue_supported(const fhe_ctx* c) {
-    if (c->logN < (uint32_t)kTileLog)
-        return false;
-    if (c->logN == (uint32_t)kTileLog)
-        return true;  // the single pass
-    // the epilogue instances of launch_pass: row passes of 9..12 stages whose input class is 9 (static_mode): any 12-stage
-    // row pass (logN = 16 after 4 column stages, 17 after 5, ...), shorter ones only after a 4-stage column pass
-    const uint32_t t1 = ntt_t1(c->logN), t2 = c->logN - t1;
-    return t2 == 12u || (t1 == 4u && t2 >= 9u && t2 <= 12u);
-}
-// a two-pass forward transform whose column pass can carry the load prologue (NttPassArgs::proMode)
-static bool ntt_prologue_supported(const fhe_ctx* c) {
-    return c->logN > (uint32_t)kTileLog && ntt_t1(c->logN) <= 5u;
-}
-static fhe_status ntt_run(fhe_ctx* c, bool inverse, const uint64_t* xin, uint64_t* xout, const uint32_t* limbIdx,
-                          uint32_t nLimbs, uint32_t batch, void* stream, uint32_t inStride = 0, uint32_t inFirst = 0,
-                          uint32_t outStride = 0, uint32_t outFirst = 0, const NttEpilogue* epi = nullptr,
-                          bool canonOut = true, const uint32_t* proSrcLimb = nullptr, int64_t inDelta = 0) {
+static fhe_status ntt_run(fhe_ctx* c, bool inverse, const uint64_t* xin, uint64_t* xout, const uint32_t* limbIdx, uint32_t nLimbs,
+                          uint32_t batch, void* stream, const NttOpts& o = NttOpts()) {
     ARG_CHECK(c && xin && xout, "fhe_ntt: null argument");
     ARG_CHECK(batch >= 1, "fhe_ntt: batch must be >= 1");
     LimbSel sel;
     if (fhe_status s = make_sel(c, limbIdx, nLimbs, &sel, "fhe_ntt"))
         return s;
     RT_CHECK(rt::set_device(c->device));
-    const uint32_t logN = c->logN;
-    if (logN <= (uint32_t)kTileLog) {
-        PassPlan p;
-        plan_pass(inverse, false, logN, logN, &p);
-        uint32_t bound = 1;
-        mark_uniform(p, logN);
-        if (!inverse)
-            schedule_fwd(p, logN, &bound);
-        p.outBound = bound;
-        return launch_pass(c, p, inverse, xin, xout, sel, nLimbs, batch, canonOut, stream, inStride, inFirst, outStride, outFirst, epi,
-                           nullptr, inDelta);
-    }
-    // two passes over HBM: a strided column pass of T1 stages (the coefficient index's top bits) and a
-    // contiguous row pass of T2 = logN - T1 stages.  T1 is kept minimal (>= 4) so that the column pass reads
-    // rows of 2^(12-T1) consecutive words (2 KiB at T1 = 4) and, at T1 = 4, needs no LDS at all.
-    const uint32_t T1 = ntt_t1(logN), T2 = logN - T1;
-    PassPlan pa, pb;
-    plan_pass(inverse, true, logN, T1, &pa);
-    plan_pass(inverse, false, logN, T2, &pb);
-    mark_uniform(pa, logN);
-    mark_uniform(pb, logN);
-    if (!inverse) {
-        uint32_t bound = 1;
-        schedule_fwd(pa, logN, &bound);
-        schedule_fwd(pb, logN, &bound);
-        pb.outBound = bound;
-    }
-    const PassPlan& p1 = inverse ? pb : pa;
-    const PassPlan& p2 = inverse ? pa : pb;
-    // Both passes of the whole batch back to back on the caller's stream.  What else was built and measured, bit-exact and slower or
-    // equal, and removed again (profiles/r02_sweeps.md session 3, profiles/r05_sweeps.md): both passes in one launch with the tower
+    const NttPasses ps = ntt_passes(c, inverse);
+    if (ps.n == 1)
+        return launch_pass(c, ps.p[0], xin, xout, sel, nLimbs, batch, stream, o);
+    // Two passes over HBM, both of the whole batch back to back on the caller's stream.  What else was built and measured, bit-exact and
+    // slower or equal, and removed again (profiles/r02_sweeps.md session 3, profiles/r05_sweeps.md): both passes in one launch with the tower
     // kept in an XCD's L2 (no retention); launches per chunk sized to the Infinity Cache (its bandwidth is within 15 % of HBM's);
     // the column pass of one chunk and the row pass of another on two streams (the queues split a CU's four workgroup slots: the
     // pair takes the sum of its parts) or as one grid of alternating roles (6 % slower); persistent pass kernels (11 % slower: a
     // fresh workgroup's loads overlap the drain of its predecessor's stores); 5 + 11 stages instead of 4 + 12 (1 % slower).
-    // hand-over (launch_pass): the plain inverse 4 + 12 transform with canonical output, for the part of the batch the batched row kernel takes.  A
-    // transform whose output stays lazy keeps the parent's words (another representative of the boundary product would show in them), and
-    // the epilogue and prologue instances keep the plain intermediate tower.
-    const uint32_t rowP  = row8_batch_for(T2);
-    const uint32_t handP = (canonOut && !(epi && epi->mode) && !proSrcLimb && ntt_handover_enabled() &&
-                            handover_pass_ok(c, p1, inverse, batch, rowP) && handover_pass_ok(c, p2, inverse, batch, rowP))
+    // THE hand-over decision (launch_pass): the plain inverse 4 + 12 transform with canonical output, for the part of the batch the batched row
+    // kernel takes.  A transform whose output stays lazy keeps the parent's words (another representative of the boundary product would show in
+    // them), and the epilogue and prologue instances keep the plain intermediate tower.
+    const uint32_t rowP  = inverse ? row8_batch_for(ps.p[0].T) : 1u;
+    const uint32_t handP = (o.canonOut && !(o.epi && o.epi->mode) && !o.proSrcLimb && ntt_switches().handover && rowP >= 2 &&
+                            batch >= rowP && row8_batched_instance(ps.p[0], rowP, true, nullptr, nullptr) &&
+                            static_handover_instance(ps.p[1], nullptr, nullptr))
                                ? rowP
                                : 0u;
-    if (fhe_status s = launch_pass(c, p1, inverse, xin, xout, sel, nLimbs, batch, false, stream, inStride, inFirst, outStride, outFirst,
-                                   nullptr, proSrcLimb, inDelta, handP))
+    // the first pass reads the source into the destination's rows and leaves them lazy; the second runs in place there and ends the transform
+    NttOpts first = o, second;
+    first.epi = nullptr, first.canonOut = false;
+    second.src = second.dst = o.dst;
+    second.epi = o.epi, second.canonOut = o.canonOut;
+    if (fhe_status s = launch_pass(c, ps.p[0], xin, xout, sel, nLimbs, batch, stream, first, handP))
         return s;
-    return launch_pass(c, p2, inverse, xout, xout, sel, nLimbs, batch, canonOut, stream, outStride, outFirst, outStride, outFirst, epi, nullptr,
-                       0, handP);
+    return launch_pass(c, ps.p[1], xout, xout, sel, nLimbs, batch, stream, second, handP);
 }
 
 extern "C" fhe_status fhe_ntt_fwd(fhe_ctx* c, uint64_t* x, const uint32_t* li, uint32_t nl, uint32_t b, void* st) {
@@ -1010,15 +1006,9 @@ extern "C" fhe_status fhe_ntt_inv_oop(fhe_ctx* c, const uint64_t* xi, uint64_t* 
 // ---- negacyclic polynomial product of COEFFICIENT-format towers: c = INTT(NTT(a) o NTT(b)) per limb ----
 // What a caller of the reference writes as a.SetFormat(EVALUATION); b.SetFormat(EVALUATION); c = a * b; c.SetFormat(COEFFICIENT)
 // (dcrtpoly-impl.h:1932-1940, dcrtpoly.h:174-189): three transforms and a Hadamard product.  Two-pass rings whose row pass has a
-// static 9..12-stage instance run the fused kernels of ntt_static.h (poly_mul_row_*); every other ring runs the plain sequence.
+// poly_mul_row_* instance (ntt_static.h) run those fused kernels; every other ring runs the plain sequence.
 extern "C" size_t fhe_poly_mul_workspace_bytes(const fhe_ctx* c, uint32_t nLimbs, uint32_t batch) {
     return c ? (((size_t)2 * batch * nLimbs) << c->logN) * 8 : 0;
-}
-static bool poly_mul_fused_supported(const fhe_ctx* c) {
-    if (c->logN <= (uint32_t)kTileLog)
-        return false;
-    const uint32_t t1 = ntt_t1(c->logN), t2 = c->logN - t1;
-    return (t1 == 4u && t2 >= 9u && t2 <= 12u) || (t1 == 5u && t2 == 12u);
 }
 extern "C" fhe_status fhe_poly_mul(fhe_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* out, const uint32_t* limbIdx,
                                    uint32_t nLimbs, uint32_t batch, void* wsv, size_t wsBytes, void* stream) {
@@ -1031,7 +1021,8 @@ extern "C" fhe_status fhe_poly_mul(fhe_ctx* c, const uint64_t* a, const uint64_t
     RT_CHECK(rt::set_device(c->device));
     uint64_t* wa = (uint64_t*)wsv;
     uint64_t* wb = wa + (((size_t)batch * nLimbs) << c->logN);
-    if (!poly_mul_fused_supported(c)) {
+    const NttPasses f = ntt_passes(c, false), i = ntt_passes(c, true);  // forward column, row; inverse row, column
+    if (f.n != 2 || !poly_mul_instance(f.p[1], false, nullptr, nullptr)) {
         if (fhe_status s = ntt_run(c, false, a, wa, limbIdx, nLimbs, batch, stream))
             return s;
         if (fhe_status s = ntt_run(c, false, b, wb, limbIdx, nLimbs, batch, stream))
@@ -1040,46 +1031,28 @@ extern "C" fhe_status fhe_poly_mul(fhe_ctx* c, const uint64_t* a, const uint64_t
             return s;
         return ntt_run(c, true, out, out, limbIdx, nLimbs, batch, stream);
     }
-    const uint32_t logN = c->logN, T1 = ntt_t1(logN), T2 = logN - T1;
-    PassPlan fa, fb, ib, ia;  // forward column / row, inverse row / column
-    plan_pass(false, true, logN, T1, &fa);
-    plan_pass(false, false, logN, T2, &fb);
-    plan_pass(true, false, logN, T2, &ib);
-    plan_pass(true, true, logN, T1, &ia);
-    for (PassPlan* p : {&fa, &fb, &ib, &ia})
-        mark_uniform(*p, logN);
-    uint32_t bound = 1;
-    schedule_fwd(fa, logN, &bound);
-    schedule_fwd(fb, logN, &bound);
-    fb.outBound = bound;
+    NttOpts lazy;
+    lazy.canonOut = false;
     // column passes of a and b, out of place into the workspace
-    if (fhe_status s = launch_pass(c, fa, false, a, wa, sel, nLimbs, batch, false, stream))
+    if (fhe_status s = launch_pass(c, f.p[0], a, wa, sel, nLimbs, batch, stream, lazy))
         return s;
-    if (fhe_status s = launch_pass(c, fa, false, b, wb, sel, nLimbs, batch, false, stream))
+    if (fhe_status s = launch_pass(c, f.p[0], b, wb, sel, nLimbs, batch, stream, lazy))
         return s;
     PolyMulArgs g;
-    const uint32_t grid = fill_pass_args(c, fb, false, wa, wa, sel, nLimbs, batch, true, 0, 0, 0, 0, g.fwd);
+    fill_pass_args(c, f.p[1], wa, wa, sel, nLimbs, batch, NttOpts(), g.fwd);
     g.fwd.xcdSwizzle = 0;  // block id = tile: the workspace tile of a block is addressed by its id
     g.inv = g.fwd;
     g.aEval = wa;
     g.lc = c->d_lc;
-#define FHE_PM_A(TT) \
-    if (T2 == TT)    \
-        FHE_LAUNCH_BARRIER((poly_mul_row_a_kernel<TT>), grid, stream, g);
-    FHE_PM_A(12) FHE_PM_A(11) FHE_PM_A(10) FHE_PM_A(9)
-#undef FHE_PM_A
+    poly_mul_instance(f.p[1], false, &g, stream);
     LAUNCH_CHECK();
-    fill_pass_args(c, fb, false, wb, wb, sel, nLimbs, batch, true, 0, 0, 0, 0, g.fwd);
-    fill_pass_args(c, ib, true, out, out, sel, nLimbs, batch, false, 0, 0, 0, 0, g.inv);
+    fill_pass_args(c, f.p[1], wb, wb, sel, nLimbs, batch, NttOpts(), g.fwd);
+    fill_pass_args(c, i.p[0], out, out, sel, nLimbs, batch, lazy, g.inv);
     g.fwd.xcdSwizzle = g.inv.xcdSwizzle = 0;
-#define FHE_PM_B(TT) \
-    if (T2 == TT)    \
-        FHE_LAUNCH_BARRIER((poly_mul_row_b_kernel<TT>), grid, stream, g);
-    FHE_PM_B(12) FHE_PM_B(11) FHE_PM_B(10) FHE_PM_B(9)
-#undef FHE_PM_B
+    poly_mul_instance(f.p[1], true, &g, stream);
     LAUNCH_CHECK();
     // inverse column pass: ends the transform (N^-1 folded in, canonical residues)
-    return launch_pass(c, ia, true, out, out, sel, nLimbs, batch, true, stream);
+    return launch_pass(c, i.p[1], out, out, sel, nLimbs, batch, stream);
 }
 
 // dir: 0 fwd, 1 inv, 2 fwd then inv; 10/11 = only the column / row pass of the forward transform,
@@ -1091,24 +1064,18 @@ extern "C" fhe_status fhe_time_ntt(fhe_ctx* c, uint64_t* x, const uint32_t* li, 
     if (fhe_status s = make_sel(c, li, nl, &sel, "fhe_time_ntt"))
         return s;
     RT_CHECK(rt::set_device(c->device));
-    PassPlan pp;
+    NttPass pp;
+    NttOpts lazy;
+    lazy.canonOut = false;
     if (dir >= 10) {
         ARG_CHECK(c->logN > (uint32_t)kTileLog && dir <= 13, "fhe_time_ntt: single-pass timing needs a two-pass ring");
-        const uint32_t T1 = ntt_t1(c->logN), T2 = c->logN - T1;
-        const bool inv = dir >= 12, colPass = (dir == 10 || dir == 13);
-        plan_pass(inv, colPass, c->logN, colPass ? T1 : T2, &pp);
-        mark_uniform(pp, c->logN);
-        if (!inv) {
-            uint32_t bound = colPass ? 1u : 2u;  // the row pass sees what the column pass leaves
-            schedule_fwd(pp, c->logN, &bound);
-            pp.outBound = bound;
-        }
+        pp = ntt_passes(c, dir >= 12).p[dir & 1];  // (the passes in the order they run)
     }
     rt::Timer tm;
     RT_CHECK(tm.start((rt::stream_t)st));
     for (int i = 0; i < iters; ++i) {
         if (dir >= 10) {
-            if (fhe_status s = launch_pass(c, pp, dir >= 12, x, x, sel, nl, b, false, st))
+            if (fhe_status s = launch_pass(c, pp, x, x, sel, nl, b, st, lazy))
                 return s;
             continue;
         }
@@ -1937,11 +1904,15 @@ static fhe_status expand_run(fhe_conv* cv, const uint64_t* x, int inEval, uint64
     const uint64_t* qsrc = (resultEval && inEval) ? x : coef;
     uint64_t* qdst       = out + ((size_t)qFirst << c->logN);
     RT_CHECK(rt::d2d_2d(qdst, tot * rowB, qsrc, nQ * rowB, nQ * rowB, batch, (rt::stream_t)st));
-    if (resultEval) {  // :1112-1114
+    if (resultEval) {  // :1112-1114: in place, the Q rows and the P rows of the tot-row towers
+        NttOpts rows;
+        rows.src.stride = rows.dst.stride = tot;
+        rows.src.first = rows.dst.first = qFirst;
         if (!inEval)
-            if (fhe_status s = ntt_run(c, false, out, out, cv->srcIdx.data(), nQ, batch, st, tot, qFirst, tot, qFirst))
+            if (fhe_status s = ntt_run(c, false, out, out, cv->srcIdx.data(), nQ, batch, st, rows))
                 return s;
-        return ntt_run(c, false, out, out, cv->dstIdx.data(), nP, batch, st, tot, pFirst, tot, pFirst);
+        rows.src.first = rows.dst.first = pFirst;
+        return ntt_run(c, false, out, out, cv->dstIdx.data(), nP, batch, st, rows);
     }
     return FHE_OK;
 }
@@ -2208,13 +2179,17 @@ static fhe_status mod_down_core(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const ui
     for (uint32_t j = 0; j < sizeP; ++j)
         pIdx[j] = p->sizeQ + j;
     // P part to COEFFICIENT (:978-985): INTT of rows [sizeQl, sizeQl+sizeP) of every tower, written densely
-    if (fhe_status s = ntt_run(c, true, x, pcoef, pIdx.data(), sizeP, nTow, st, sizeQlP, sizeQl))
+    NttOpts pRows;
+    pRows.src.stride = sizeQlP, pRows.src.first = sizeQl;
+    if (fhe_status s = ntt_run(c, true, x, pcoef, pIdx.data(), sizeP, nTow, st, pRows))
         return s;
     // P -> Q_l (:987-988)
     if (fhe_status s = fhe_approx_switch_basis(down ? down : lv->down, pcoef, sizeP, 0, md, sizeQl, 0, nTow, st))
         return s;
     // back to EVALUATION (:1001); with an epilogue the last pass also applies (:1002) and stores the final result
-    return ntt_run(c, false, md, md, nullptr, sizeQl, nTow, st, 0, 0, 0, 0, epi);
+    NttOpts fused;
+    fused.epi = epi;
+    return ntt_run(c, false, md, md, nullptr, sizeQl, nTow, st, fused);
 }
 static fhe_status mod_down_tail(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const uint64_t* x, const uint64_t* md, uint32_t nTow,
                                 uint64_t* out, bool accumulate, void* st) {
@@ -2240,6 +2215,8 @@ static fhe_status ks_precompute_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, cons
     const uint32_t sizeQl = lv->sizeQl;
     if (fhe_status s = fhe_ntt_inv_oop(c, cin, ws + w.coef, nullptr, sizeQl, batch, st))
         return s;
+    NttOpts lazy;
+    lazy.canonOut = false;
     for (uint32_t j = 0; j < lv->numParts; ++j) {
         const uint32_t nc = (uint32_t)lv->cidx[j].size();
         uint64_t* dj      = ws + w.dig[j];
@@ -2247,7 +2224,7 @@ static fhe_status ks_precompute_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, cons
             return s;
         // the digits are only read by the inner product, whose 128-bit accumulation takes any 64-bit operand: the
         // transform's outputs stay in the lazy range (< 16q), the 4-level canonicalisation is skipped
-        if (fhe_status s = ntt_run(c, false, dj, dj, lv->cidx[j].data(), nc, batch, st, 0, 0, 0, 0, nullptr, false))
+        if (fhe_status s = ntt_run(c, false, dj, dj, lv->cidx[j].data(), nc, batch, st, lazy))
             return s;
     }
     return FHE_OK;
@@ -2997,7 +2974,9 @@ static fhe_status rescale_run(fhe_ctx* c, const uint64_t* x, const uint32_t* lim
     }
     const int64_t xDelta = x1 ? x1 - x : 0;
     // lastPoly.SetFormat(COEFFICIENT)  (:696-697): INTT of the last limb of every tower, written densely
-    if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, sizeQl, l, 0, 0, nullptr, true, nullptr, xDelta))
+    NttOpts lastRow;
+    lastRow.src.stride = sizeQl, lastRow.src.first = l, lastRow.srcDelta = xDelta;
+    if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
         return s;
     if (fused) {
         NttEpilogue epi;
@@ -3005,15 +2984,19 @@ static fhe_status rescale_run(fhe_ctx* c, const uint64_t* x, const uint32_t* lim
         epi.A = x, epi.C = dB, epi.out0 = out, epi.out1 = x1 ? out1 : out;
         // (two elements: the transform works in the workspace, its fused store goes to the two output towers)
         uint64_t* work = x1 ? tmp : out;
-        if (ntt_prologue_supported(c))
-            return ntt_run(c, false, last, work, limbIdx, l, batch, st, 1, 0, 0, 0, &epi, true, &lastIdx);
+        NttOpts fusedStore;
+        fusedStore.epi = &epi;
+        if (ntt_prologue_supported(c)) {  // every limb from the one row of `last`
+            fusedStore.src.stride = 1, fusedStore.src.first = 0, fusedStore.proSrcLimb = &lastIdx;
+            return ntt_run(c, false, last, work, limbIdx, l, batch, st, fusedStore);
+        }
         // the single pass of N = 4096: SwitchModulus as a kernel of its own, then the transform with the fused store
         LimbSel sel;
         if (fhe_status s = make_sel(c, limbIdx, l, &sel, "fhe_rescale"))
             return s;
         if (fhe_status s = switch_modulus_run(c, work, sel, l, last, 1, 0, lastIdx, nullptr, batch, st))
             return s;
-        return ntt_run(c, false, work, work, limbIdx, l, batch, st, 0, 0, 0, 0, &epi);
+        return ntt_run(c, false, work, work, limbIdx, l, batch, st, fusedStore);
     }
     // tmp = SwitchModulus(last -> q_i) * QlQlInvModqlDivqlModq[i]   (:703-705)
     LimbSel sel;
@@ -3143,7 +3126,9 @@ extern "C" fhe_status fhe_mod_reduce(fhe_ctx* c, const uint64_t* x, uint32_t siz
     lock.unlock();
     const uint32_t lastIdx = l;
     if (evalFormat) {  // delta.SetFormat(COEFFICIENT)  :741
-        if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, sizeQl, l))
+        NttOpts lastRow;
+        lastRow.src.stride = sizeQl, lastRow.src.first = l;
+        if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
             return s;
     }
     else
@@ -3640,7 +3625,9 @@ extern "C" fhe_status fhe_behz_q_to_bsk(fhe_behz* h, uint64_t* x, int evalFormat
     if (evalFormat) {
         ARG_CHECK(ws && wsBytes >= fhe_behz_workspace_bytes(h, batch), "fhe_behz_q_to_bsk: workspace too small");
         uint64_t* coef = (uint64_t*)ws;
-        if (fhe_status s = ntt_run(c, true, x, coef, h->qIdx.data(), h->numQ, batch, st, tot, 0))  // :1708-1712
+        NttOpts rows;  // the Q rows of the tot-row towers ...
+        rows.src.stride = tot, rows.src.first = 0;
+        if (fhe_status s = ntt_run(c, true, x, coef, h->qIdx.data(), h->numQ, batch, st, rows))  // :1708-1712
             return s;
         g.inQ = TowerView{coef, h->numQ, 0};
         if (h->tb.W > (uint32_t)kMaxBfvLimbs)
@@ -3651,7 +3638,8 @@ extern "C" fhe_status fhe_behz_q_to_bsk(fhe_behz* h, uint64_t* x, int evalFormat
             FHE_LAUNCH((behz_q_to_bsk_kernel<false>), coeff_grid(c, batch), st, g);
         LAUNCH_CHECK();
         // only the new Bsk limbs go to EVALUATION; the Q limbs keep their original NTT form (:1776-1780)
-        return ntt_run(c, false, x, x, h->bskIdx.data(), h->numBsk, batch, st, tot, h->numQ, tot, h->numQ);
+        rows.dst.stride = tot, rows.src.first = rows.dst.first = h->numQ;  // ... and, in place, their Bsk rows
+        return ntt_run(c, false, x, x, h->bskIdx.data(), h->numBsk, batch, st, rows);
     }
     g.inQ = TowerView{x, tot, 0};
     if (h->tb.W > (uint32_t)kMaxBfvLimbs)
@@ -4623,12 +4611,11 @@ extern "C" size_t fhe_launch_stats(char* buf, size_t cap, uint64_t* total) {
     uint64_t sum = 0;
     for (auto* s = fhe::rt::LaunchSite::head().load(); s; s = s->next) {
         std::string k = s->kernel;
-        const bool hand = k.find("kHandOver") != std::string::npos;
         k = k.substr(0, k.find('<'));
         k.erase(std::remove(k.begin(), k.end(), '('), k.end());
         byKernel[k] += s->n.load();
-        if (hand)  // the hand-over instances of the NTT passes once more, on a line of their own (not in the total twice)
-            byKernel[k + "<HAND>"] += s->n.load();
+        if (s->label[0])  // a labelled site (the hand-over instances of the NTT passes: <HAND>) once more, on a line of its own (not in the total twice)
+            byKernel[k + "<" + s->label + ">"] += s->n.load();
         sum += s->n.load();
     }
     std::vector<std::pair<uint64_t, std::string>> v;

@@ -69,15 +69,16 @@ struct NttPassArgs {
     uint32_t nLimbs;      // limbs per tower (row % nLimbs selects sel.idx[])
     uint32_t rows;        // batch * nLimbs
     uint32_t batch;
-    uint32_t nSteps;
-    uint32_t canonLevels; // fast forward kernel: outputs of the canon step are < 2^canonLevels * q
-    uint32_t canonStep;   // index of the step after whose stages values are canonicalised to [0,q); >= nSteps: never
+    uint32_t nSteps;      // steps / nSteps / canonLevels: the run-time plan, read by ntt_pass_kernel alone (rings below 4096); 0 for every other kernel
+    uint32_t canonLevels; // ntt_pass_kernel, forward: outputs of the canon step are < 2^canonLevels * q
+    uint32_t canonStep;   // ntt_pass_kernel: index of the step after whose stages values are canonicalised to [0,q); 0xffffffff: never.  The static,
+                          // row8 and poly_mul kernels (compile-time plans) read of all four fields only this: != 0xffffffff = canonical output
     uint32_t xcdSwizzle;  // 1: remap blockIdx so that an XCD keeps one (limb, tile) pair across the batch
     uint32_t inStride;    // 0: xin is dense like x; else towers of xin are inStride rows apart and the
     uint32_t inFirst;     //    transformed rows start at row inFirst of each tower
     uint32_t outStride;   // 0: x is dense; else x is a [batch][outStride][N] view, rows outFirst.. of each tower
     uint32_t outFirst;    //    (applies to every access of a.x, i.e. stores and in-place reloads)
-    NttStep steps[6];
+    NttStep steps[6];     // ntt_pass_kernel alone; "no step" ({0, 0, -1, 0}) for every other kernel
     LimbSel sel;
     // Optional epilogue of the pass that stores the transform's result (static forward kernels only): instead of the
     // plain store, out = (A - r) * C [+ out]  — ApproxModDown's last line (dcrtpoly-impl.h:1002) fused with EvalMult's

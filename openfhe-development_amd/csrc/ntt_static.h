@@ -7,8 +7,8 @@
 //  * the 16 residues of a lane stay in v[32:63] and the butterflies / conditional subtractions run in place on them
 //    (ntt_bfly_pinned.h, generated and simulated by tools/gen_ntt_asm.py),
 //  * wave-uniform twiddles and all limb constants are scalar operands.
-// Same transform, tables, stage order and lazy-reduction bounds as ntt_pass_full_kernel (ntt_kernels.h), which remains
-// the fallback for pass shapes that are not instantiated here; reference: transformnat-impl.h:303-374, 512-625.
+// Same transform, tables, stage order and lazy-reduction bounds as ntt_pass_kernel (ntt_kernels.h: rings below 4096).  The host names an instance by
+// (layout, direction, T, MODE) and fails for a shape that has none (fhe_hip.cpp: NttPass, static_instance); reference: transformnat-impl.h:303-374, 512-625.
 #ifndef FHE_NTT_STATIC_H
 #define FHE_NTT_STATIC_H
 #include "ntt_kernels.h"
@@ -37,8 +37,8 @@ struct BflyZero {
 constexpr int kFwdGrow = 3;
 
 // ---- the generated code's arithmetic restated in C++ (round 5; the path of the lane emulator and of FHE_NO_BFLY_ASM builds).  Until
-// round 4 this path used exact quotients and `% 2q`: the CPU suite could not see a wrong lazy bound, a wrong pairing of SPlan with
-// schedule_fwd, or a bad quotient estimate.  Now it computes what ntt_bfly_pinned.h computes (tools/gen_ntt_asm.py: fwd_stream,
+// round 4 this path used exact quotients and `% 2q`: the CPU suite could not see a wrong lazy bound, a wrong schedule in SPlan
+// or a bad quotient estimate.  Now it computes what ntt_bfly_pinned.h computes (tools/gen_ntt_asm.py: fwd_stream,
 // red_stream) and checks the bounds the schedule promises, value by value.
 // y * w - Q' * q  (mod 2^64) with the TRUNCATED Shoup quotient Q' = y_h p_h + floor((y_h p_l + y_l p_h) / 2^32): in [0, 3q)
 FHE_HD uint64_t shoup_trunc(uint64_t y, const TwPair w, uint64_t nq) {
@@ -70,7 +70,7 @@ FHE_HD uint64_t red_estimate(uint64_t x, const BflyConst c) {
     const uint32_t k  = (uint32_t)(((x >> 32) * (uint64_t)c.redM) >> 32) >> c.redR;
     return x + (uint64_t)k * nq;
 }
-// compile-time plan of one pass: the same grouping of the T stages into register-resident steps as plan_pass()
+// compile-time plan of one pass (the host builds none for these kernels): the grouping of the T stages into steps that plan_pass() makes for ntt_pass_kernel
 template <bool LA, bool INV, int T>
 struct SPlan {
     static constexpr int logC = kTileLog - T;
@@ -96,7 +96,7 @@ struct SPlan {
     static constexpr int fI(int i) { return fp(i) + ish; }
     static constexpr bool stageFirst = !LA && fI(0) < 4;        // coalesced staging through LDS before the first step
     static constexpr bool stageLast  = !LA && fI(nst - 1) < 4;  // ... and after the last one
-    // forward lazy-reduction schedule (schedule_fwd): bound of the values, in units of q, before step i
+    // forward lazy-reduction schedule (as schedule_fwd of fhe_hip.cpp makes it for ntt_pass_kernel): bound of the values, in units of q, before step i
     static constexpr int boundBefore(int i, int bin) {
         int b = bin;
         for (int j = 0; j < i; ++j)

@@ -11,16 +11,17 @@
 #include <atomic>
 namespace fhe {
 namespace rt {
-// one counter per FHE_LAUNCH site (a relaxed increment per launch): fhe_launch_stats() sums them by kernel name
+// one counter per FHE_LAUNCH site (a relaxed increment per launch): fhe_launch_stats() sums them by kernel name.  A site may carry a
+// label (FHE_LAUNCH_AS): its launches are listed once more as kernel<label>
 struct LaunchSite {
-    const char* kernel;
+    const char *kernel, *label;
     std::atomic<uint64_t> n{0};
     LaunchSite* next;
     static std::atomic<LaunchSite*>& head() {
         static std::atomic<LaunchSite*> h{nullptr};
         return h;
     }
-    explicit LaunchSite(const char* k) : kernel(k) {
+    LaunchSite(const char* k, const char* l) : kernel(k), label(l) {
         next = head().load();
         while (!head().compare_exchange_weak(next, this)) {
         }
@@ -28,9 +29,18 @@ struct LaunchSite {
 };
 }  // namespace rt
 }  // namespace fhe
-#define FHE_COUNT_LAUNCH(kernel)                      \
-    static fhe::rt::LaunchSite fhe_launch_site_(#kernel); \
-    fhe_launch_site_.n.fetch_add(1, std::memory_order_relaxed)
+// FHE_LAUNCH: a kernel without barriers (on the lane emulator its lanes run one after the other on the launching thread);
+// FHE_LAUNCH_BARRIER: a kernel whose lanes exchange through LDS (there: one OS thread per lane); FHE_LAUNCH_BARRIER_N: such a kernel
+// with a workgroup of `threads` lanes instead of fhe::kThreads (the 8-residues-per-lane row pass, ntt_row8.h).  The same launch on the device.
+#define FHE_LAUNCH_AS(label, kernel, grid, threads, barrier, stream, ...)                    \
+    do {                                                                                     \
+        static fhe::rt::LaunchSite fhe_launch_site_(#kernel, label);                         \
+        fhe_launch_site_.n.fetch_add(1, std::memory_order_relaxed);                          \
+        FHE_RT_LAUNCH(kernel, (uint32_t)(grid), (uint32_t)(threads), barrier, stream, __VA_ARGS__); \
+    } while (0)
+#define FHE_LAUNCH(kernel, grid, stream, ...) FHE_LAUNCH_AS("", kernel, grid, fhe::kThreads, false, stream, __VA_ARGS__)
+#define FHE_LAUNCH_BARRIER(kernel, grid, stream, ...) FHE_LAUNCH_AS("", kernel, grid, fhe::kThreads, true, stream, __VA_ARGS__)
+#define FHE_LAUNCH_BARRIER_N(kernel, grid, threads, stream, ...) FHE_LAUNCH_AS("", kernel, grid, threads, true, stream, __VA_ARGS__)
 
 #ifdef FHE_EMU
 #include <chrono>
@@ -115,24 +125,7 @@ struct Timer {
 };
 }  // namespace rt
 }  // namespace fhe
-// FHE_LAUNCH: a kernel without barriers (its lanes run one after the other on the launching thread); FHE_LAUNCH_BARRIER: a kernel whose
-// lanes exchange through LDS (one OS thread per lane).  The same launch on the device.
-#define FHE_LAUNCH(kernel, grid, stream, ...)                                                     \
-    do {                                                                                          \
-        FHE_COUNT_LAUNCH(kernel);                                                                 \
-        fhe_emu::launch((uint32_t)(grid), fhe::kThreads, [=]() { kernel(__VA_ARGS__); }, false); \
-    } while (0)
-#define FHE_LAUNCH_BARRIER(kernel, grid, stream, ...)                                            \
-    do {                                                                                         \
-        FHE_COUNT_LAUNCH(kernel);                                                                \
-        fhe_emu::launch((uint32_t)(grid), fhe::kThreads, [=]() { kernel(__VA_ARGS__); }, true); \
-    } while (0)
-// (a workgroup of `threads` lanes instead of fhe::kThreads: the 8-residues-per-lane row pass, ntt_row8.h)
-#define FHE_LAUNCH_BARRIER_N(kernel, grid, threads, stream, ...)                                  \
-    do {                                                                                         \
-        FHE_COUNT_LAUNCH(kernel);                                                                \
-        fhe_emu::launch((uint32_t)(grid), (uint32_t)(threads), [=]() { kernel(__VA_ARGS__); }, true); \
-    } while (0)
+#define FHE_RT_LAUNCH(kernel, grid, threads, barrier, stream, ...) fhe_emu::launch(grid, threads, [=]() { kernel(__VA_ARGS__); }, barrier)
 #else
 #include <hip/hip_runtime.h>
 namespace fhe {
@@ -233,16 +226,7 @@ struct Timer {
 };
 }  // namespace rt
 }  // namespace fhe
-#define FHE_LAUNCH(kernel, grid, stream, ...)                                                                            \
-    do {                                                                                                                 \
-        FHE_COUNT_LAUNCH(kernel);                                                                                        \
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)(grid)), dim3(fhe::kThreads), 0, (hipStream_t)(stream), __VA_ARGS__); \
-    } while (0)
-#define FHE_LAUNCH_BARRIER FHE_LAUNCH  // (the distinction only matters to the lane emulator of the tests)
-#define FHE_LAUNCH_BARRIER_N(kernel, grid, threads, stream, ...)                                                             \
-    do {                                                                                                                    \
-        FHE_COUNT_LAUNCH(kernel);                                                                                           \
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)(grid)), dim3((uint32_t)(threads)), 0, (hipStream_t)(stream), __VA_ARGS__); \
-    } while (0)
+#define FHE_RT_LAUNCH(kernel, grid, threads, barrier, stream, ...) \
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, (hipStream_t)(stream), __VA_ARGS__)
 #endif
 #endif
