@@ -379,6 +379,31 @@ fhe_status fhe_approx_mod_down(fhe_ks_plan* plan, const uint64_t* x, uint32_t si
  * with t > 0; tables tInvModp / tModqPrecon of CryptoParametersBGVRNS are derived inside).  Same layout and workspace. */
 fhe_status fhe_approx_mod_down_bgv(fhe_ks_plan* plan, const uint64_t* x, uint32_t sizeQl, uint64_t t, uint32_t batch,
                                    uint64_t* out, void* ws, size_t wsBytes, void* stream);
+/* BGV on HYBRID keys.  The reference passes t = GetPlaintextModulus() to ApproxModDown whenever GetNoiseScale() != 1
+ * (keyswitch-hybrid.cpp:263, 299, 386); these are the composites above in that form.  Same plan, key, workspace and tower layout as
+ * their twins and the same launches: the ModDown runs with the conversion of fhe_approx_mod_down_bgv under the same fused store (the
+ * accumulating one included).  t >= 2 and invertible modulo every p_j, checked before the first launch; otherwise the twin's checks.
+ *   fhe_bgv_keyswitch_hybrid[_acc]  KeySwitchHYBRID::KeySwitchCore (keyswitch-hybrid.cpp:308-400) [+ base-leveledshe.cpp:210-211]
+ *   fhe_bgv_eval_mult               LeveledSHEBase::EvalMult(ct, ct, key) (base-leveledshe.cpp:201-214, 607-644)
+ *   fhe_bgv_ks_fast_keyswitch       EvalFastKeySwitchCore (keyswitch-hybrid.cpp:381-400) on the digits fhe_ks_precompute left: the digit
+ *                                   decomposition does not depend on t, so hoisting is shared with CKKS
+ *   fhe_bgv_eval_fast_rotation      LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:432-463)
+ *   fhe_bgv_eval_automorphism       LeveledSHEBase::EvalAutomorphism (base-leveledshe.cpp:381-422) */
+fhe_status fhe_bgv_keyswitch_hybrid(fhe_ks_plan* plan, const fhe_ks_key* key, const uint64_t* c, uint32_t sizeQl, uint64_t t,
+                                    uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bgv_keyswitch_hybrid_acc(fhe_ks_plan* plan, const fhe_ks_key* key, const uint64_t* c, uint32_t sizeQl, uint64_t t,
+                                        uint32_t batch, uint64_t* acc0, uint64_t* acc1, void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bgv_eval_mult(fhe_ks_plan* plan, const fhe_ks_key* key, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
+                             const uint64_t* b1, uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* c0, uint64_t* c1, void* ws,
+                             size_t wsBytes, void* stream);
+fhe_status fhe_bgv_ks_fast_keyswitch(fhe_ks_plan* plan, const fhe_ks_key* key, const uint64_t* c1, uint32_t sizeQl, uint64_t t,
+                                     uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bgv_eval_fast_rotation(fhe_ks_plan* plan, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k,
+                                      uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws,
+                                      size_t wsBytes, void* stream);
+fhe_status fhe_bgv_eval_automorphism(fhe_ks_plan* plan, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k,
+                                     uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws,
+                                     size_t wsBytes, void* stream);
 
 /* ---- a15: CKKS rescale ---------------------------------------------------------------------------
  * Replaces DCRTPolyImpl::DropLastElementAndScale (dcrtpoly-impl.h:693-712) with the tables of
@@ -406,6 +431,28 @@ fhe_status fhe_rescale_limbs_pair(fhe_ctx* ctx, const uint64_t* x0, const uint64
  * `evalFormat`, out [batch][sizeQl-1][N] in the same format; ws as for fhe_rescale. */
 fhe_status fhe_mod_reduce(fhe_ctx* ctx, const uint64_t* x, uint32_t sizeQl, uint64_t t, int evalFormat, uint32_t batch,
                           uint64_t* out, void* ws, size_t wsBytes, void* stream);
+/* An EVALUATION tower on a ring of static passes (N >= 4096) takes the fused form (fhe_hip.cpp mod_reduce_run): with
+ * d = INTT(x_l) * (t^-1 mod q_l), out_i = (x_i - NTT((t mod q_i) * SwitchModulus(d -> q_i))) * q_l^-1 -- the reference's words, because
+ * SwitchModulus is odd under negation for odd q_l and every step yields canonical residues.  On rings of two passes that is five launches
+ * (two INTT passes of the dropped limb, the one-row product, the column pass that switches and multiplies on its way in, the row pass
+ * whose store is the last line); the switched tower and its transform never go to HBM.  Smaller rings and COEFFICIENT towers run the
+ * member launch by launch.  t may exceed a limb (its residue is used); t must be invertible modulo the dropped limb.
+ *
+ * fhe_mod_reduce_limbs: the same over any limbs of the context (limbIdx[sizeQl], NULL = the leading ones; the last entry is the dropped
+ * limb) with the CALLER's tables as DCRTPolyImpl::ModReduce receives them (dcrtpoly-impl.h:736-738): t, negtInvModq = -t^-1 mod q_l and
+ * qlInvModq[sizeQl-1] (CryptoParametersBGVRNS::GetNegtInvModq(l) / GetqlInvModq(l)).  Fused exactly when those are the values the library
+ * derives itself; any other reduced values run the member's formula with them, launch by launch.  Errors: null argument, sizeQl < 2, a
+ * limb index outside the context, a workspace below fhe_rescale_workspace_bytes, t < 2 or a multiple of the dropped limb, a table entry
+ * that is not reduced modulo its limb.  out must not alias x. */
+fhe_status fhe_mod_reduce_limbs(fhe_ctx* ctx, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t,
+                                uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint32_t batch, uint64_t* out,
+                                void* ws, size_t wsBytes, void* stream);
+/* The two elements of one ciphertext -- towers x0, x1 -> out0, out1, each allocated on its own -- in the same launches
+ * (LeveledSHEBGVRNS::ModReduceInternalInPlace, bgvrns-leveledshe.cpp:44-75, applies the member to both elements with the same tables);
+ * ws of fhe_rescale_workspace_bytes(ctx, sizeQl, 2). */
+fhe_status fhe_mod_reduce_limbs_pair(fhe_ctx* ctx, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
+                                     uint64_t t, uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint64_t* out0,
+                                     uint64_t* out1, void* ws, size_t wsBytes, void* stream);
 
 /* ---- a17: ScaleAndRound family (BFV HPS) ----------------------------------------------------------------
  * fhe_sr_plan_create keeps the caller's tables on the device. They are the reference's own

@@ -268,7 +268,7 @@ struct fhe_ctx {
     std::map<std::vector<uint64_t>, TwPair*> constTabs;  // per-limb constants of callers' tables, by content (const_table); the map owns
                                                          // them and is emptied when it passes kMaxConstTabs entries (const_tables_trim)
     std::shared_mutex constTabsGate;  // shared: an entry point between asking for its tables and enqueuing the launches that read them
-    // cached ModReduce tables per (sizeQl, t): [0..l) = A_i, [l..2l) = B_i, [2l] = negtInvModq   (fhe_mod_reduce)
+    // cached ModReduce tables per (sizeQl, t): [0..l) = A_i, [l..2l) = B_i, [2l] = negtInvModq, [2l+1] = t^-1 mod q_l, [2l+2..3l+2) = t mod q_i   (fhe_mod_reduce)
     std::map<std::pair<uint32_t, uint64_t>, TwPair*> modReduceTabs;
     std::mutex cacheMutex;        // guards the lazily filled caches above (callers may be OpenMP threads)
 };
@@ -654,6 +654,7 @@ struct NttOpts {
     const NttEpilogue* epi = nullptr;
     bool canonOut = true;            // false: the output may stay lazy (forward: below the bound of the last step)
     const uint32_t* proSrcLimb = nullptr;  // forward: every limb is loaded from row src.first, a limb modulo q[*proSrcLimb] (NttPassArgs::proMode)
+    const TwPair* proC = nullptr;          // with proSrcLimb: ... and multiplied by proC[row of the tower] (proMode 2)
 };
 
 // ---- the small-ring kernel (N < 4096): ntt_pass_kernel reads its plan from the arguments (steps, nSteps, canonLevels, canonStep) ----
@@ -775,15 +776,20 @@ static bool static_instance(const NttPass& p, const NttPassArgs* a, void* stream
 // ... with the fused epilogue (NttPassArgs::epi*): the forward row passes and the single pass
 static bool static_epilogue_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
 #define FHE_CASE(TT, MODE) \
-    FHE_INSTANCE(FHE_PASS_IS(false, false, TT, MODE), FHE_LAUNCH_BARRIER((ntt_static_kernel<false, false, TT, MODE, true>), pass_tiles(*a), stream, *a))
+    FHE_INSTANCE(FHE_PASS_IS(false, false, TT, MODE),                                                                                \
+                 FHE_LAUNCH_AS("EPI", (ntt_static_kernel<false, false, TT, MODE, true>), pass_tiles(*a), kThreads, true, stream, *a))
     FHE_CASE(12, 9) FHE_CASE(11, 9) FHE_CASE(10, 9) FHE_CASE(9, 9) FHE_CASE(12, 1)
 #undef FHE_CASE
     return false;
 }
-// ... with the load prologue (NttPassArgs::proMode): the forward column passes
+// ... with the load prologue (NttPassArgs::proMode): the forward column passes.  Both prologue modes have the same pass shapes, so the
+// question "is there an instance" (a == nullptr) has one answer for both; a launch takes the instance of a->proMode.
 static bool static_prologue_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
-#define FHE_CASE(TT) \
-    FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1), FHE_LAUNCH_BARRIER((ntt_static_kernel<true, false, TT, 1, false, true>), pass_tiles(*a), stream, *a))
+#define FHE_CASE(TT)                                                                                                                  \
+    FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1) && !(a && a->proMode == 2u),                                                         \
+                 FHE_LAUNCH_AS("PRO", (ntt_static_kernel<true, false, TT, 1, false, 1>), pass_tiles(*a), kThreads, true, stream, *a))  \
+    FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1) && a && a->proMode == 2u,                                                            \
+                 FHE_LAUNCH_AS("PRO2", (ntt_static_kernel<true, false, TT, 1, false, 2>), pass_tiles(*a), kThreads, true, stream, *a))
     FHE_CASE(4) FHE_CASE(5)
 #undef FHE_CASE
     return false;
@@ -881,7 +887,8 @@ static void fill_pass_args(const fhe_ctx* c, const NttPass& p, const uint64_t* x
     const NttEpilogue& e = o.epi && o.epi->mode ? *o.epi : noEpi;
     a.epiMode = e.mode, a.epiSplit = e.split, a.epiAStride = e.aStride, a.epiAFirst = e.aFirst;
     a.epiA = e.A, a.epiC = e.C, a.epiOut0 = e.out0, a.epiOut1 = e.out1, a.epiADelta = e.aDelta;
-    a.proMode = o.proSrcLimb ? 1 : 0, a.proSrcLimb = o.proSrcLimb ? *o.proSrcLimb : 0;
+    a.proMode = o.proSrcLimb ? (o.proC ? 2 : 1) : 0, a.proSrcLimb = o.proSrcLimb ? *o.proSrcLimb : 0;
+    a.proC = o.proSrcLimb ? o.proC : nullptr;
 }
 // the first n polynomials of the pass's batch as a pass of their own; `a` goes on with the rest, on the same stream, as the same pass over a
 // view that starts at its first polynomial
@@ -2367,11 +2374,48 @@ extern "C" fhe_status fhe_inner_product(fhe_ctx* c, uint32_t nTerms, const uint6
     }
     return FHE_OK;
 }
+// The level's conversion P -> Q_l of ApproxModDown: t == 0 the plain one (CKKS, BFV), t >= 2 the BGV one with t^-1 mod p_j and t mod q_i
+// folded into its two constant sets (fhe_approx_mod_down_bgv below), built on first use and kept per (level, t).  The reference passes
+// t = GetPlaintextModulus() whenever GetNoiseScale() != 1 (keyswitch-hybrid.cpp:263, 299, 386).
+static fhe_status ks_down_conv(fhe_ks_plan* p, fhe_ks_plan::Level* lv, uint64_t t, const char* who, fhe_conv** out) {
+    if (t == 0) {
+        *out = lv->down;
+        return FHE_OK;
+    }
+    fhe_ctx* c = p->ctx;
+    ARG_CHECK(t >= 2, std::string(who) + ": t must be at least 2");
+    std::lock_guard<std::mutex> lock(p->cacheMutex);
+    auto it = lv->downT.find(t);
+    if (it == lv->downT.end()) {
+        const uint32_t sizeQl = lv->sizeQl;
+        std::vector<uint64_t> src(p->sizeP), dst(sizeQl), sScale(p->sizeP), dScale(sizeQl);
+        for (uint32_t j = 0; j < p->sizeP; ++j) {
+            src[j] = c->q[p->sizeQ + j];
+            ARG_CHECK(t % src[j] != 0, std::string(who) + ": t must be invertible modulo every p_j");
+            sScale[j] = host::invmod(t % src[j], src[j]);  // tInvModp (bgvrns-cryptoparameters.cpp:77-81)
+        }
+        for (uint32_t i = 0; i < sizeQl; ++i) {
+            dst[i]    = c->q[i];
+            dScale[i] = t % dst[i];
+        }
+        fhe_conv* cv = nullptr;
+        if (fhe_status s = conv_build(c, src, dst, &cv, sScale.data(), dScale.data()))
+            return s;
+        it = lv->downT.emplace(t, cv).first;
+    }
+    *out = it->second;
+    return FHE_OK;
+}
+// t: 0 = the CKKS / BFV form; >= 2 = the BGV form, the ModDown with the level's downT conversion (ks_down_conv) under the same fused epilogue
 static fhe_status ks_fast_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const fhe_ks_key* key, const uint64_t* cin,
                               uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* ws, const KsLayout& w, void* st,
-                              bool accumulate) {
+                              bool accumulate, uint64_t t = 0) {
     fhe_ctx* c            = p->ctx;
     const uint32_t sizeQl = lv->sizeQl;
+    fhe_conv* down        = nullptr;  // (null: the plan's own conversion, mod_down_core)
+    if (t)
+        if (fhe_status s = ks_down_conv(p, lv, t, "key switch", &down))
+            return s;
     if (fhe_status s = ks_inner_run(p, lv, key, cin, batch, ws + w.e0, ws + w.e1, ws, w, st))
         return s;
     // 2 x ApproxModDown (:381-400): e0 and e1 are adjacent in the workspace (w.e1 == w.e0 + batch*sizeQlP*N), so the
@@ -2382,9 +2426,9 @@ static fhe_status ks_fast_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const fhe_
         NttEpilogue epi;
         epi.mode = accumulate ? 2u : 1u, epi.split = batch, epi.aStride = sizeQl + p->sizeP, epi.aFirst = 0;
         epi.A = ws + w.e0, epi.C = lv->d_PInv, epi.out0 = out0, epi.out1 = out1;
-        return mod_down_core(p, lv, ws + w.e0, 2 * batch, ws + w.pcoef, ws + w.md, st, nullptr, &epi);
+        return mod_down_core(p, lv, ws + w.e0, 2 * batch, ws + w.pcoef, ws + w.md, st, down, &epi);
     }
-    if (fhe_status s = mod_down_core(p, lv, ws + w.e0, 2 * batch, ws + w.pcoef, ws + w.md, st))
+    if (fhe_status s = mod_down_core(p, lv, ws + w.e0, 2 * batch, ws + w.pcoef, ws + w.md, st, down))
         return s;
     if (fhe_status s = mod_down_tail(p, lv, ws + w.e0, ws + w.md, batch, out0, accumulate, st))
         return s;
@@ -2392,13 +2436,13 @@ static fhe_status ks_fast_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const fhe_
 }
 static fhe_status keyswitch_run(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* cin, uint32_t sizeQl,
                                 uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* ws, const KsLayout& w,
-                                void* st, bool accumulate = false) {
+                                void* st, bool accumulate = false, uint64_t t = 0) {
     fhe_ks_plan::Level* lv = nullptr;
     if (fhe_status s = ks_level(p, sizeQl, &lv))
         return s;
     if (fhe_status s = ks_precompute_run(p, lv, cin, batch, ws, w, st))
         return s;
-    return ks_fast_run(p, lv, key, cin, batch, out0, out1, ws, w, st, accumulate);
+    return ks_fast_run(p, lv, key, cin, batch, out0, out1, ws, w, st, accumulate, t);
 }
 
 extern "C" fhe_status fhe_keyswitch_hybrid(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* cin, uint32_t sizeQl,
@@ -2469,21 +2513,26 @@ extern "C" fhe_status fhe_ks_fast_keyswitch(fhe_ks_plan* p, const fhe_ks_key* ke
 }
 // LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:432-463): ba = EvalFastKeySwitchCore(digits, key_k);
 // ba[0] += cv[0]; both elements through AutomorphismTransform(k)
-extern "C" fhe_status fhe_eval_fast_rotation(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1,
-                                             uint32_t k, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1,
-                                             void* ws, size_t wsBytes, void* st) {
-    KS_COMMON_CHECKS("fhe_eval_fast_rotation")
-    ARG_CHECK(key && c0 && c1 && out0 && out1 && key->plan == p, "fhe_eval_fast_rotation: bad key or null argument");
-    ARG_CHECK(k % 2 == 1, "Automorphism index not odd");
-    uint64_t* wsp = (uint64_t*)ws;
-    fhe_ctx* c    = p->ctx;
-    if (fhe_status s = ks_fast_run(p, lv, key, c1, batch, wsp + w.k0, wsp + w.k1, wsp, w, st, false))
+static fhe_status fast_rotation_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1,
+                                    uint32_t k, uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* wsp, const KsLayout& w, void* st,
+                                    uint64_t t) {
+    fhe_ctx* c            = p->ctx;
+    const uint32_t sizeQl = lv->sizeQl;
+    if (fhe_status s = ks_fast_run(p, lv, key, c1, batch, wsp + w.k0, wsp + w.k1, wsp, w, st, false, t))
         return s;
     if (fhe_status s = fhe_add(c, wsp + w.k0, wsp + w.k0, c0, nullptr, sizeQl, batch, st))
         return s;
     if (fhe_status s = fhe_automorph(c, out0, wsp + w.k0, k, 1, nullptr, sizeQl, batch, st))
         return s;
     return fhe_automorph(c, out1, wsp + w.k1, k, 1, nullptr, sizeQl, batch, st);
+}
+extern "C" fhe_status fhe_eval_fast_rotation(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1,
+                                             uint32_t k, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1,
+                                             void* ws, size_t wsBytes, void* st) {
+    KS_COMMON_CHECKS("fhe_eval_fast_rotation")
+    ARG_CHECK(key && c0 && c1 && out0 && out1 && key->plan == p, "fhe_eval_fast_rotation: bad key or null argument");
+    ARG_CHECK(k % 2 == 1, "Automorphism index not odd");
+    return fast_rotation_run(p, lv, key, c0, c1, k, batch, out0, out1, (uint64_t*)ws, w, st, 0);
 }
 // LeveledSHEBase::EvalAutomorphism (base-leveledshe.cpp:381-422) = KeySwitchInPlace + AutomorphismTransform on both
 // elements; identical result to precompute + fast rotation
@@ -2494,6 +2543,74 @@ extern "C" fhe_status fhe_eval_automorphism(fhe_ks_plan* p, const fhe_ks_key* ke
         return s;
     return fhe_eval_fast_rotation(p, key, c0, c1, k, sizeQl, batch, out0, out1, ws, wsBytes, st);
 }
+
+// ---- BGV on HYBRID keys: the composites above with ApproxModDown's plaintext-modulus factors (t = GetPlaintextModulus(), passed by the
+// reference whenever GetNoiseScale() != 1: keyswitch-hybrid.cpp:263, 299, 386).  Same plan, key, workspace and layout as the CKKS twins, the
+// same launches: only the conversion constants of the ModDown differ (ks_down_conv).  Checks: those of the twin, t >= 2, t invertible modulo
+// every p_j -- all before the first launch.
+#define BGV_COMMON_CHECKS(who)                                      \
+    KS_COMMON_CHECKS(who)                                           \
+    ARG_CHECK(t >= 2, who ": t must be at least 2");                \
+    {                                                               \
+        fhe_conv* down_ = nullptr;                                  \
+        if (fhe_status s_ = ks_down_conv(p, lv, t, who, &down_))    \
+            return s_;                                              \
+    }
+// replaces KeySwitchHYBRID::KeySwitchCore (keyswitch-hybrid.cpp:308-400) under BGV
+extern "C" fhe_status fhe_bgv_keyswitch_hybrid(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* cin, uint32_t sizeQl, uint64_t t,
+                                               uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes, void* st) {
+    BGV_COMMON_CHECKS("fhe_bgv_keyswitch_hybrid")
+    ARG_CHECK(key && cin && out0 && out1 && key->plan == p, "fhe_bgv_keyswitch_hybrid: bad key or null argument");
+    return keyswitch_run(p, key, cin, sizeQl, batch, out0, out1, (uint64_t*)ws, w, st, false, t);
+}
+// ... with `acc0 += ks0(c); acc1 += ks1(c)` (base-leveledshe.cpp:207-211), the additions in the ModDown epilogue
+extern "C" fhe_status fhe_bgv_keyswitch_hybrid_acc(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* cin, uint32_t sizeQl, uint64_t t,
+                                                   uint32_t batch, uint64_t* acc0, uint64_t* acc1, void* ws, size_t wsBytes, void* st) {
+    BGV_COMMON_CHECKS("fhe_bgv_keyswitch_hybrid_acc")
+    ARG_CHECK(key && cin && acc0 && acc1 && key->plan == p, "fhe_bgv_keyswitch_hybrid_acc: bad key or null argument");
+    return keyswitch_run(p, key, cin, sizeQl, batch, acc0, acc1, (uint64_t*)ws, w, st, true, t);
+}
+// replaces LeveledSHEBase::EvalMult(ct, ct, key) (base-leveledshe.cpp:201-214, EvalMultCore :607-644) under BGV
+extern "C" fhe_status fhe_bgv_eval_mult(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
+                                        const uint64_t* b1, uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* c0, uint64_t* c1,
+                                        void* ws, size_t wsBytes, void* st) {
+    BGV_COMMON_CHECKS("fhe_bgv_eval_mult")
+    ARG_CHECK(key && a0 && a1 && b0 && b1 && c0 && c1 && key->plan == p, "fhe_bgv_eval_mult: bad key or null argument");
+    uint64_t* wsp = (uint64_t*)ws;
+    if (fhe_status s = fhe_tensor(p->ctx, a0, a1, b0, b1, c0, c1, wsp + w.d2, nullptr, sizeQl, batch, st))
+        return s;
+    return keyswitch_run(p, key, wsp + w.d2, sizeQl, batch, c0, c1, wsp, w, st, true, t);
+}
+// replaces KeySwitchHYBRID::EvalFastKeySwitchCore (keyswitch-hybrid.cpp:381-400) under BGV, on the digits fhe_ks_precompute left (the digit
+// decomposition does not depend on t: hoisting is shared with CKKS)
+extern "C" fhe_status fhe_bgv_ks_fast_keyswitch(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* c1, uint32_t sizeQl, uint64_t t,
+                                                uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes, void* st) {
+    BGV_COMMON_CHECKS("fhe_bgv_ks_fast_keyswitch")
+    ARG_CHECK(key && c1 && out0 && out1 && key->plan == p, "fhe_bgv_ks_fast_keyswitch: bad key or null argument");
+    return ks_fast_run(p, lv, key, c1, batch, out0, out1, (uint64_t*)ws, w, st, false, t);
+}
+// replaces LeveledSHEBase::EvalFastRotation (base-leveledshe.cpp:432-463) under BGV
+extern "C" fhe_status fhe_bgv_eval_fast_rotation(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k,
+                                                 uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws,
+                                                 size_t wsBytes, void* st) {
+    BGV_COMMON_CHECKS("fhe_bgv_eval_fast_rotation")
+    ARG_CHECK(key && c0 && c1 && out0 && out1 && key->plan == p, "fhe_bgv_eval_fast_rotation: bad key or null argument");
+    ARG_CHECK(k % 2 == 1, "Automorphism index not odd");
+    return fast_rotation_run(p, lv, key, c0, c1, k, batch, out0, out1, (uint64_t*)ws, w, st, t);
+}
+// replaces LeveledSHEBase::EvalAutomorphism (base-leveledshe.cpp:381-422) under BGV
+extern "C" fhe_status fhe_bgv_eval_automorphism(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k,
+                                                uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws,
+                                                size_t wsBytes, void* st) {
+    BGV_COMMON_CHECKS("fhe_bgv_eval_automorphism")
+    ARG_CHECK(key && c0 && c1 && out0 && out1 && key->plan == p, "fhe_bgv_eval_automorphism: bad key or null argument");
+    ARG_CHECK(k % 2 == 1, "Automorphism index not odd");
+    uint64_t* wsp = (uint64_t*)ws;
+    if (fhe_status s = ks_precompute_run(p, lv, c1, batch, wsp, w, st))
+        return s;
+    return fast_rotation_run(p, lv, key, c0, c1, k, batch, out0, out1, wsp, w, st, t);
+}
+#undef BGV_COMMON_CHECKS
 
 // ---- double hoisting: work in the extended basis Q_l u P, one ModDown at the end (ckksrns-fhe.cpp:1830-2000) ----
 static fhe_status ext_limbs(const fhe_ks_plan* p, uint32_t sizeQl, std::vector<uint32_t>& idx) {
@@ -2871,26 +2988,9 @@ extern "C" fhe_status fhe_approx_mod_down_bgv(fhe_ks_plan* p, const uint64_t* x,
     fhe_ks_plan::Level* lv = nullptr;
     if (fhe_status s = ks_level(p, sizeQl, &lv))
         return s;
-    std::unique_lock<std::mutex> lock(p->cacheMutex);
-    auto it = lv->downT.find(t);
-    if (it == lv->downT.end()) {
-        std::vector<uint64_t> src(p->sizeP), dst(sizeQl), sScale(p->sizeP), dScale(sizeQl);
-        for (uint32_t j = 0; j < p->sizeP; ++j) {
-            src[j] = c->q[p->sizeQ + j];
-            ARG_CHECK(t % src[j] != 0, "fhe_approx_mod_down_bgv: t must be invertible modulo every p_j");
-            sScale[j] = host::invmod(t % src[j], src[j]);  // tInvModp (bgvrns-cryptoparameters.cpp:77-81)
-        }
-        for (uint32_t i = 0; i < sizeQl; ++i) {
-            dst[i]    = c->q[i];
-            dScale[i] = t % dst[i];
-        }
-        fhe_conv* cv = nullptr;
-        if (fhe_status s = conv_build(c, src, dst, &cv, sScale.data(), dScale.data()))
-            return s;
-        it = lv->downT.emplace(t, cv).first;
-    }
-    fhe_conv* downT = it->second;
-    lock.unlock();
+    fhe_conv* downT = nullptr;
+    if (fhe_status s = ks_down_conv(p, lv, t, "fhe_approx_mod_down_bgv", &downT))
+        return s;
     uint64_t* ws = (uint64_t*)wsv;
     if (fhe_status s = mod_down_core(p, lv, x, batch, ws + w.pcoef, ws + w.md, st, downT))
         return s;
@@ -3089,8 +3189,86 @@ extern "C" fhe_status fhe_rescale_limbs_pair(fhe_ctx* c, const uint64_t* x0, con
 
 // DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755), the BGV modulus switch by the last limb with plaintext modulus t:
 //   delta = [last limb]_COEFF * (-t^-1 mod q_l);  x_i = (x_i + t * SwitchModulus(delta -> q_i)) * q_l^-1,  i < l.
-// Launched as x_i * B_i + NTT(SwitchModulus(delta) * A_i) with B_i = q_l^-1 and A_i = t * q_l^-1 mod q_i: the NTT is
-// linear, every step yields canonical residues, so the words equal the reference's.  Same workspace as fhe_rescale.
+// The device constants of one call (one Shoup pair per kept limb unless noted):
+struct ModReduceTabs {
+    const TwPair* A;     // t * qlInvModq[i] mod q_i                       (unfused)
+    const TwPair* B;     // qlInvModq[i]
+    const TwPair* T;     // t mod q_i                                      (fused)
+    const TwPair* neg;   // one pair modulo q_l: negtInvModq               (unfused)
+    const TwPair* pos;   // one pair modulo q_l: t^-1 mod q_l = -negtInvModq  (fused)
+    bool derived;        // B and neg are what the library derives from the moduli and t: the fused form computes the member's words
+};
+// x[batch][sizeQl][N] over context limbs limbIdx[0..sizeQl) (null: the leading ones) -> out[batch][sizeQl-1][N].  ws: last[batch][N] +
+// tmp[batch][l][N] (fhe_rescale_workspace_bytes).
+//   unfused (rings below 4096, COEFFICIENT towers, foreign tables): x_i * B_i + NTT(SwitchModulus(delta) * A_i).  The NTT is linear and every
+//   step yields canonical residues, so the words equal the reference's.  Six launches for an EVALUATION tower.
+//   fused (EVALUATION towers on rings of static passes, derived tables): the shape (A - r) * C of the transform's epilogue (NttPassArgs::epi*),
+//     d     = INTT(x_l) * (t^-1 mod q_l)                    one row per tower: the canonical residue of -delta
+//     r_i   = NTT((t mod q_i) * SwitchModulus(d -> q_i))
+//     out_i = (x_i - r_i) * q_l^-1.
+//   SwitchModulus is odd under negation for odd q_l: with h = floor(q_l / 2), v > h holds exactly when q_l - v <= h (v != 0), so the centred
+//   representative of q_l - v is minus that of v and SwitchModulus(q_l - v -> q_i) = -SwitchModulus(v -> q_i) mod q_i (0 maps to 0).  Hence
+//   r_i = -NTT(t * SwitchModulus(delta)) and out_i = (x_i + t * NTT(SwitchModulus(delta))) * q_l^-1 as residues; every step (the one-row
+//   product, the switch, the product by t mod q_i, the transform, the epilogue) yields the canonical residue, so the words are the reference's.
+//   Launches on rings of two passes: the two INTT passes of the dropped limb, the one-row product by t^-1 (kept a launch of its own: it is one
+//   row per tower, against 16 more multiplications per lane and limb inside the prologue), the column pass with prologue mode 2, the row pass
+//   with the epilogue.  Neither the switched tower nor its transform goes to HBM outside `out`.  N = 4096: the stand-alone switch kernel
+//   with the constant t mod q_i, then the single pass with the epilogue.
+// x1 / out1 != null: the two elements of one ciphertext, allocated on their own (batch must be 2): the same launches over both towers.
+static fhe_status mod_reduce_run(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, const ModReduceTabs& tb,
+                                 int evalFormat, uint32_t batch, uint64_t* out, uint64_t* ws, void* st, const uint64_t* x1 = nullptr,
+                                 uint64_t* out1 = nullptr) {
+    const uint32_t l       = sizeQl - 1;
+    const uint32_t lastIdx = limbIdx ? limbIdx[l] : l;
+    uint64_t* last         = ws;                                 // [batch][N]
+    uint64_t* tmp          = last + ((size_t)batch << c->logN);  // [batch][l][N]
+    static const bool noFuse = env_u32("FHE_MOD_REDUCE_UNFUSED", 0) != 0;
+    const bool fused = evalFormat && tb.derived && !noFuse && ntt_epilogue_supported(c);
+    if (x1 && !fused) {  // (small rings, COEFFICIENT towers, foreign tables: element by element)
+        if (fhe_status s = mod_reduce_run(c, x, limbIdx, sizeQl, tb, evalFormat, 1, out, ws, st))
+            return s;
+        return mod_reduce_run(c, x1, limbIdx, sizeQl, tb, evalFormat, 1, out1, ws, st);
+    }
+    const int64_t xDelta = x1 ? x1 - x : 0;
+    if (evalFormat) {  // delta.SetFormat(COEFFICIENT)  :741
+        NttOpts lastRow;
+        lastRow.src.stride = sizeQl, lastRow.src.first = l, lastRow.srcDelta = xDelta;
+        if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
+            return s;
+    }
+    else
+        RT_CHECK(rt::d2d_2d(last, (size_t)8 << c->logN, x + ((size_t)l << c->logN), ((size_t)sizeQl * 8) << c->logN,
+                            (size_t)8 << c->logN, batch, (rt::stream_t)st));
+    if (fhe_status s = elem_run<OP_MUL_CONST>(c, last, last, nullptr, fused ? tb.pos : tb.neg, &lastIdx, 1, batch, st, "fhe_mod_reduce"))  // :742
+        return s;
+    LimbSel sel;
+    if (fhe_status s = make_sel(c, limbIdx, l, &sel, "fhe_mod_reduce"))
+        return s;
+    if (fused) {
+        NttEpilogue epi;
+        epi.mode = 1, epi.split = x1 ? 1 : batch, epi.aStride = sizeQl, epi.aFirst = 0, epi.aDelta = xDelta;
+        epi.A = x, epi.C = tb.B, epi.out0 = out, epi.out1 = x1 ? out1 : out;
+        // (two elements: the transform works in the workspace, its fused store goes to the two output towers)
+        uint64_t* work = x1 ? tmp : out;
+        NttOpts fusedStore;
+        fusedStore.epi = &epi;
+        if (ntt_prologue_supported(c)) {  // every limb from the one row of `last`, times t mod q_i on the way in
+            fusedStore.src.stride = 1, fusedStore.src.first = 0, fusedStore.proSrcLimb = &lastIdx, fusedStore.proC = tb.T;
+            return ntt_run(c, false, last, work, limbIdx, l, batch, st, fusedStore);
+        }
+        // the single pass of N = 4096: SwitchModulus and the product by t mod q_i as a kernel of their own, then the transform with the fused store
+        if (fhe_status s = switch_modulus_run(c, work, sel, l, last, 1, 0, lastIdx, tb.T, batch, st))
+            return s;
+        return ntt_run(c, false, work, work, limbIdx, l, batch, st, fusedStore);
+    }
+    if (fhe_status s = switch_modulus_run(c, tmp, sel, l, last, 1, 0, lastIdx, tb.A, batch, st))  // :749, :752 (t folded into A_i)
+        return s;
+    if (evalFormat)  // :750-751
+        if (fhe_status s = fhe_ntt_fwd(c, tmp, limbIdx, l, batch, st))
+            return s;
+    return elem_run<OP_MUL_CONST_ADD>(c, out, x, tmp, tb.B, limbIdx, l, batch, st, "fhe_mod_reduce", sizeQl, 0);  // :752-753
+}
+// replaces DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755) on towers over the leading limbs, tables derived per (sizeQl, t)
 extern "C" fhe_status fhe_mod_reduce(fhe_ctx* c, const uint64_t* x, uint32_t sizeQl, uint64_t t, int evalFormat,
                                      uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes, void* st) {
     ARG_CHECK(c && x && out && wsv, "fhe_mod_reduce: null argument");
@@ -3100,21 +3278,22 @@ extern "C" fhe_status fhe_mod_reduce(fhe_ctx* c, const uint64_t* x, uint32_t siz
     const uint32_t l  = sizeQl - 1;
     const uint64_t ql = c->q[l];
     ARG_CHECK(t >= 2 && t % ql != 0, "fhe_mod_reduce: t must be invertible modulo the dropped limb");
-    uint64_t* last = (uint64_t*)wsv;                    // [batch][N]
-    uint64_t* tmp  = last + ((size_t)batch << c->logN);  // [batch][l][N]
     std::unique_lock<std::mutex> lock(c->cacheMutex);
     auto it = c->modReduceTabs.find({sizeQl, t});
     if (it == c->modReduceTabs.end()) {
-        std::vector<TwPair> h(2 * (size_t)l + 1);
+        std::vector<TwPair> h(3 * (size_t)l + 2);
         for (uint32_t i = 0; i < l; ++i) {
             const uint64_t qi = c->q[i];
             const uint64_t B  = host::invmod(ql % qi, qi);      // qlInvModq
             const uint64_t A  = host::mulmod(t % qi, B, qi);
             h[i]              = TwPair{A, host::shoup(A, qi)};
             h[l + i]          = TwPair{B, host::shoup(B, qi)};
+            h[2 * (size_t)l + 2 + i] = TwPair{t % qi, host::shoup(t % qi, qi)};  // (t > q_i: its residue)
         }
-        const uint64_t negtInv = (ql - host::invmod(t % ql, ql)) % ql;  // negtInvModq
+        const uint64_t tInv    = host::invmod(t % ql, ql);
+        const uint64_t negtInv = (ql - tInv) % ql;  // negtInvModq
         h[2 * (size_t)l]       = TwPair{negtInv, host::shoup(negtInv, ql)};
+        h[2 * (size_t)l + 1]   = TwPair{tInv, host::shoup(tInv, ql)};
         void* d = nullptr;
         RT_CHECK(rt::dmalloc(&d, h.size() * sizeof(TwPair)));
         c->owned.push_back(d);
@@ -3122,29 +3301,70 @@ extern "C" fhe_status fhe_mod_reduce(fhe_ctx* c, const uint64_t* x, uint32_t siz
         RT_CHECK(rt::sync(nullptr));
         it = c->modReduceTabs.emplace(std::make_pair(sizeQl, t), (TwPair*)d).first;
     }
-    TwPair *dA = it->second, *dB = dA + l, *dN = dA + 2 * (size_t)l;
+    const TwPair* d = it->second;
     lock.unlock();
-    const uint32_t lastIdx = l;
-    if (evalFormat) {  // delta.SetFormat(COEFFICIENT)  :741
-        NttOpts lastRow;
-        lastRow.src.stride = sizeQl, lastRow.src.first = l;
-        if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
-            return s;
+    const ModReduceTabs tb{d, d + l, d + 2 * (size_t)l + 2, d + 2 * (size_t)l, d + 2 * (size_t)l + 1, true};
+    return mod_reduce_run(c, x, nullptr, sizeQl, tb, evalFormat, batch, out, (uint64_t*)wsv, st);
+}
+// the same with the caller's tables over any limbs of the context, as DCRTPoly::ModReduce receives them (t, negtInvModq = -t^-1 mod q_l,
+// qlInvModq[i] = q_l^-1 mod q_i for the sizeQl-1 kept limbs: CryptoParametersBGVRNS::GetNegtInvModq(l) / GetqlInvModq(l)).  Fused exactly
+// when the tables are the ones the library would derive itself (the rule of `negated` in rescale_limbs_run); any other tables run the
+// member's formula with the given values, launch by launch.
+static fhe_status mod_reduce_limbs_run(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t,
+                                       uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint32_t batch, uint64_t* out,
+                                       uint64_t* out1, void* wsv, size_t wsBytes, void* st, const char* who) {
+    ARG_CHECK(c && x && out && wsv && qlInvModq, std::string(who) + ": null argument");
+    ARG_CHECK(sizeQl >= 2 && sizeQl <= (uint32_t)kMaxLimbs, "Removing last element of DCRTPoly renders it invalid.");  // :672-673
+    ARG_CHECK(batch >= 1 && wsBytes >= fhe_rescale_workspace_bytes(c, sizeQl, batch), std::string(who) + ": workspace too small");
+    RT_CHECK(rt::set_device(c->device));
+    const uint32_t l = sizeQl - 1;
+    for (uint32_t i = 0; i < sizeQl; ++i)
+        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, std::string(who) + ": limb index exceeds context size");
+    const uint32_t lastIdx = limbIdx ? limbIdx[l] : l;
+    const uint64_t ql      = c->q[lastIdx];
+    ARG_CHECK(t >= 2 && t % ql != 0, std::string(who) + ": t must be invertible modulo the dropped limb");
+    ARG_CHECK(negtInvModq < ql, std::string(who) + ": negtInvModq is not reduced modulo the dropped limb");
+    const uint64_t tInv = host::invmod(t % ql, ql);
+    bool derived        = negtInvModq == (ql - tInv) % ql;
+    std::vector<uint64_t> vA(l), vT(l);
+    for (uint32_t i = 0; i < l; ++i) {
+        const uint64_t qi = c->q[limbIdx ? limbIdx[i] : i];
+        ARG_CHECK(qlInvModq[i] < qi, std::string(who) + ": qlInvModq is not reduced modulo its limb");
+        derived = derived && qi != ql && qlInvModq[i] == host::invmod(ql % qi, qi);
+        vT[i]   = t % qi;
+        vA[i]   = host::mulmod(vT[i], qlInvModq[i], qi);
     }
-    else
-        RT_CHECK(rt::d2d_2d(last, (size_t)8 << c->logN, x + ((size_t)l << c->logN), ((size_t)sizeQl * 8) << c->logN,
-                            (size_t)8 << c->logN, batch, (rt::stream_t)st));
-    if (fhe_status s = elem_run<OP_MUL_CONST>(c, last, last, nullptr, dN, &lastIdx, 1, batch, st, "fhe_mod_reduce"))  // :742
+    ModReduceTabs tb{};
+    tb.derived = derived;
+    if (fhe_status s = const_tables_trim(c))
         return s;
-    LimbSel sel;
-    if (fhe_status s = make_sel(c, nullptr, l, &sel, "fhe_mod_reduce"))
+    std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
+    if (fhe_status s = const_table(c, limbIdx, vA.data(), l, &tb.A))
         return s;
-    if (fhe_status s = switch_modulus_run(c, tmp, sel, l, last, 1, 0, l, dA, batch, st))  // :749, :752 (t folded into A_i)
+    if (fhe_status s = const_table(c, limbIdx, qlInvModq, l, &tb.B))
         return s;
-    if (evalFormat)  // :750-751
-        if (fhe_status s = fhe_ntt_fwd(c, tmp, nullptr, l, batch, st))
-            return s;
-    return elem_run<OP_MUL_CONST_ADD>(c, out, x, tmp, dB, nullptr, l, batch, st, "fhe_mod_reduce", sizeQl, 0);  // :752-753
+    if (fhe_status s = const_table(c, limbIdx, vT.data(), l, &tb.T))
+        return s;
+    if (fhe_status s = const_table(c, &lastIdx, &negtInvModq, 1, &tb.neg))
+        return s;
+    if (fhe_status s = const_table(c, &lastIdx, &tInv, 1, &tb.pos))
+        return s;
+    return mod_reduce_run(c, x, limbIdx, sizeQl, tb, evalFormat, batch, out, (uint64_t*)wsv, st, x1, out1);
+}
+extern "C" fhe_status fhe_mod_reduce_limbs(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t,
+                                           uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint32_t batch, uint64_t* out,
+                                           void* wsv, size_t wsBytes, void* st) {
+    return mod_reduce_limbs_run(c, x, nullptr, limbIdx, sizeQl, t, negtInvModq, qlInvModq, evalFormat, batch, out, nullptr, wsv, wsBytes, st,
+                                "fhe_mod_reduce_limbs");
+}
+// the two elements of one ciphertext (towers x0, x1 -> out0, out1, each allocated on its own) in the same launches: what
+// LeveledSHEBGVRNS::ModReduceInternalInPlace (bgvrns-leveledshe.cpp:44-75) does element by element; ws of fhe_rescale_workspace_bytes(ctx, sizeQl, 2)
+extern "C" fhe_status fhe_mod_reduce_limbs_pair(fhe_ctx* c, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
+                                                uint64_t t, uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint64_t* out0,
+                                                uint64_t* out1, void* wsv, size_t wsBytes, void* st) {
+    ARG_CHECK(x1 && out1 && x1 != x0 && out1 != out0, "fhe_mod_reduce_limbs_pair: needs two distinct towers");
+    return mod_reduce_limbs_run(c, x0, x1, limbIdx, sizeQl, t, negtInvModq, qlInvModq, evalFormat, 2, out0, out1, wsv, wsBytes, st,
+                                "fhe_mod_reduce_limbs_pair");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -92,8 +92,11 @@ struct NttPassArgs {
     // Optional prologue of a forward transform's first pass (static column kernels only, PRO instances): every limb of a tower
     // is loaded from ONE row of xin (row inFirst of the tower's inStride rows), a COEFFICIENT limb modulo q[proSrcLimb], and
     // brought to the limb's own modulus on the way in (SwitchModulus, mubintvecnat.cpp:109-122) — the `tmp[i] = lastPoly;
-    // tmp[i].SwitchModulus(q_i)` of DropLastElementAndScale (dcrtpoly-impl.h:703-704) never goes to HBM.  0: off.
+    // tmp[i].SwitchModulus(q_i)` of DropLastElementAndScale (dcrtpoly-impl.h:703-704) never goes to HBM.  0: off, 1: the switch alone,
+    // 2: the switched residue times proC[row of the tower] (one Shoup pair per tower row, like epiC), canonical — the
+    // `t * SwitchModulus(delta)` of DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:749-752) with proC = t mod q_i.
     uint32_t proMode, proSrcLimb;
+    const TwPair* proC;
     // != 0: consecutive towers of the pass's first load / of the epilogue's operand A are this many WORDS apart (signed: towers
     // allocated on their own — the two elements of a ciphertext); overrides inStride / epiAStride (static kernels only)
     int64_t inDelta, epiADelta;

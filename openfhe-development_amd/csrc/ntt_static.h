@@ -559,11 +559,12 @@ FHE_HD void lane_geom_s(uint32_t t, uint32_t S, uint32_t& Ib, uint32_t& jrel, ui
 // Both exist for the fused polynomial product (poly_mul kernels below): a forward row pass whose last step and an inverse
 // row pass whose first step both act on tile bit 0 hold the same 16 consecutive residues per lane.
 // PRO: the first load takes every limb of a tower from one COEFFICIENT row modulo another limb's modulus and switches it to the
-// limb's own modulus (NttPassArgs::proMode) — forward column passes only.
+// limb's own modulus (NttPassArgs::proMode) — forward column passes only.  PRO = 2 (proMode 2) also multiplies the switched residue by the
+// tower row's constant NttPassArgs::proC (BGV ModReduce: t mod q_i) and leaves it canonical, which is what the first stage expects of a load.
 // HAND: the inverse 4-stage column pass does the twiddle products of the preceding row pass's last stage (hand_mul16) on its way in, for the
 // tiles whose columns have coefficient bit T2 - 1 set.  Its partner is ntt_row8.h's batched kernel with HAND;
 // no other kernel reads or writes that intermediate tower.
-template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool RAWIN = false, bool RAWOUT = false, bool PRO = false, bool HAND = false>
+template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool RAWIN = false, bool RAWOUT = false, int PRO = 0, bool HAND = false>
 FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, uint64_t (&r)[16]) {
     using P = SPlan<LA, INV, T>;
     static_assert(!HAND || (LA && INV && T == 4 && MODE == 1 && !EPI && !PRO), "hand-over exists for the plain inverse 4-stage column pass only");
@@ -694,6 +695,13 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
 #pragma unroll
         for (int k = 0; k < 16; ++k)
             v[k] = switch_modulus_word(v[k], qs, halfQs, q);
+        if constexpr (PRO == 2) {  // SwitchModulus leaves canonical residues; so does the product (ModMulFastConst, ubintnat.h:1464-1469)
+            const uint64_t* cw = reinterpret_cast<const uint64_t*>(a.proC + rit);
+            const uint64_t cW = FHE_ULOAD64(cw, 0), cWp = FHE_ULOAD64(cw, 1);
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                v[k] = csub(mul_shoup_lazy_nq(v[k], cW, cWp, nq), q);
+        }
     };
 
 #define FHE_SHARED_TW_TO_LDS()                                             \
@@ -804,13 +812,13 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
     }
 }
 
-template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool PRO = false, bool HAND = false>
+template <bool LA, bool INV, int T, int MODE, bool EPI = false, int PRO = 0, bool HAND = false>
 FHE_DEV void ntt_static_body(const NttPassArgs& a, uint32_t bid, uint64_t* lds) {
     uint64_t r[16];
     ntt_static_core<LA, INV, T, MODE, EPI, false, false, PRO, HAND>(a, bid, lds, r);
 }
 
-template <bool LA, bool INV, int T, int MODE, bool EPI = false, bool PRO = false, bool HAND = false>
+template <bool LA, bool INV, int T, int MODE, bool EPI = false, int PRO = 0, bool HAND = false>
 FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ntt_static_kernel(const NttPassArgs a) {
     // a single-step pass without staging (the 4-stage column pass) never touches LDS: do not reserve any, so that
     // more workgroups fit on a CU

@@ -159,6 +159,14 @@ class Lib:
         S("fhe_mem_info", C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
         S("fhe_lincomb", C.c_int, [vp, vp, C.POINTER(vp), u64p, u32, u32p, u32, u32, C.c_int, vp])
         S("fhe_mod_reduce", C.c_int, [vp, vp, u32, u64, C.c_int, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_mod_reduce_limbs", C.c_int, [vp, vp, u32p, u32, u64, u64, u64p, C.c_int, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_mod_reduce_limbs_pair", C.c_int, [vp, vp, vp, u32p, u32, u64, u64, u64p, C.c_int, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bgv_keyswitch_hybrid", C.c_int, [vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bgv_keyswitch_hybrid_acc", C.c_int, [vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bgv_eval_mult", C.c_int, [vp, vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bgv_ks_fast_keyswitch", C.c_int, [vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bgv_eval_fast_rotation", C.c_int, [vp, vp, vp, vp, u32, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bgv_eval_automorphism", C.c_int, [vp, vp, vp, vp, u32, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
         f64p = C.POINTER(C.c_double)
         S("fhe_sr_plan_create", C.c_int, [vp, u32, u32p, u32, u64p, f64p, C.POINTER(vp)])
         S("fhe_sr_plan_destroy", None, [vp])
@@ -668,24 +676,47 @@ class KeySwitchPlan:
             self._ws_bytes = need
         return self._ws, self._ws_bytes
 
-    def KeySwitchCore(self, c, stream=None):  # keyswitch-hybrid.cpp:308-312
+    # t = 0: CKKS / BFV; t >= 2: the BGV form with the plaintext modulus t (the fhe_bgv_* twin of the entry point)
+    def KeySwitchCore(self, c, stream=None, t=0):  # keyswitch-hybrid.cpp:308-312
         ws, wsb = self.workspace(c.n_limbs, c.batch)
         o0, o1 = c.like(), c.like()
-        self.ctx.lib.check(self.ctx.lib.L.fhe_keyswitch_hybrid(self.h, self.key, c.ptr, c.n_limbs, c.batch, o0.ptr,
-                                                               o1.ptr, ws, wsb, stream))
+        L = self.ctx.lib.L
+        if t:
+            self.ctx.lib.check(L.fhe_bgv_keyswitch_hybrid(self.h, self.key, c.ptr, c.n_limbs, t, c.batch, o0.ptr, o1.ptr, ws, wsb, stream))
+        else:
+            self.ctx.lib.check(L.fhe_keyswitch_hybrid(self.h, self.key, c.ptr, c.n_limbs, c.batch, o0.ptr, o1.ptr, ws, wsb, stream))
         return o0, o1
 
-    def KeySwitchCoreAcc(self, c, acc0, acc1, stream=None):  # base-leveledshe.cpp:207-211: acc += KeySwitchCore(c), in place
+    def KeySwitchCoreAcc(self, c, acc0, acc1, stream=None, t=0):  # base-leveledshe.cpp:207-211: acc += KeySwitchCore(c), in place
         ws, wsb = self.workspace(c.n_limbs, c.batch)
-        self.ctx.lib.check(self.ctx.lib.L.fhe_keyswitch_hybrid_acc(self.h, self.key, c.ptr, c.n_limbs, c.batch, acc0.ptr, acc1.ptr, ws, wsb,
-                                                                   stream))
+        L = self.ctx.lib.L
+        if t:
+            self.ctx.lib.check(L.fhe_bgv_keyswitch_hybrid_acc(self.h, self.key, c.ptr, c.n_limbs, t, c.batch, acc0.ptr, acc1.ptr, ws, wsb,
+                                                              stream))
+        else:
+            self.ctx.lib.check(L.fhe_keyswitch_hybrid_acc(self.h, self.key, c.ptr, c.n_limbs, c.batch, acc0.ptr, acc1.ptr, ws, wsb, stream))
 
-    def EvalMult(self, a0, a1, b0, b1, stream=None):  # base-leveledshe.cpp:201-214
+    def EvalMult(self, a0, a1, b0, b1, stream=None, t=0):  # base-leveledshe.cpp:201-214
         ws, wsb = self.workspace(a0.n_limbs, a0.batch)
         c0, c1 = a0.like(), a0.like()
-        self.ctx.lib.check(self.ctx.lib.L.fhe_ckks_eval_mult(self.h, self.key, a0.ptr, a1.ptr, b0.ptr, b1.ptr,
-                                                             a0.n_limbs, a0.batch, c0.ptr, c1.ptr, ws, wsb, stream))
+        L = self.ctx.lib.L
+        if t:
+            self.ctx.lib.check(L.fhe_bgv_eval_mult(self.h, self.key, a0.ptr, a1.ptr, b0.ptr, b1.ptr, a0.n_limbs, t, a0.batch, c0.ptr,
+                                                   c1.ptr, ws, wsb, stream))
+        else:
+            self.ctx.lib.check(L.fhe_ckks_eval_mult(self.h, self.key, a0.ptr, a1.ptr, b0.ptr, b1.ptr, a0.n_limbs, a0.batch, c0.ptr,
+                                                    c1.ptr, ws, wsb, stream))
         return c0, c1
+
+    def FastKeySwitch(self, key, c1, stream=None, t=0):  # keyswitch-hybrid.cpp:381-400 on the digits EvalFastRotationPrecompute(c1) left
+        ws, wsb = self.workspace(c1.n_limbs, c1.batch)
+        o0, o1 = c1.like(), c1.like()
+        L = self.ctx.lib.L
+        if t:
+            self.ctx.lib.check(L.fhe_bgv_ks_fast_keyswitch(self.h, key, c1.ptr, c1.n_limbs, t, c1.batch, o0.ptr, o1.ptr, ws, wsb, stream))
+        else:
+            self.ctx.lib.check(L.fhe_ks_fast_keyswitch(self.h, key, c1.ptr, c1.n_limbs, c1.batch, o0.ptr, o1.ptr, ws, wsb, stream))
+        return o0, o1
 
     def make_key(self, keyB, keyA):
         """upload an additional evaluation key (e.g. a rotation key); returns the handle"""
@@ -700,11 +731,16 @@ class KeySwitchPlan:
         ws, wsb = self.workspace(c1.n_limbs, c1.batch)
         self.ctx.lib.check(self.ctx.lib.L.fhe_ks_precompute(self.h, c1.ptr, c1.n_limbs, c1.batch, ws, wsb, stream))
 
-    def EvalFastRotation(self, key, c0, c1, k, stream=None):  # base-leveledshe.cpp:432-463 (digits already in ws)
+    def EvalFastRotation(self, key, c0, c1, k, stream=None, t=0):  # base-leveledshe.cpp:432-463 (digits already in ws)
         ws, wsb = self.workspace(c0.n_limbs, c0.batch)
         o0, o1 = c0.like(), c0.like()
-        self.ctx.lib.check(self.ctx.lib.L.fhe_eval_fast_rotation(self.h, key, c0.ptr, c1.ptr, k, c0.n_limbs, c0.batch,
-                                                                 o0.ptr, o1.ptr, ws, wsb, stream))
+        L = self.ctx.lib.L
+        if t:
+            self.ctx.lib.check(L.fhe_bgv_eval_fast_rotation(self.h, key, c0.ptr, c1.ptr, k, c0.n_limbs, t, c0.batch, o0.ptr, o1.ptr, ws,
+                                                            wsb, stream))
+        else:
+            self.ctx.lib.check(L.fhe_eval_fast_rotation(self.h, key, c0.ptr, c1.ptr, k, c0.n_limbs, c0.batch, o0.ptr, o1.ptr, ws, wsb,
+                                                        stream))
         return o0, o1
 
     def ext_limbs(self, sizeQl):
@@ -767,11 +803,16 @@ class KeySwitchPlan:
         diag = [[A[bStep * j + i] if bStep * j + i < slots else None for i in range(bStep)] for j in range(gStep)]
         return self.BsgsTransform(c0, c1, in_rot, out_rot, diag, stream=stream)
 
-    def EvalAutomorphism(self, key, c0, c1, k, stream=None):  # base-leveledshe.cpp:381-422
+    def EvalAutomorphism(self, key, c0, c1, k, stream=None, t=0):  # base-leveledshe.cpp:381-422
         ws, wsb = self.workspace(c0.n_limbs, c0.batch)
         o0, o1 = c0.like(), c0.like()
-        self.ctx.lib.check(self.ctx.lib.L.fhe_eval_automorphism(self.h, key, c0.ptr, c1.ptr, k, c0.n_limbs, c0.batch,
-                                                                o0.ptr, o1.ptr, ws, wsb, stream))
+        L = self.ctx.lib.L
+        if t:
+            self.ctx.lib.check(L.fhe_bgv_eval_automorphism(self.h, key, c0.ptr, c1.ptr, k, c0.n_limbs, t, c0.batch, o0.ptr, o1.ptr, ws,
+                                                           wsb, stream))
+        else:
+            self.ctx.lib.check(L.fhe_eval_automorphism(self.h, key, c0.ptr, c1.ptr, k, c0.n_limbs, c0.batch, o0.ptr, o1.ptr, ws, wsb,
+                                                       stream))
         return o0, o1
 
     def ApproxModDown(self, x, sizeQl, t=0, stream=None):  # dcrtpoly-impl.h:966-1005 (t > 0: the BGV form)
@@ -947,6 +988,41 @@ def mod_reduce(ctx, x, t, stream=None):
     ctx.sync(stream)
     ctx.free(ws)
     return out
+
+
+def mod_reduce_limbs(ctx, x, t, negt_inv_modq, ql_inv_modq, stream=None):
+    """DCRTPoly::ModReduce on a Tower over ANY limbs of the context (x.limb_idx; its last limb is dropped) with the caller's tables
+    negtInvModq / qlInvModq (dcrtpoly-impl.h:736-738): fhe_mod_reduce_limbs, the entry the DCRTPoly backend calls."""
+    sizeQl = x.n_limbs
+    need = ctx.lib.L.fhe_rescale_workspace_bytes(ctx.h, sizeQl, x.batch)
+    ws = ctx.malloc(need)
+    kept = None if x.limb_idx is None else x.limb_idx[:sizeQl - 1]
+    out = ctx.empty(x.batch, sizeQl - 1, kept, x.fmt)
+    b = np.ascontiguousarray(ql_inv_modq, dtype=np.uint64)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_mod_reduce_limbs(ctx.h, x.ptr, x._li(), sizeQl, t, negt_inv_modq, b.ctypes.data_as(u64p),
+                                                     1 if x.fmt == EVALUATION else 0, x.batch, out.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
+    return out
+
+
+def mod_reduce_pair(ctx, x0, x1, t, negt_inv_modq, ql_inv_modq, stream=None):
+    """the two elements of a ciphertext (two Towers of batch 1, allocated on their own) through fhe_mod_reduce_limbs_pair"""
+    sizeQl = x0.n_limbs
+    need = ctx.lib.L.fhe_rescale_workspace_bytes(ctx.h, sizeQl, 2)
+    ws = ctx.malloc(need)
+    kept = None if x0.limb_idx is None else x0.limb_idx[:sizeQl - 1]
+    o0, o1 = ctx.empty(1, sizeQl - 1, kept, x0.fmt), ctx.empty(1, sizeQl - 1, kept, x0.fmt)
+    b = np.ascontiguousarray(ql_inv_modq, dtype=np.uint64)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_mod_reduce_limbs_pair(ctx.h, x0.ptr, x1.ptr, x0._li(), sizeQl, t, negt_inv_modq, b.ctypes.data_as(u64p),
+                                                          1 if x0.fmt == EVALUATION else 0, o0.ptr, o1.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
+    return o0, o1
 
 
 def scale_and_round_native(ctx, x, t, tab_modt, frac, tab_bmodt=None, bfrac=None, stream=None):

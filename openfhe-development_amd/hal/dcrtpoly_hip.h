@@ -192,6 +192,44 @@ public:
         check(s);
         *this = std::move(out);
     }
+    // ... over any limbs of the context with the caller's tables, as DCRTPoly::ModReduce receives them (dcrtpoly-impl.h:736-738):
+    // negtInvModq = -t^-1 mod q_l, qlInvModq[i] = q_l^-1 mod q_i for the limbs that stay (fhe_mod_reduce_limbs)
+    void ModReduce(uint64_t t, uint64_t negtInvModq, const std::vector<uint64_t>& qlInvModq) {
+        if (qlInvModq.size() + 1 < m_limbs)
+            throw Error("ModReduce: one qlInvModq entry per remaining limb expected");
+        std::vector<uint32_t> kept(m_idx.begin(), m_idx.empty() ? m_idx.end() : m_idx.end() - 1);
+        DCRTPolyHip out(m_params, m_limbs - 1, m_format, m_batch, kept);
+        size_t wsb = fhe_rescale_workspace_bytes(m_params->ctx(), m_limbs, m_batch);
+        void* ws   = nullptr;
+        check(fhe_malloc(m_params->ctx(), wsb, &ws));
+        fhe_status s = fhe_mod_reduce_limbs(m_params->ctx(), m_data, idx(), m_limbs, t, negtInvModq, qlInvModq.data(), m_format == EVALUATION,
+                                            m_batch, out.m_data, ws, wsb, nullptr);
+        fhe_stream_sync(m_params->ctx(), nullptr);
+        fhe_free(m_params->ctx(), ws);
+        check(s);
+        *this = std::move(out);
+    }
+    // ... of the two elements of one ciphertext (batch 1 each, allocated on their own) in the same launches
+    // (LeveledSHEBGVRNS::ModReduceInternalInPlace, bgvrns-leveledshe.cpp:44-75; fhe_mod_reduce_limbs_pair)
+    static void ModReducePair(DCRTPolyHip& x0, DCRTPolyHip& x1, uint64_t t, uint64_t negtInvModq, const std::vector<uint64_t>& qlInvModq) {
+        if (x0.m_batch != 1 || x1.m_batch != 1 || x0.m_limbs != x1.m_limbs || x0.m_format != x1.m_format || x0.m_idx != x1.m_idx)
+            throw Error("ModReducePair: two single towers over the same limbs in the same format expected");
+        if (qlInvModq.size() + 1 < x0.m_limbs)
+            throw Error("ModReduce: one qlInvModq entry per remaining limb expected");
+        const auto& P = x0.m_params;
+        std::vector<uint32_t> kept(x0.m_idx.begin(), x0.m_idx.empty() ? x0.m_idx.end() : x0.m_idx.end() - 1);
+        DCRTPolyHip o0(P, x0.m_limbs - 1, x0.m_format, 1, kept), o1(P, x0.m_limbs - 1, x0.m_format, 1, kept);
+        size_t wsb = fhe_rescale_workspace_bytes(P->ctx(), x0.m_limbs, 2);
+        void* ws   = nullptr;
+        check(fhe_malloc(P->ctx(), wsb, &ws));
+        fhe_status s = fhe_mod_reduce_limbs_pair(P->ctx(), x0.m_data, x1.m_data, x0.idx(), x0.m_limbs, t, negtInvModq, qlInvModq.data(),
+                                                 x0.m_format == EVALUATION, o0.m_data, o1.m_data, ws, wsb, nullptr);
+        fhe_stream_sync(P->ctx(), nullptr);
+        fhe_free(P->ctx(), ws);
+        check(s);
+        x0 = std::move(o0);
+        x1 = std::move(o1);
+    }
     // ExpandCRTBasis / ExpandCRTBasisReverseOrder to this basis + the context limbs `extra` (dcrtpoly-impl.h:1088-1148)
     DCRTPolyHip ExpandCRTBasis(const std::vector<uint32_t>& extra, Format resultFormat, bool reverseOrder = false) const {
         std::vector<uint32_t> src = m_idx;
@@ -286,19 +324,33 @@ public:
         m_key = nullptr;
         check(fhe_ks_key_upload(m_plan, keyB.data(), keyA.data(), &m_key));
     }
+    // t = 0: CKKS / BFV; t >= 2: BGV, ApproxModDown with the plaintext modulus (the fhe_bgv_* twin of the entry point)
     // KeySwitchCore(a, evalKey)
-    std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchCore(const DCRTPolyHip& a) {
-        DCRTPolyHip o0(m_params, a.GetNumOfElements(), EVALUATION, a.GetBatch()), o1(m_params, a.GetNumOfElements(), EVALUATION, a.GetBatch());
-        reserve(a.GetNumOfElements(), a.GetBatch());
-        check(fhe_keyswitch_hybrid(m_plan, m_key, a.data(), a.GetNumOfElements(), a.GetBatch(), o0.data(), o1.data(), m_ws, m_wsBytes, nullptr));
+    std::pair<DCRTPolyHip, DCRTPolyHip> KeySwitchCore(const DCRTPolyHip& a, uint64_t t = 0) {
+        const uint32_t sizeQl = a.GetNumOfElements(), batch = a.GetBatch();
+        DCRTPolyHip o0(m_params, sizeQl, EVALUATION, batch), o1(m_params, sizeQl, EVALUATION, batch);
+        reserve(sizeQl, batch);
+        check(t ? fhe_bgv_keyswitch_hybrid(m_plan, m_key, a.data(), sizeQl, t, batch, o0.data(), o1.data(), m_ws, m_wsBytes, nullptr)
+                : fhe_keyswitch_hybrid(m_plan, m_key, a.data(), sizeQl, batch, o0.data(), o1.data(), m_ws, m_wsBytes, nullptr));
         return {std::move(o0), std::move(o1)};
     }
+    // acc += KeySwitchCore(a), in place (base-leveledshe.cpp:207-211)
+    void KeySwitchCoreAcc(const DCRTPolyHip& a, DCRTPolyHip& acc0, DCRTPolyHip& acc1, uint64_t t = 0) {
+        const uint32_t sizeQl = a.GetNumOfElements(), batch = a.GetBatch();
+        reserve(sizeQl, batch);
+        check(t ? fhe_bgv_keyswitch_hybrid_acc(m_plan, m_key, a.data(), sizeQl, t, batch, acc0.data(), acc1.data(), m_ws, m_wsBytes, nullptr)
+                : fhe_keyswitch_hybrid_acc(m_plan, m_key, a.data(), sizeQl, batch, acc0.data(), acc1.data(), m_ws, m_wsBytes, nullptr));
+    }
     // LeveledSHEBase::EvalMult(ct1, ct2, evalKey) for 2-element ciphertexts (base-leveledshe.cpp:201-214)
-    std::pair<DCRTPolyHip, DCRTPolyHip> EvalMult(const DCRTPolyHip& a0, const DCRTPolyHip& a1, const DCRTPolyHip& b0, const DCRTPolyHip& b1) {
-        DCRTPolyHip c0(m_params, a0.GetNumOfElements(), EVALUATION, a0.GetBatch()), c1(m_params, a0.GetNumOfElements(), EVALUATION, a0.GetBatch());
-        reserve(a0.GetNumOfElements(), a0.GetBatch());
-        check(fhe_ckks_eval_mult(m_plan, m_key, a0.data(), a1.data(), b0.data(), b1.data(), a0.GetNumOfElements(), a0.GetBatch(),
-                                 c0.data(), c1.data(), m_ws, m_wsBytes, nullptr));
+    std::pair<DCRTPolyHip, DCRTPolyHip> EvalMult(const DCRTPolyHip& a0, const DCRTPolyHip& a1, const DCRTPolyHip& b0, const DCRTPolyHip& b1,
+                                                 uint64_t t = 0) {
+        const uint32_t sizeQl = a0.GetNumOfElements(), batch = a0.GetBatch();
+        DCRTPolyHip c0(m_params, sizeQl, EVALUATION, batch), c1(m_params, sizeQl, EVALUATION, batch);
+        reserve(sizeQl, batch);
+        check(t ? fhe_bgv_eval_mult(m_plan, m_key, a0.data(), a1.data(), b0.data(), b1.data(), sizeQl, t, batch, c0.data(), c1.data(), m_ws,
+                                    m_wsBytes, nullptr)
+                : fhe_ckks_eval_mult(m_plan, m_key, a0.data(), a1.data(), b0.data(), b1.data(), sizeQl, batch, c0.data(), c1.data(), m_ws,
+                                     m_wsBytes, nullptr));
         return {std::move(c0), std::move(c1)};
     }
 
@@ -325,15 +377,17 @@ public:
         return {std::move(o0), std::move(o1)};
     }
     // LeveledSHEBase::EvalAutomorphism / EvalRotate (base-leveledshe.cpp:381-422) with the key set by SetRotationKey
-    std::pair<DCRTPolyHip, DCRTPolyHip> EvalRotate(const DCRTPolyHip& c0, const DCRTPolyHip& c1, int32_t index) {
+    std::pair<DCRTPolyHip, DCRTPolyHip> EvalRotate(const DCRTPolyHip& c0, const DCRTPolyHip& c1, int32_t index, uint64_t t = 0) {
         auto it = m_rot.find(index);
         if (it == m_rot.end())
             throw Error("EvalRotate: no rotation key for index " + std::to_string(index));
         const uint32_t sizeQl = c0.GetNumOfElements(), batch = c0.GetBatch();
         DCRTPolyHip o0(m_params, sizeQl, EVALUATION, batch), o1(m_params, sizeQl, EVALUATION, batch);
         reserve(sizeQl, batch);
-        check(fhe_eval_automorphism(m_plan, it->second.second, c0.data(), c1.data(), it->second.first, sizeQl, batch, o0.data(),
-                                    o1.data(), m_ws, m_wsBytes, nullptr));
+        check(t ? fhe_bgv_eval_automorphism(m_plan, it->second.second, c0.data(), c1.data(), it->second.first, sizeQl, t, batch, o0.data(),
+                                            o1.data(), m_ws, m_wsBytes, nullptr)
+                : fhe_eval_automorphism(m_plan, it->second.second, c0.data(), c1.data(), it->second.first, sizeQl, batch, o0.data(),
+                                        o1.data(), m_ws, m_wsBytes, nullptr));
         return {std::move(o0), std::move(o1)};
     }
     // hoisted rotations: EvalFastRotationPrecompute once (base-leveledshe.cpp:425-430), then EvalFastRotation per index
@@ -342,14 +396,27 @@ public:
         reserve(c1.GetNumOfElements(), c1.GetBatch());
         check(fhe_ks_precompute(m_plan, c1.data(), c1.GetNumOfElements(), c1.GetBatch(), m_ws, m_wsBytes, nullptr));
     }
-    std::pair<DCRTPolyHip, DCRTPolyHip> EvalFastRotation(const DCRTPolyHip& c0, const DCRTPolyHip& c1, int32_t index) {
+    std::pair<DCRTPolyHip, DCRTPolyHip> EvalFastRotation(const DCRTPolyHip& c0, const DCRTPolyHip& c1, int32_t index, uint64_t t = 0) {
         auto it = m_rot.find(index);
         if (it == m_rot.end())
             throw Error("EvalFastRotation: no rotation key for index " + std::to_string(index));
         const uint32_t sizeQl = c0.GetNumOfElements(), batch = c0.GetBatch();
         DCRTPolyHip o0(m_params, sizeQl, EVALUATION, batch), o1(m_params, sizeQl, EVALUATION, batch);
-        check(fhe_eval_fast_rotation(m_plan, it->second.second, c0.data(), c1.data(), it->second.first, sizeQl, batch, o0.data(),
-                                     o1.data(), m_ws, m_wsBytes, nullptr));
+        check(t ? fhe_bgv_eval_fast_rotation(m_plan, it->second.second, c0.data(), c1.data(), it->second.first, sizeQl, t, batch, o0.data(),
+                                             o1.data(), m_ws, m_wsBytes, nullptr)
+                : fhe_eval_fast_rotation(m_plan, it->second.second, c0.data(), c1.data(), it->second.first, sizeQl, batch, o0.data(),
+                                         o1.data(), m_ws, m_wsBytes, nullptr));
+        return {std::move(o0), std::move(o1)};
+    }
+    // EvalFastKeySwitchCore (keyswitch-hybrid.cpp:381-400) with the rotation key of `index` on the digits EvalFastRotationPrecompute left
+    std::pair<DCRTPolyHip, DCRTPolyHip> FastKeySwitch(const DCRTPolyHip& c1, int32_t index, uint64_t t = 0) {
+        auto it = m_rot.find(index);
+        if (it == m_rot.end())
+            throw Error("FastKeySwitch: no rotation key for index " + std::to_string(index));
+        const uint32_t sizeQl = c1.GetNumOfElements(), batch = c1.GetBatch();
+        DCRTPolyHip o0(m_params, sizeQl, EVALUATION, batch), o1(m_params, sizeQl, EVALUATION, batch);
+        check(t ? fhe_bgv_ks_fast_keyswitch(m_plan, it->second.second, c1.data(), sizeQl, t, batch, o0.data(), o1.data(), m_ws, m_wsBytes, nullptr)
+                : fhe_ks_fast_keyswitch(m_plan, it->second.second, c1.data(), sizeQl, batch, o0.data(), o1.data(), m_ws, m_wsBytes, nullptr));
         return {std::move(o0), std::move(o1)};
     }
     uint32_t AutomorphismIndex(int32_t index) const { return m_rot.at(index).first; }

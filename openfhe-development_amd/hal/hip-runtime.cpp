@@ -170,7 +170,8 @@ Runtime* build() {
                   FHE_SYM(crt_decompose, fhe_crt_decompose) && FHE_SYM(rescale_limbs, fhe_rescale_limbs) &&
                   FHE_SYM(event_create, fhe_event_create) && FHE_SYM(event_record, fhe_event_record) && FHE_SYM(stream_wait_event, fhe_stream_wait_event) &&
                   FHE_SYM(event_destroy, fhe_event_destroy) && FHE_SYM(sample_uniform, fhe_sample_uniform) && FHE_SYM(sample_gaussian, fhe_sample_gaussian) && FHE_SYM(sample_ternary, fhe_sample_ternary) &&
-                  FHE_SYM(rescale_limbs_pair, fhe_rescale_limbs_pair) && FHE_SYM(add_pair, fhe_add_pair) && FHE_SYM(sub_pair, fhe_sub_pair) &&
+                  FHE_SYM(rescale_limbs_pair, fhe_rescale_limbs_pair) && FHE_SYM(mod_reduce_limbs, fhe_mod_reduce_limbs) &&
+                  FHE_SYM(add_pair, fhe_add_pair) && FHE_SYM(sub_pair, fhe_sub_pair) &&
                   FHE_SYM(mul_const_pair, fhe_mul_const_pair) && FHE_SYM(lincomb, fhe_lincomb) && FHE_SYM(mem_info, fhe_mem_info) &&
                   FHE_SYM(rescale_workspace_bytes, fhe_rescale_workspace_bytes) && FHE_SYM(conv_create_custom, fhe_conv_create_custom) &&
                   FHE_SYM(approx_switch_basis, fhe_approx_switch_basis) && FHE_SYM(switch_basis_exact, fhe_switch_basis_exact) &&

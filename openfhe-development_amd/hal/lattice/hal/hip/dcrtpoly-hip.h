@@ -2187,31 +2187,23 @@ private:
         if (!OnDevice(&r))
             return false;
         const size_t N          = m_h.GetParams()->GetRingDimension();
-        const uint32_t l        = L - 1;
-        const uint32_t lastLimb = r.idx[0][l];
-        const bool eval         = m_h.GetFormat() == Format::EVALUATION;
-        std::vector<uint32_t> idx(r.idx[0].begin(), r.idx[0].begin() + l);
-        std::vector<uint64_t> tq(l, t.ConvertToInt<uint64_t>()), qi(l);
+        const uint32_t l = L - 1;
+        const bool eval  = m_h.GetFormat() == Format::EVALUATION;
+        std::vector<uint64_t> qi(l);
         for (uint32_t i = 0; i < l; ++i)
             qi[i] = qlInvModq[i].ConvertToInt<uint64_t>();
-        const uint64_t nt = negtInvModq.ConvertToInt<uint64_t>();
-        const auto& A     = hiprt::api();
+        // the whole member is ONE library call with the caller's tables (fhe_mod_reduce_limbs): with the reference's own tables an
+        // EVALUATION tower on a ring of static passes takes the fused form (the switched tower and its transform never go to HBM),
+        // everything else the member launch by launch
+        const auto& A = hiprt::api();
         hiprt::Op op;
         const uint64_t* self = op.R(m_d);
-        auto delta           = hiprt::Alloc(N);
+        const size_t wsBytes = A.rescale_workspace_bytes(r.ctx, L, 1);
+        auto ws              = hiprt::Alloc(wsBytes / 8);
         auto tmp             = hiprt::Alloc((size_t)l * N);
-        uint64_t *dl = op.W(delta), *tp = op.W(tmp);
-        if (eval)
-            hiprt::Check(A.ntt_inv_oop(r.ctx, self + (size_t)l * N, dl, &lastLimb, 1, 1, op.s), "ModReduce");
-        else
-            hiprt::D2D(op, dl, self + (size_t)l * N, N * 8, "ModReduce");
-        hiprt::Check(A.mul_const(r.ctx, dl, dl, &nt, &lastLimb, 1, 1, op.s), "ModReduce");
-        hiprt::Check(A.switch_modulus(r.ctx, tp, idx.data(), l, dl, 1, 0, lastLimb, 1, op.s), "ModReduce");
-        if (eval)
-            hiprt::Check(A.ntt_fwd(r.ctx, tp, idx.data(), l, 1, op.s), "ModReduce");
-        hiprt::Check(A.mul_const(r.ctx, tp, tp, tq.data(), idx.data(), l, 1, op.s), "ModReduce");
-        hiprt::Check(A.add(r.ctx, tp, self, tp, idx.data(), l, 1, op.s), "ModReduce");
-        hiprt::Check(A.mul_const(r.ctx, tp, tp, qi.data(), idx.data(), l, 1, op.s), "ModReduce");
+        hiprt::Check(A.mod_reduce_limbs(r.ctx, self, r.idx[0].data(), L, t.ConvertToInt<uint64_t>(), negtInvModq.ConvertToInt<uint64_t>(),
+                                        qi.data(), eval ? 1 : 0, 1, op.W(tmp), op.W(ws, false), wsBytes, op.s),
+                     "ModReduce");
         m_d = std::move(tmp);
         hiprt::CountDevice();
         DeviceIsNewer(m_h.GetFormat());

@@ -67,6 +67,7 @@ struct Api {
     decltype(&fhe_sample_ternary_blake2) sample_ternary_blake2;
     decltype(&fhe_rescale_limbs) rescale_limbs;
     decltype(&fhe_rescale_limbs_pair) rescale_limbs_pair;
+    decltype(&fhe_mod_reduce_limbs) mod_reduce_limbs;
     decltype(&fhe_add_pair) add_pair;
     decltype(&fhe_sub_pair) sub_pair;
     decltype(&fhe_mul_const_pair) mul_const_pair;
