@@ -426,6 +426,40 @@ fhe_status fhe_rescale_limbs(fhe_ctx* ctx, const uint64_t* x, const uint32_t* li
 fhe_status fhe_rescale_limbs_pair(fhe_ctx* ctx, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
                                   const uint64_t* QlQlInvModqlDivqlModq, const uint64_t* qlInvModq, uint64_t* out0, uint64_t* out1,
                                   void* ws, size_t wsBytes, void* stream);
+/* ---- CKKS rescale by several limbs in one pass (composite scaling) ---------------------------------------------------
+ * Replaces the loop of LeveledSHECKKSRNS::ModReduceInternalInPlace(ct, levels) (ckksrns-leveledshe.cpp:172-191: DropLastElementAndScale
+ * `levels` times on every element; levels = compositeDegree under COMPOSITESCALINGAUTO / COMPOSITESCALINGMANUAL), optionally with the scalar
+ * product in front and the level drop behind it that AdjustLevelsAndDepthInPlace (ckksrns-leveledshe.cpp:600-730) adds:
+ *   x[batch][sizeQl][N] EVALUATION -> out[batch][nOut][N], 1 <= nOut <= sizeQl - levels;
+ *   scale: NULL, or host residues scale[sizeQl] of the integer of EvalMultCoreInPlace(ct, double) as the caller computed it: every limb is
+ *          multiplied by its residue first;
+ *   nOut < sizeQl - levels: the LevelReduceInternalInPlace that follows -- those limbs are not produced.
+ * The words are those of the loop.  On a ring of two static passes (N >= 8192) with the reference's own tables a call of levels <= 4 is five
+ * launches whatever levels is; more levels run in chunks of at most 4; smaller rings, other tables, a zero scale residue and
+ * FHE_RESCALE_UNFUSED=1 run the member step by step.  levels == 1 without scale and with nOut == sizeQl - 1 is fhe_rescale itself.
+ * Errors (nothing is enqueued): a null argument, levels == 0 or levels >= sizeQl, nOut out of range, a limb index outside the context, a
+ * table or scale entry that is not reduced modulo its limb, a workspace below fhe_rescale_multi_workspace_bytes, out aliasing x. */
+size_t     fhe_rescale_multi_workspace_bytes(const fhe_ctx* ctx, uint32_t sizeQl, uint32_t levels, uint32_t batch);
+/* tables of CryptoParametersCKKSRNS (ckksrns-cryptoparameters.cpp:60-81) computed inside; context limbs [0, sizeQl) */
+fhe_status fhe_rescale_multi(fhe_ctx* ctx, const uint64_t* x, uint32_t sizeQl, uint32_t levels, uint32_t nOut, const uint64_t* scale,
+                             uint32_t batch, uint64_t* out, void* ws, size_t wsBytes, void* stream);
+/* any limbs of the context (limbIdx[sizeQl], NULL = the leading ones; the LAST entries are dropped, the last one first) with the CALLER's
+ * tables as the loop's steps receive them (dcrtpoly-impl.h:693-694): step k = 0 .. levels-1 drops limb sizeQl-1-k and reads the
+ * sizeQl-1-k residues GetQlQlInvModqlDivqlModq(.) / GetqlInvModq(.) of that level at offset sum_{j<k} (sizeQl-1-j) of each array. */
+fhe_status fhe_rescale_multi_limbs(fhe_ctx* ctx, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint32_t levels,
+                                   uint32_t nOut, const uint64_t* scale, const uint64_t* QlQlInvModqlDivqlModq,
+                                   const uint64_t* qlInvModq, uint32_t batch, uint64_t* out, void* ws, size_t wsBytes, void* stream);
+/* both elements of a ciphertext (towers x0, x1 -> out0, out1, each allocated on its own) in the same launches, as
+ * ModReduceInternalInPlace treats them (ckksrns-leveledshe.cpp:176-181); ws of fhe_rescale_multi_workspace_bytes(ctx, sizeQl, levels, 2) */
+fhe_status fhe_rescale_multi_limbs_pair(fhe_ctx* ctx, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
+                                        uint32_t levels, uint32_t nOut, const uint64_t* scale, const uint64_t* QlQlInvModqlDivqlModq,
+                                        const uint64_t* qlInvModq, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes,
+                                        void* stream);
+/* The host-side constants of one fused pass of d <= 4 limbs, as the library derives them (host_math.h rescale_multi_tables; nothing touches a
+ * device): qDrop[d] in dropping order, qKeep[nKeep] the produced limbs, sDrop / sKeep the scalar's residues (both NULL: none).  Pairs
+ * {value, Shoup companion}: B[d][d][2] (q_k^-1 mod q_j for k < j, else 0), W[d][nKeep][2], C[nKeep][2], S[d][2]. */
+fhe_status fhe_rescale_multi_host_tables(const uint64_t* qDrop, uint32_t d, const uint64_t* qKeep, uint32_t nKeep, const uint64_t* sDrop,
+                                         const uint64_t* sKeep, uint64_t* B, uint64_t* W, uint64_t* C, uint64_t* S);
 /* DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755) — BGV modulus switching by the last limb with plaintext modulus t
  * (tables negtInvModq / qlInvModq / tModqPrecon of CryptoParametersBGVRNS are derived inside): x [batch][sizeQl][N] in
  * `evalFormat`, out [batch][sizeQl-1][N] in the same format; ws as for fhe_rescale. */

@@ -390,6 +390,52 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) switch_modulus_kernel(const SwitchMo
     }
 }
 
+// ---- the coefficient-domain chain of a rescale by d limbs ---------------------------------------------------
+// rows[b][p][.] holds INTT of the d dropped limbs of tower b in ascending limb order: step k of the reference's loop
+// (ckksrns-leveledshe.cpp:172-191 -> DropLastElementAndScale, dcrtpoly-impl.h:693-712) drops row d-1-k.  What that loop would find as its
+// last limb in COEFFICIENT format at step k, computed without leaving the coefficient domain and written in place:
+//   r_0 = e_0,   r_k = (...((e_k - SM(r_0 -> q_k)) * B[0][k] - SM(r_1 -> q_k)) * B[1][k] ... - SM(r_{k-1} -> q_k)) * B[k-1][k]  mod q_k
+// with e_k the row (times the scalar's residue s[k] when hasScale) and B[i][k] = q_i^-1 mod q_k.  One lane per coefficient; the triangle
+// travels by value.
+constexpr int kMaxRescaleDrop = 4;
+struct RescaleChainArgs {
+    uint64_t* rows;  // [batch][d][N]
+    uint32_t logN, d, batch, hasScale;
+    uint64_t q[kMaxRescaleDrop];                     // modulus of step k
+    TwPair B[kMaxRescaleDrop][kMaxRescaleDrop];      // [i][k], i < k
+    TwPair s[kMaxRescaleDrop];                       // scalar residue of step k's limb
+};
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) rescale_chain_kernel(const RescaleChainArgs g) {
+    const uint32_t t     = FHE_TID;
+    const uint64_t base  = (uint64_t)FHE_BID << kTileLog;
+    const uint64_t total = (uint64_t)g.batch << g.logN;
+    const uint32_t mask  = (1u << g.logN) - 1u;
+#pragma unroll 2
+    for (int m = 0; m < 16; ++m) {
+        const uint64_t off = base + (uint64_t)m * kThreads + t;
+        if (off >= total)
+            continue;
+        uint64_t* p = g.rows + (((off >> g.logN) * g.d) << g.logN) + ((uint32_t)off & mask);
+        uint64_t r[kMaxRescaleDrop];
+#pragma unroll
+        for (int k = 0; k < kMaxRescaleDrop; ++k) {
+            if ((uint32_t)k >= g.d)
+                break;
+            uint64_t* pk      = p + ((uint64_t)(g.d - 1u - (uint32_t)k) << g.logN);
+            const uint64_t qk = g.q[k];
+            uint64_t v        = *pk;
+            if (g.hasScale)
+                v = mul_shoup(v, g.s[k].w, g.s[k].wp, qk);
+#pragma unroll
+            for (int i = 0; i < k; ++i)
+                v = mul_shoup(sub_mod(v, switch_modulus_word(r[i], g.q[i], g.q[i] >> 1, qk), qk), g.B[i][k].w, g.B[i][k].wp, qk);
+            r[k] = v;
+            if (k > 0 || g.hasScale)
+                *pk = v;
+        }
+    }
+}
+
 // ---- DCRTPolyImpl::CRTDecompose (dcrtpoly-impl.h:230-285; the digit decomposition of KeySwitchBV) of a whole batch in ONE launch: every
 // window of every source limb, each lifted (centred, PolyImpl::SwitchModulus) into every limb of its own tower; COEFFICIENT in,
 // COEFFICIENT out (the caller transforms all towers in one launch).  Digit w of a word = its bits [w * baseBits, (w + 1) * baseBits)

@@ -655,6 +655,8 @@ struct NttOpts {
     bool canonOut = true;            // false: the output may stay lazy (forward: below the bound of the last step)
     const uint32_t* proSrcLimb = nullptr;  // forward: every limb is loaded from row src.first, a limb modulo q[*proSrcLimb] (NttPassArgs::proMode)
     const TwPair* proC = nullptr;          // with proSrcLimb: ... and multiplied by proC[row of the tower] (proMode 2)
+    uint32_t proRows = 0;                  // != 0 (proMode 3): every limb is the sum of rows 0..proRows-1 of the source tower, row k modulo
+                                           // q[proSrcLimb[k]] and weighted by proC[k * nLimbs + row of the tower]
 };
 
 // ---- the small-ring kernel (N < 4096): ntt_pass_kernel reads its plan from the arguments (steps, nSteps, canonLevels, canonStep) ----
@@ -782,14 +784,16 @@ static bool static_epilogue_instance(const NttPass& p, const NttPassArgs* a, voi
 #undef FHE_CASE
     return false;
 }
-// ... with the load prologue (NttPassArgs::proMode): the forward column passes.  Both prologue modes have the same pass shapes, so the
-// question "is there an instance" (a == nullptr) has one answer for both; a launch takes the instance of a->proMode.
+// ... with the load prologue (NttPassArgs::proMode): the forward column passes.  The prologue modes have the same pass shapes, so the
+// question "is there an instance" (a == nullptr) has one answer for all; a launch takes the instance of a->proMode.
 static bool static_prologue_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
 #define FHE_CASE(TT)                                                                                                                  \
-    FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1) && !(a && a->proMode == 2u),                                                         \
+    FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1) && !(a && a->proMode >= 2u),                                                         \
                  FHE_LAUNCH_AS("PRO", (ntt_static_kernel<true, false, TT, 1, false, 1>), pass_tiles(*a), kThreads, true, stream, *a))  \
     FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1) && a && a->proMode == 2u,                                                            \
-                 FHE_LAUNCH_AS("PRO2", (ntt_static_kernel<true, false, TT, 1, false, 2>), pass_tiles(*a), kThreads, true, stream, *a))
+                 FHE_LAUNCH_AS("PRO2", (ntt_static_kernel<true, false, TT, 1, false, 2>), pass_tiles(*a), kThreads, true, stream, *a)) \
+    FHE_INSTANCE(FHE_PASS_IS(true, false, TT, 1) && a && a->proMode == 3u,                                                            \
+                 FHE_LAUNCH_AS("PRO3", (ntt_static_kernel<true, false, TT, 1, false, 3>), pass_tiles(*a), kThreads, true, stream, *a))
     FHE_CASE(4) FHE_CASE(5)
 #undef FHE_CASE
     return false;
@@ -887,8 +891,11 @@ static void fill_pass_args(const fhe_ctx* c, const NttPass& p, const uint64_t* x
     const NttEpilogue& e = o.epi && o.epi->mode ? *o.epi : noEpi;
     a.epiMode = e.mode, a.epiSplit = e.split, a.epiAStride = e.aStride, a.epiAFirst = e.aFirst;
     a.epiA = e.A, a.epiC = e.C, a.epiOut0 = e.out0, a.epiOut1 = e.out1, a.epiADelta = e.aDelta;
-    a.proMode = o.proSrcLimb ? (o.proC ? 2 : 1) : 0, a.proSrcLimb = o.proSrcLimb ? *o.proSrcLimb : 0;
+    a.proMode = o.proSrcLimb ? (o.proRows ? 3 : o.proC ? 2 : 1) : 0, a.proSrcLimb = o.proSrcLimb ? *o.proSrcLimb : 0;
     a.proC = o.proSrcLimb ? o.proC : nullptr;
+    a.proRows = o.proSrcLimb ? o.proRows : 0;
+    for (uint32_t k = 0; k < 4; ++k)
+        a.proSrcLimbs[k] = k < a.proRows ? o.proSrcLimb[k] : 0;
 }
 // the first n polynomials of the pass's batch as a pass of their own; `a` goes on with the rest, on the same stream, as the same pass over a
 // view that starts at its first polynomial
@@ -3185,6 +3192,228 @@ extern "C" fhe_status fhe_rescale_limbs_pair(fhe_ctx* c, const uint64_t* x0, con
     ARG_CHECK(x1 && out1 && x1 != x0 && out1 != out0, "fhe_rescale_limbs_pair: needs two distinct towers");
     return rescale_limbs_run(c, x0, x1, limbIdx, sizeQl, QlQlInvModqlDivqlModq, qlInvModq, 2, out0, out1, wsv, wsBytes, st,
                              "fhe_rescale_limbs_pair");
+}
+
+// ---- CKKS rescale by several limbs (composite scaling) ----
+// LeveledSHECKKSRNS::ModReduceInternalInPlace(ct, levels) (ckksrns-leveledshe.cpp:172-191) calls DropLastElementAndScale `levels` times on
+// every element; under COMPOSITESCALINGAUTO / COMPOSITESCALINGMANUAL levels = compositeDegree on every rescale, and AdjustLevelsAndDepthInPlace
+// (:600-730) puts a scalar product in front and a LevelReduceInternalInPlace behind.  One call here: x[batch][sizeQl][N] EVALUATION, optionally
+// times the scalar's residues scale[sizeQl], rescaled by the last `levels` limbs, of which the first nOut limbs are produced.
+// ws: three regions of batch * sizeQl * N words each —
+//   R0  fused: INTT of the dropped limbs, rows[batch][d][N];  sequential: the workspace of rescale_run
+//   R1, R2  the towers between chunks / steps, alternating; the transform's working tower when the store goes to two output towers
+extern "C" size_t fhe_rescale_multi_workspace_bytes(const fhe_ctx* c, uint32_t sizeQl, uint32_t levels, uint32_t batch) {
+    if (!c || sizeQl < 2 || levels < 1 || levels >= sizeQl)
+        return 0;
+    return (((size_t)3 * batch * sizeQl) << c->logN) * 8;
+}
+// the caller's (or the derived) tables of step k: sizeQl-1-k residues at offset sum_{j<k} (sizeQl-1-j)
+static size_t rescale_multi_tab_offset(uint32_t sizeQl, uint32_t k) { return (size_t)k * (sizeQl - 1) - (size_t)k * (k ? k - 1 : 0) / 2; }
+// One chunk of d <= kMaxRescaleDrop limbs, fused: x is a tower of n limbs (towers n rows or xDelta words apart), limbs
+// limbIdx[0..n) of the context; out0 (and out1 != null: tower 1 goes there, batch must be 2) dense [.][nOut][N].  Five launches on a ring of
+// two passes: the two inverse passes over the d dropped limbs, the chain kernel, the column pass whose load sums the d switched rows, the row
+// pass whose store is (x - r) * C.
+static fhe_status rescale_multi_chunk(fhe_ctx* c, const uint64_t* x, int64_t xDelta, const uint32_t* limbIdx, uint32_t n, uint32_t d,
+                                      uint32_t nOut, const uint64_t* scale, uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* rows,
+                                      uint64_t* work, void* st) {
+    uint32_t dropIdx[kMaxRescaleDrop], rowIdx[kMaxRescaleDrop];  // step k drops limb n-1-k; row p of `rows` is limb n-d+p
+    uint64_t qDrop[kMaxRescaleDrop], sDrop[kMaxRescaleDrop];
+    for (uint32_t k = 0; k < d; ++k) {
+        dropIdx[k] = limbIdx ? limbIdx[n - 1 - k] : n - 1 - k;
+        rowIdx[k]  = limbIdx ? limbIdx[n - d + k] : n - d + k;
+        qDrop[k]   = c->q[dropIdx[k]];
+        sDrop[k]   = scale ? scale[n - 1 - k] : 1;
+    }
+    std::vector<uint64_t> qKeep(nOut), W(2 * (size_t)d * nOut), C(2 * (size_t)nOut);
+    for (uint32_t i = 0; i < nOut; ++i)
+        qKeep[i] = c->q[limbIdx ? limbIdx[i] : i];
+    uint64_t B[2 * kMaxRescaleDrop * kMaxRescaleDrop], S[2 * kMaxRescaleDrop];
+    host::rescale_multi_tables(qDrop, d, qKeep.data(), nOut, scale ? sDrop : nullptr, scale, B, W.data(), C.data(), S);
+    // device copies: the weights in the order of the rows (row p = step d-1-p), cached by content like every per-call table
+    std::vector<uint32_t> wLimb((size_t)d * nOut);
+    std::vector<uint64_t> wVal((size_t)d * nOut), cVal(nOut);
+    for (uint32_t p = 0; p < d; ++p)
+        for (uint32_t i = 0; i < nOut; ++i) {
+            wLimb[(size_t)p * nOut + i] = limbIdx ? limbIdx[i] : i;
+            wVal[(size_t)p * nOut + i]  = W[2 * ((size_t)(d - 1 - p) * nOut + i)];
+        }
+    for (uint32_t i = 0; i < nOut; ++i)
+        cVal[i] = C[2 * i];
+    const TwPair *dW = nullptr, *dC = nullptr;
+    if (fhe_status s = const_table(c, wLimb.data(), wVal.data(), d * nOut, &dW))
+        return s;
+    if (fhe_status s = const_table(c, wLimb.data(), cVal.data(), nOut, &dC))
+        return s;
+    // lastPoly.SetFormat(COEFFICIENT) of every step's last limb (dcrtpoly-impl.h:696-697), all d rows of every tower at once
+    NttOpts dropped;
+    dropped.src.stride = n, dropped.src.first = n - d, dropped.srcDelta = xDelta;
+    if (fhe_status s = ntt_run(c, true, x, rows, rowIdx, d, batch, st, dropped))
+        return s;
+    RescaleChainArgs g;
+    g.rows = rows, g.logN = c->logN, g.d = d, g.batch = batch, g.hasScale = scale ? 1u : 0u;
+    for (uint32_t k = 0; k < (uint32_t)kMaxRescaleDrop; ++k) {
+        g.q[k] = k < d ? qDrop[k] : 1;
+        g.s[k] = k < d ? TwPair{S[2 * k], S[2 * k + 1]} : TwPair{0, 0};
+        for (uint32_t j = 0; j < (uint32_t)kMaxRescaleDrop; ++j)
+            g.B[k][j] = (k < d && j < d) ? TwPair{B[2 * (k * d + j)], B[2 * (k * d + j) + 1]} : TwPair{0, 0};
+    }
+    if (d > 1 || scale) {
+        FHE_LAUNCH(rescale_chain_kernel, tiles_for(c, batch), st, g);
+        LAUNCH_CHECK();
+    }
+    NttEpilogue epi;
+    epi.mode = 1, epi.split = out1 ? 1 : batch, epi.aStride = n, epi.aFirst = 0, epi.aDelta = xDelta;
+    epi.A = x, epi.C = dC, epi.out0 = out0, epi.out1 = out1 ? out1 : out0;
+    NttOpts fusedStore;
+    fusedStore.epi        = &epi;
+    fusedStore.src.stride = d, fusedStore.src.first = 0;
+    fusedStore.proSrcLimb = rowIdx, fusedStore.proRows = d, fusedStore.proC = dW;
+    return ntt_run(c, false, rows, out1 ? work : out0, limbIdx, nOut, batch, st, fusedStore);
+}
+// derived: the tables are the negated pair of the true inverses at every step, i.e. what the library would compute itself; only then do the
+// steps collapse into the one-pass form.  tabA / tabB: host tables in the layout of fhe_rescale_multi_limbs.
+static fhe_status rescale_multi_run(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
+                                    uint32_t levels, uint32_t nOut, const uint64_t* scale, const uint64_t* tabA, const uint64_t* tabB,
+                                    bool derived, uint32_t batch, uint64_t* out, uint64_t* out1, uint64_t* ws, void* st) {
+    const size_t region = ((size_t)batch * sizeQl) << c->logN;
+    uint64_t *R0 = ws, *R[2] = {ws + region, ws + 2 * region};
+    static const bool noFuse = env_u32("FHE_RESCALE_UNFUSED", 0) != 0;
+    bool fused = derived && !noFuse && ntt_epilogue_supported(c) && ntt_prologue_supported(c);
+    for (uint32_t i = 0; scale && i < sizeQl; ++i)
+        fused = fused && scale[i] != 0;  // (a zero residue has no inverse to put into the load's weights)
+    if (levels == 1 && !scale && nOut == sizeQl - 1)
+        fused = false;  // the member itself: rescale_run's four launches
+    if (fused) {
+        const uint64_t* cur = x;
+        int64_t curDelta    = x1 ? x1 - x : 0;
+        uint32_t n = sizeQl, left = levels, j = 0;
+        while (left) {
+            const uint32_t d    = std::min<uint32_t>(left, (uint32_t)kMaxRescaleDrop);
+            const bool lastOne  = left == d;
+            const uint32_t keep = lastOne ? nOut : n - d;
+            uint64_t* dst       = lastOne ? out : R[j & 1];
+            if (fhe_status s = rescale_multi_chunk(c, cur, curDelta, limbIdx, n, d, keep, j == 0 ? scale : nullptr, batch, dst,
+                                                   lastOne ? out1 : nullptr, R0, R[j & 1], st))
+                return s;
+            cur = dst, curDelta = 0, n -= d, left -= d, ++j;
+        }
+        return FHE_OK;
+    }
+    if (x1) {  // element by element
+        if (fhe_status s = rescale_multi_run(c, x, nullptr, limbIdx, sizeQl, levels, nOut, scale, tabA, tabB, derived, 1, out, nullptr, ws, st))
+            return s;
+        return rescale_multi_run(c, x1, nullptr, limbIdx, sizeQl, levels, nOut, scale, tabA, tabB, derived, 1, out1, nullptr, ws, st);
+    }
+    // the reference's loop: EvalMultCoreInPlace's scalar product, DropLastElementAndScale `levels` times, the limbs beyond nOut dropped
+    const uint64_t* cur = x;
+    if (scale) {
+        const TwPair* dS = nullptr;
+        if (fhe_status s = const_table(c, limbIdx, scale, sizeQl, &dS))
+            return s;
+        if (fhe_status s = elem_run<OP_MUL_CONST>(c, R[1], x, nullptr, dS, limbIdx, sizeQl, batch, st, "fhe_rescale_multi"))
+            return s;
+        cur = R[1];
+    }
+    uint32_t n = sizeQl;
+    for (uint32_t k = 0; k < levels; ++k, --n) {
+        const size_t off = rescale_multi_tab_offset(sizeQl, k);
+        bool negated     = true;
+        for (uint32_t i = 0; i + 1 < n; ++i) {
+            const uint64_t qi = c->q[limbIdx ? limbIdx[i] : i];
+            negated           = negated && tabA[off + i] == (qi - tabB[off + i]) % qi;
+        }
+        const TwPair *dA = nullptr, *dB = nullptr;
+        if (fhe_status s = const_table(c, limbIdx, tabA + off, n - 1, &dA))
+            return s;
+        if (fhe_status s = const_table(c, limbIdx, tabB + off, n - 1, &dB))
+            return s;
+        const bool direct = k + 1 == levels && nOut == n - 1;
+        uint64_t* dst     = direct ? out : R[k & 1];
+        if (fhe_status s = rescale_run(c, cur, limbIdx, n, dA, dB, negated, batch, dst, R0, st))
+            return s;
+        cur = dst;
+    }
+    if (cur != out)  // LevelReduceInternalInPlace: the first nOut limbs of every tower
+        RT_CHECK(rt::d2d_2d(out, ((size_t)nOut * 8) << c->logN, cur, ((size_t)n * 8) << c->logN, ((size_t)nOut * 8) << c->logN, batch,
+                            (rt::stream_t)st));
+    return FHE_OK;
+}
+// argument checks and tables of the three entry points; tabA / tabB null: the library's own tables over the leading limbs
+static fhe_status rescale_multi_entry(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
+                                      uint32_t levels, uint32_t nOut, const uint64_t* scale, const uint64_t* tabA, const uint64_t* tabB,
+                                      bool ownTables, uint32_t batch, uint64_t* out, uint64_t* out1, void* wsv, size_t wsBytes, void* st,
+                                      const char* who) {
+    const std::string w(who);
+    ARG_CHECK(c && x && out && wsv && (ownTables || (tabA && tabB)), w + ": null argument");
+    ARG_CHECK(sizeQl >= 2 && sizeQl <= (uint32_t)kMaxLimbs && (limbIdx || sizeQl <= c->L),
+              "Removing last element of DCRTPoly renders it invalid.");  // dcrtpoly-impl.h:672-673
+    ARG_CHECK(levels >= 1 && levels < sizeQl, w + ": levels must be in [1, sizeQl)");
+    ARG_CHECK(nOut >= 1 && nOut <= sizeQl - levels, w + ": nOut must be in [1, sizeQl - levels]");
+    for (uint32_t i = 0; i < sizeQl; ++i)
+        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, w + ": limb index exceeds context size");
+    ARG_CHECK(batch >= 1 && wsBytes >= fhe_rescale_multi_workspace_bytes(c, sizeQl, levels, batch), w + ": workspace too small");
+    ARG_CHECK(out != x && out != x1 && (!out1 || (out1 != x && out1 != x1)), w + ": out must not alias x");
+    for (uint32_t i = 0; scale && i < sizeQl; ++i)
+        ARG_CHECK(scale[i] < c->q[limbIdx ? limbIdx[i] : i], w + ": scale is not reduced modulo its limb");
+    std::vector<uint64_t> ownA, ownB;
+    bool derived = true;
+    if (ownTables) {  // ckksrns-cryptoparameters.cpp:60-81 at every step
+        ownA.resize(rescale_multi_tab_offset(sizeQl, levels)), ownB.resize(ownA.size());
+        tabA = ownA.data(), tabB = ownB.data();
+    }
+    for (uint32_t k = 0; k < levels; ++k) {
+        const uint64_t ql = c->q[limbIdx ? limbIdx[sizeQl - 1 - k] : sizeQl - 1 - k];
+        const size_t off  = rescale_multi_tab_offset(sizeQl, k);
+        for (uint32_t i = 0; i + 1 + k < sizeQl; ++i) {
+            const uint64_t qi  = c->q[limbIdx ? limbIdx[i] : i];
+            const uint64_t inv = ql % qi ? host::invmod(ql % qi, qi) : 0;
+            if (ownTables) {
+                ARG_CHECK(inv != 0, w + ": the moduli of a tower must be distinct");
+                ownB[off + i] = inv, ownA[off + i] = (qi - inv) % qi;
+                continue;
+            }
+            ARG_CHECK(tabA[off + i] < qi && tabB[off + i] < qi, w + ": table entry is not reduced modulo its limb");
+            derived = derived && inv != 0 && tabB[off + i] == inv && tabA[off + i] == (qi - inv) % qi;
+        }
+    }
+    RT_CHECK(rt::set_device(c->device));
+    if (fhe_status s = const_tables_trim(c))
+        return s;
+    std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
+    return rescale_multi_run(c, x, x1, limbIdx, sizeQl, levels, nOut, scale, tabA, tabB, derived, batch, out, out1, (uint64_t*)wsv, st);
+}
+extern "C" fhe_status fhe_rescale_multi(fhe_ctx* c, const uint64_t* x, uint32_t sizeQl, uint32_t levels, uint32_t nOut,
+                                        const uint64_t* scale, uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes, void* st) {
+    return rescale_multi_entry(c, x, nullptr, nullptr, sizeQl, levels, nOut, scale, nullptr, nullptr, true, batch, out, nullptr, wsv,
+                               wsBytes, st, "fhe_rescale_multi");
+}
+extern "C" fhe_status fhe_rescale_multi_limbs(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint32_t levels,
+                                              uint32_t nOut, const uint64_t* scale, const uint64_t* QlQlInvModqlDivqlModq,
+                                              const uint64_t* qlInvModq, uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes,
+                                              void* st) {
+    return rescale_multi_entry(c, x, nullptr, limbIdx, sizeQl, levels, nOut, scale, QlQlInvModqlDivqlModq, qlInvModq, false, batch, out,
+                               nullptr, wsv, wsBytes, st, "fhe_rescale_multi_limbs");
+}
+// the two elements of one ciphertext (towers x0, x1 -> out0, out1, each allocated on its own) in the same launches; ws for batch 2
+extern "C" fhe_status fhe_rescale_multi_limbs_pair(fhe_ctx* c, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx,
+                                                   uint32_t sizeQl, uint32_t levels, uint32_t nOut, const uint64_t* scale,
+                                                   const uint64_t* QlQlInvModqlDivqlModq, const uint64_t* qlInvModq, uint64_t* out0,
+                                                   uint64_t* out1, void* wsv, size_t wsBytes, void* st) {
+    ARG_CHECK(x1 && out1, "fhe_rescale_multi_limbs_pair: null argument");
+    ARG_CHECK(x1 != x0 && out1 != out0, "fhe_rescale_multi_limbs_pair: needs two distinct towers");
+    return rescale_multi_entry(c, x0, x1, limbIdx, sizeQl, levels, nOut, scale, QlQlInvModqlDivqlModq, qlInvModq, false, 2, out0, out1,
+                               wsv, wsBytes, st, "fhe_rescale_multi_limbs_pair");
+}
+// the host-side constants of one fused chunk (host::rescale_multi_tables) as the library derives them, for checks against exact integers
+extern "C" fhe_status fhe_rescale_multi_host_tables(const uint64_t* qDrop, uint32_t d, const uint64_t* qKeep, uint32_t nKeep,
+                                                    const uint64_t* sDrop, const uint64_t* sKeep, uint64_t* B, uint64_t* W, uint64_t* C,
+                                                    uint64_t* S) {
+    ARG_CHECK(qDrop && qKeep && B && W && C && S && (!sDrop == !sKeep), "fhe_rescale_multi_host_tables: null argument");
+    ARG_CHECK(d >= 1 && d <= (uint32_t)kMaxRescaleDrop && nKeep >= 1, "fhe_rescale_multi_host_tables: bad sizes");
+    for (uint32_t i = 0; sKeep && i < nKeep; ++i)
+        ARG_CHECK(sKeep[i] % qKeep[i] != 0, "fhe_rescale_multi_host_tables: a zero scalar residue has no inverse");
+    host::rescale_multi_tables(qDrop, d, qKeep, nKeep, sDrop, sKeep, B, W, C, S);
+    return FHE_OK;
 }
 
 // DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755), the BGV modulus switch by the last limb with plaintext modulus t:

@@ -63,6 +63,39 @@ uint64_t min_root_of_unity(uint64_t m, uint64_t q);
 // product of mods[k] (k in sel, k != skip) reduced mod `mod`
 uint64_t prod_mod(const std::vector<uint64_t>& mods, int skip, uint64_t mod);
 
+// Constants of a rescale by d limbs in one pass (LeveledSHECKKSRNS::ModReduceInternalInPlace, ckksrns-leveledshe.cpp:172-191, as one
+// step).  qDrop[k]: the modulus dropped at step k (the last limb first), qKeep[i]: the limbs that are produced,
+// sKeep / sDrop: residues of the scalar the tower is multiplied by first (null: none; every sKeep[i] must be non-zero).
+//   B[k][j]  = qDrop[k]^-1 mod qDrop[j], k < j                       the triangle of the coefficient-domain chain
+//   W[k][i]  = sKeep[i]^-1 * prod_{j<k} qDrop[j] mod qKeep[i]        weight of chain row k in the column pass's load
+//   C[i]     = sKeep[i] * prod_k qDrop[k]^-1 mod qKeep[i]            constant of the row pass's store (A - r) * C
+// so that (x_i - NTT(sum_k SM(r_k) * W[k][i])) * C[i] = x_i * s_i * prod_k B[k][i] - NTT(sum_k SM(r_k) * prod_{j>=k} B[j][i]).
+// Every entry comes with its Shoup companion: out arrays hold {value, shoup(value)} pairs, B as [d][d] (entries k >= j zero), W as [d][nKeep].
+inline void rescale_multi_tables(const uint64_t* qDrop, uint32_t d, const uint64_t* qKeep, uint32_t nKeep, const uint64_t* sDrop,
+                                 const uint64_t* sKeep, uint64_t* B, uint64_t* W, uint64_t* C, uint64_t* S) {
+    for (uint32_t k = 0; k < d; ++k) {
+        for (uint32_t j = 0; j < d; ++j) {
+            const uint64_t v       = k < j ? invmod(qDrop[k] % qDrop[j], qDrop[j]) : 0;
+            B[2 * (k * d + j)]     = v;
+            B[2 * (k * d + j) + 1] = k < j ? shoup(v, qDrop[j]) : 0;
+        }
+        const uint64_t s = sDrop ? sDrop[k] : 1;
+        S[2 * k] = s, S[2 * k + 1] = shoup(s, qDrop[k]);
+    }
+    for (uint32_t i = 0; i < nKeep; ++i) {
+        const uint64_t qi = qKeep[i];
+        uint64_t w        = sKeep ? invmod(sKeep[i], qi) : 1 % qi;
+        uint64_t cst      = sKeep ? sKeep[i] : 1 % qi;
+        for (uint32_t k = 0; k < d; ++k) {
+            W[2 * ((size_t)k * nKeep + i)]     = w;
+            W[2 * ((size_t)k * nKeep + i) + 1] = shoup(w, qi);
+            w                                  = mulmod(w, qDrop[k] % qi, qi);
+            cst                                = mulmod(cst, invmod(qDrop[k] % qi, qi), qi);
+        }
+        C[2 * i] = cst, C[2 * i + 1] = shoup(cst, qi);
+    }
+}
+
 }  // namespace host
 }  // namespace fhe
 #endif

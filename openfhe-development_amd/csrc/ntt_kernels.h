@@ -95,8 +95,12 @@ struct NttPassArgs {
     // tmp[i].SwitchModulus(q_i)` of DropLastElementAndScale (dcrtpoly-impl.h:703-704) never goes to HBM.  0: off, 1: the switch alone,
     // 2: the switched residue times proC[row of the tower] (one Shoup pair per tower row, like epiC), canonical — the
     // `t * SwitchModulus(delta)` of DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:749-752) with proC = t mod q_i.
+    // 3: the limb is the weighted sum of proRows switched rows, sum_k SwitchModulus(row k -> q_i) * proC[k * nLimbs + row of the tower]
+    // mod q_i, canonical: rows 0..proRows-1 of the tower's inStride rows, row k a COEFFICIENT limb modulo q[proSrcLimbs[k]] — the load of
+    // a rescale by several limbs, whose switched and weighted rows never go to HBM.
     uint32_t proMode, proSrcLimb;
     const TwPair* proC;
+    uint32_t proRows, proSrcLimbs[4];
     // != 0: consecutive towers of the pass's first load / of the epilogue's operand A are this many WORDS apart (signed: towers
     // allocated on their own — the two elements of a ciphertext); overrides inStride / epiAStride (static kernels only)
     int64_t inDelta, epiADelta;

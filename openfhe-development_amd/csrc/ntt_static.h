@@ -561,6 +561,8 @@ FHE_HD void lane_geom_s(uint32_t t, uint32_t S, uint32_t& Ib, uint32_t& jrel, ui
 // PRO: the first load takes every limb of a tower from one COEFFICIENT row modulo another limb's modulus and switches it to the
 // limb's own modulus (NttPassArgs::proMode) — forward column passes only.  PRO = 2 (proMode 2) also multiplies the switched residue by the
 // tower row's constant NttPassArgs::proC (BGV ModReduce: t mod q_i) and leaves it canonical, which is what the first stage expects of a load.
+// PRO = 3 (proMode 3) loads the weighted sum of NttPassArgs::proRows such rows, each switched from its own modulus, canonical too (the CKKS
+// rescale by several limbs).
 // HAND: the inverse 4-stage column pass does the twiddle products of the preceding row pass's last stage (hand_mul16) on its way in, for the
 // tiles whose columns have coefficient bit T2 - 1 set.  Its partner is ntt_row8.h's batched kernel with HAND;
 // no other kernel reads or writes that intermediate tower.
@@ -704,6 +706,32 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
         }
     };
 
+    // PRO == 3: the load itself — one source row at a time into the 16 residues (live registers do not grow with the row count), in two
+    // halves of 8 loads each
+    auto pro_sum = [&](uint64_t (&v)[16], uint32_t jr, uint64_t kstr) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            v[k] = 0;
+        for (uint32_t s = 0; s < a.proRows; ++s) {
+            const uint64_t qs = FHE_ULOAD64(a.q, FHE_UNIFORM(a.proSrcLimbs[s])), halfQs = qs >> 1;
+            const uint64_t* cw = reinterpret_cast<const uint64_t*>(a.proC + (size_t)s * a.nLimbs + rit);
+            const uint64_t cW = FHE_ULOAD64(cw, 0), cWp = FHE_ULOAD64(cw, 1);
+            const uint64_t* sp = src + ((uint64_t)s << logN);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                uint64_t w[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    w[k] = FHE_GLD(&sp[jr + (8 * h + k) * kstr]);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const uint64_t sw = switch_modulus_word(w[k], qs, halfQs, q);
+                    v[8 * h + k]      = add_mod(v[8 * h + k], csub(mul_shoup_lazy_nq(sw, cW, cWp, nq), q), q);
+                }
+            }
+        }
+    };
+
 #define FHE_SHARED_TW_TO_LDS()                                             \
     if constexpr (useShared) {                                             \
         if (t < (uint32_t)SS::total)                                       \
@@ -725,11 +753,15 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
     }
     else if constexpr (P::stageFirst) {
         lane_geom_s<LA, T, 8>(t, S, Ib, jrel, ks);
+        if constexpr (PRO == 3)
+            pro_sum(r, jrel, ks);
+        else {
 #pragma unroll
-        for (int k = 0; k < 16; ++k)
-            r[k] = FHE_GLD(&src[jrel + k * ks]);
-        if constexpr (PRO)
-            pro_switch(r);
+            for (int k = 0; k < 16; ++k)
+                r[k] = FHE_GLD(&src[jrel + k * ks]);
+            if constexpr (PRO)
+                pro_switch(r);
+        }
         FHE_SHARED_TW_TO_LDS()
         uint64_t* L = lds + lds_pad(Ib);
 #pragma unroll
@@ -746,9 +778,13 @@ FHE_DEV void ntt_static_core(const NttPassArgs& a, uint32_t bid, uint64_t* lds, 
             /* residues already in r[] in this step's layout */                                                   \
         }                                                                                                         \
         else if constexpr (I == 0 && !P::stageFirst) {                                                            \
-            _Pragma("unroll") for (int k = 0; k < 16; ++k) r[k] = FHE_GLD(&src[jrel + k * ks]);                   \
-            if constexpr (PRO)                                                                                    \
-                pro_switch(r);                                                                                    \
+            if constexpr (PRO == 3)                                                                               \
+                pro_sum(r, jrel, ks);                                                                             \
+            else {                                                                                                \
+                _Pragma("unroll") for (int k = 0; k < 16; ++k) r[k] = FHE_GLD(&src[jrel + k * ks]);               \
+                if constexpr (PRO)                                                                                \
+                    pro_switch(r);                                                                                \
+            }                                                                                                     \
             FHE_SHARED_TW_TO_LDS()                                                                                \
         }                                                                                                         \
         else {                                                                                                    \

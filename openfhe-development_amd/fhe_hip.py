@@ -158,6 +158,11 @@ class Lib:
         S("fhe_mul_const_pair", C.c_int, [vp, vp, vp, vp, vp, u64p, u32p, u32, vp])
         S("fhe_mem_info", C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
         S("fhe_lincomb", C.c_int, [vp, vp, C.POINTER(vp), u64p, u32, u32p, u32, u32, C.c_int, vp])
+        S("fhe_rescale_multi_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_rescale_multi", C.c_int, [vp, vp, u32, u32, u32, u64p, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_rescale_multi_limbs", C.c_int, [vp, vp, u32p, u32, u32, u32, u64p, u64p, u64p, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_rescale_multi_limbs_pair", C.c_int, [vp, vp, vp, u32p, u32, u32, u32, u64p, u64p, u64p, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_rescale_multi_host_tables", C.c_int, [u64p, u32, u64p, u32, u64p, u64p, u64p, u64p, u64p, u64p])
         S("fhe_mod_reduce", C.c_int, [vp, vp, u32, u64, C.c_int, u32, vp, vp, C.c_size_t, vp])
         S("fhe_mod_reduce_limbs", C.c_int, [vp, vp, u32p, u32, u64, u64, u64p, C.c_int, u32, vp, vp, C.c_size_t, vp])
         S("fhe_mod_reduce_limbs_pair", C.c_int, [vp, vp, vp, u32p, u32, u64, u64, u64p, C.c_int, vp, vp, vp, C.c_size_t, vp])
@@ -947,6 +952,72 @@ def rescale_limbs_pair(ctx, x0, x1, scale_tab, inv_tab, stream=None):
                                                    o0.ptr, o1.ptr, ws, need, stream))
     ctx.sync(stream)
     ctx.free(ws)
+    return o0, o1
+
+
+def _u64_or_null(v):
+    if v is None:
+        return None, None
+    a = np.ascontiguousarray(v, dtype=np.uint64)
+    return a, a.ctypes.data_as(u64p)
+
+
+def rescale_multi(ctx, x, levels, n_out=None, scale=None, stream=None):
+    """LeveledSHECKKSRNS::ModReduceInternalInPlace(ct, levels) (ckksrns-leveledshe.cpp:172-191) on a Tower over context limbs [0, sizeQl)
+    in one fused pass: optionally times the scalar's residues scale[sizeQl] first, the last `levels` limbs dropped and scaled, the first
+    n_out limbs (default: all sizeQl - levels) produced."""
+    sizeQl = x.n_limbs
+    n_out = sizeQl - levels if n_out is None else n_out
+    need = ctx.lib.L.fhe_rescale_multi_workspace_bytes(ctx.h, sizeQl, levels, x.batch)
+    ws = ctx.malloc(max(need, 8))
+    out = ctx.empty(x.batch, max(n_out, 1))
+    sc, scp = _u64_or_null(scale)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_rescale_multi(ctx.h, x.ptr, sizeQl, levels, n_out, scp, x.batch, out.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
+    return out
+
+
+def rescale_multi_limbs(ctx, x, levels, scale_tabs, inv_tabs, n_out=None, scale=None, stream=None):
+    """the same on a Tower over ANY limbs of the context (x.limb_idx; its last limbs are dropped, the last one first) with the caller's
+    tables: scale_tabs / inv_tabs hold step k's QlQlInvModqlDivqlModq / qlInvModq (sizeQl-1-k residues) one after the other."""
+    sizeQl = x.n_limbs
+    n_out = sizeQl - levels if n_out is None else n_out
+    need = ctx.lib.L.fhe_rescale_multi_workspace_bytes(ctx.h, sizeQl, levels, x.batch)
+    ws = ctx.malloc(max(need, 8))
+    kept = None if x.limb_idx is None else x.limb_idx[:n_out]
+    out = ctx.empty(x.batch, max(n_out, 1), kept)
+    a, ap = _u64_or_null(scale_tabs)
+    b, bp = _u64_or_null(inv_tabs)
+    sc, scp = _u64_or_null(scale)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_rescale_multi_limbs(ctx.h, x.ptr, x._li(), sizeQl, levels, n_out, scp, ap, bp, x.batch, out.ptr, ws,
+                                                        need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
+    return out
+
+
+def rescale_multi_pair(ctx, x0, x1, levels, scale_tabs, inv_tabs, n_out=None, scale=None, stream=None):
+    """the two elements of a ciphertext (two Towers of batch 1, allocated on their own) through fhe_rescale_multi_limbs_pair"""
+    sizeQl = x0.n_limbs
+    n_out = sizeQl - levels if n_out is None else n_out
+    need = ctx.lib.L.fhe_rescale_multi_workspace_bytes(ctx.h, sizeQl, levels, 2)
+    ws = ctx.malloc(max(need, 8))
+    kept = None if x0.limb_idx is None else x0.limb_idx[:n_out]
+    o0, o1 = ctx.empty(1, max(n_out, 1), kept), ctx.empty(1, max(n_out, 1), kept)
+    a, ap = _u64_or_null(scale_tabs)
+    b, bp = _u64_or_null(inv_tabs)
+    sc, scp = _u64_or_null(scale)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_rescale_multi_limbs_pair(ctx.h, x0.ptr, x1.ptr, x0._li(), sizeQl, levels, n_out, scp, ap, bp, o0.ptr,
+                                                             o1.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
     return o0, o1
 
 

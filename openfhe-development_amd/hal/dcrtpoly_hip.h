@@ -178,6 +178,34 @@ public:
         check(s);
         *this = std::move(out);
     }
+    // DropLastElementAndScale `levels` times in one fused pass: what LeveledSHECKKSRNS::ModReduceInternalInPlace(ct, levels)
+    // (ckksrns-leveledshe.cpp:172-191) does to an element, levels = compositeDegree under composite scaling.  scale: empty, or one residue per
+    // limb the tower is multiplied by first (EvalMultCoreInPlace's integer); nOut: 0 = every remaining limb, else the leading nOut of them
+    // (the LevelReduceInternalInPlace that follows in AdjustLevelsAndDepthInPlace).  fhe_rescale_multi
+    void DropLastElementsAndScale(uint32_t levels, const std::vector<uint64_t>& scale = {}, uint32_t nOut = 0) {
+        if (!m_idx.empty())
+            throw Error("DropLastElementsAndScale: tower must use the leading context limbs");
+        if (m_format != EVALUATION)
+            throw Error("DropLastElementsAndScale: EVALUATION format expected");
+        if (levels < 1 || levels >= m_limbs)
+            throw Error("DropLastElementsAndScale: levels must be in [1, limbs)");
+        if (!scale.empty() && scale.size() < m_limbs)
+            throw Error("DropLastElementsAndScale: one scale residue per limb expected");
+        if (nOut == 0)
+            nOut = m_limbs - levels;
+        if (nOut > m_limbs - levels)
+            throw Error("DropLastElementsAndScale: nOut exceeds the remaining limbs");
+        DCRTPolyHip out(m_params, nOut, m_format, m_batch);
+        size_t wsb = fhe_rescale_multi_workspace_bytes(m_params->ctx(), m_limbs, levels, m_batch);
+        void* ws   = nullptr;
+        check(fhe_malloc(m_params->ctx(), wsb, &ws));
+        fhe_status s = fhe_rescale_multi(m_params->ctx(), m_data, m_limbs, levels, nOut, scale.empty() ? nullptr : scale.data(), m_batch,
+                                         out.m_data, ws, wsb, nullptr);
+        fhe_stream_sync(m_params->ctx(), nullptr);
+        fhe_free(m_params->ctx(), ws);
+        check(s);
+        *this = std::move(out);
+    }
     // ModReduce (BGV modulus switch by the last limb, plaintext modulus t)  dcrtpoly-impl.h:736-755
     void ModReduce(uint64_t t) {
         if (!m_idx.empty())
