@@ -416,7 +416,7 @@ fhe_status fhe_rescale(fhe_ctx* ctx, const uint64_t* x, uint32_t sizeQl, uint32_
 /* The same over any limbs of the context (limbIdx[sizeQl], NULL = the leading ones; the last entry is the dropped limb) with the
  * CALLER's tables, host arrays of sizeQl-1 residues as DropLastElementAndScale receives them (dcrtpoly-impl.h:693-694).  When
  * QlQlInvModqlDivqlModq[i] == -qlInvModq[i] mod q_i (the reference's own tables) on a ring of two static passes, the call is 4
- * launches: the switched tower and its transform never go to HBM (fhe_hip.cpp rescale_run).  out must not alias x. */
+ * launches: the switched tower and its transform never go to HBM (fhe_hip.cpp drop_last_run).  out must not alias x. */
 fhe_status fhe_rescale_limbs(fhe_ctx* ctx, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl,
                              const uint64_t* QlQlInvModqlDivqlModq, const uint64_t* qlInvModq, uint32_t batch, uint64_t* out,
                              void* ws, size_t wsBytes, void* stream);
@@ -465,7 +465,7 @@ fhe_status fhe_rescale_multi_host_tables(const uint64_t* qDrop, uint32_t d, cons
  * `evalFormat`, out [batch][sizeQl-1][N] in the same format; ws as for fhe_rescale. */
 fhe_status fhe_mod_reduce(fhe_ctx* ctx, const uint64_t* x, uint32_t sizeQl, uint64_t t, int evalFormat, uint32_t batch,
                           uint64_t* out, void* ws, size_t wsBytes, void* stream);
-/* An EVALUATION tower on a ring of static passes (N >= 4096) takes the fused form (fhe_hip.cpp mod_reduce_run): with
+/* An EVALUATION tower on a ring of static passes (N >= 4096) takes the fused form (fhe_hip.cpp drop_last_run): with
  * d = INTT(x_l) * (t^-1 mod q_l), out_i = (x_i - NTT((t mod q_i) * SwitchModulus(d -> q_i))) * q_l^-1 -- the reference's words, because
  * SwitchModulus is odd under negation for odd q_l and every step yields canonical residues.  On rings of two passes that is five launches
  * (two INTT passes of the dropped limb, the one-row product, the column pass that switches and multiplies on its way in, the row pass

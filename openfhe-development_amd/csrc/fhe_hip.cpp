@@ -16,6 +16,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "basis_kernels.h"
@@ -241,6 +242,23 @@ extern "C" uint32_t fhe_param_select_p(uint32_t logN, uint32_t sizeQ, const uint
 
 static uint32_t env_u32(const char* name, uint32_t dflt);
 
+// The device copy of a host table h[0..n): allocated, copied and waited for on the null stream, so that the table is complete before any
+// launch that reads it is enqueued, on whatever stream.  owned: the list its owner frees from when it is destroyed (null: the caller keeps
+// the pointer, as a cache that frees its own entries does).  Every table of the library is uploaded here; allocations that a call frees
+// again before it returns are not tables and do not come here.
+template <typename T, typename D>
+static fhe_status dev_copy(std::vector<void*>* owned, const T* h, size_t n, D** d) {
+    static_assert(std::is_same<T, typename std::remove_const<D>::type>::value, "dev_copy: host and device element types differ");
+    void* p = nullptr;
+    RT_CHECK(rt::dmalloc(&p, n * sizeof(T)));
+    if (owned)
+        owned->push_back(p);
+    RT_CHECK(rt::h2d(p, h, n * sizeof(T), nullptr));
+    RT_CHECK(rt::sync(nullptr));
+    *d = (D*)p;
+    return FHE_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
@@ -273,13 +291,6 @@ struct fhe_ctx {
     std::mutex cacheMutex;        // guards the lazily filled caches above (callers may be OpenMP threads)
 };
 
-static fhe_status upload(fhe_ctx* c, const void* host, size_t bytes, void** dev) {
-    RT_CHECK(rt::dmalloc(dev, bytes));
-    c->owned.push_back(*dev);
-    RT_CHECK(rt::h2d(*dev, host, bytes, nullptr));
-    RT_CHECK(rt::sync(nullptr));
-    return FHE_OK;
-}
 
 extern "C" fhe_status fhe_ctx_create(uint32_t logN, uint32_t nLimbs, const uint64_t* q, const uint64_t* psi,
                                      int device, fhe_ctx** out) {
@@ -361,15 +372,12 @@ extern "C" fhe_status fhe_ctx_create(uint32_t logN, uint32_t nLimbs, const uint6
     }
     c->h_fin = fin;
     fhe_status s;
-    if ((s = upload(c, tw.data(), tw.size() * sizeof(TwPair), (void**)&c->d_tw)) ||
-        (s = upload(c, twInv.data(), twInv.size() * sizeof(TwPair), (void**)&c->d_twInv)) ||
-        (s = upload(c, fin.data(), fin.size() * sizeof(TwPair), (void**)&c->d_fin)) ||
-        (rowTables && (s = upload(c, twRow.data(), twRow.size() * sizeof(TwPair), (void**)&c->d_twRow))) ||
-        (rowTables && (s = upload(c, twRowInv.data(), twRowInv.size() * sizeof(TwPair), (void**)&c->d_twRowInv))) ||
-        (s = upload(c, c->q.data(), nLimbs * sizeof(uint64_t), (void**)&c->d_q)) ||
-        (s = upload(c, lc.data(), nLimbs * sizeof(LimbConst), (void**)&c->d_lc)) ||
-        (s = upload(c, red.data(), nLimbs * sizeof(uint64_t), (void**)&c->d_red)) ||
-        (s = upload(c, mu.data(), mu.size() * sizeof(uint64_t), (void**)&c->d_mu128))) {
+    if ((s = dev_copy(&c->owned, tw.data(), tw.size(), &c->d_tw)) || (s = dev_copy(&c->owned, twInv.data(), twInv.size(), &c->d_twInv)) ||
+        (s = dev_copy(&c->owned, fin.data(), fin.size(), &c->d_fin)) ||
+        (rowTables && (s = dev_copy(&c->owned, twRow.data(), twRow.size(), &c->d_twRow))) ||
+        (rowTables && (s = dev_copy(&c->owned, twRowInv.data(), twRowInv.size(), &c->d_twRowInv))) ||
+        (s = dev_copy(&c->owned, c->q.data(), nLimbs, &c->d_q)) || (s = dev_copy(&c->owned, lc.data(), nLimbs, &c->d_lc)) ||
+        (s = dev_copy(&c->owned, red.data(), nLimbs, &c->d_red)) || (s = dev_copy(&c->owned, mu.data(), mu.size(), &c->d_mu128))) {
         fhe_ctx_destroy(c);
         return s;
     }
@@ -1545,10 +1553,10 @@ static fhe_status dgg_table(fhe_ctx* c, double sigma, const double** cdf, uint32
         const double a = 1.0 / (2 * cusum + 1.0);
         for (auto& v : vals)
             v *= a;
-        void* d = nullptr;
-        if (fhe_status s = upload(c, vals.data(), vals.size() * sizeof(double), &d))
+        const double* d = nullptr;
+        if (fhe_status s = dev_copy(&c->owned, vals.data(), vals.size(), &d))
             return s;
-        it = c->dggTabs.emplace(sigma, std::make_tuple((const double*)d, (uint32_t)fin, a)).first;
+        it = c->dggTabs.emplace(sigma, std::make_tuple(d, (uint32_t)fin, a)).first;
     }
     *cdf = std::get<0>(it->second), *len = std::get<1>(it->second), *av = std::get<2>(it->second);
     return FHE_OK;
@@ -1658,16 +1666,6 @@ struct fhe_conv {
     std::vector<void*> owned;
 };
 
-static fhe_status conv_upload(fhe_conv* cv, const void* h, size_t bytes, const void** d) {
-    void* p = nullptr;
-    RT_CHECK(rt::dmalloc(&p, bytes));
-    cv->owned.push_back(p);
-    RT_CHECK(rt::h2d(p, h, bytes, nullptr));
-    RT_CHECK(rt::sync(nullptr));
-    *d = p;
-    return FHE_OK;
-}
-
 static uint32_t conv_nsrc_pad(uint32_t nSrc) { return nSrc <= 8 ? 8u : nSrc <= 16 ? 16u : 32u; }
 // device plan from explicit tables: hatInv[i] (multiplier of source residue i, mod src_i), hatMod[i*nDst + j] (weight of
 // y_i in target j, mod dst_j), alphaMod[a*nDst + j] / qInv[i] for the exact variant (may be null: approximate only).
@@ -1698,10 +1696,10 @@ static fhe_status conv_from_tables(fhe_ctx* c, const std::vector<uint64_t>& src,
             alphaMod[k] = alphaIn[k] % dst[k % nDst];
     ConvTables shared{};
     fhe_status s;
-    if ((s = conv_upload(cv, dst.data(), dst.size() * 8, (const void**)&shared.dstQ)) ||
-        (s = conv_upload(cv, mu.data(), mu.size() * 8, (const void**)&shared.dstMu)) ||
-        (s = conv_upload(cv, red.data(), red.size() * 8, (const void**)&shared.dstRed)) ||
-        (s = conv_upload(cv, alphaMod.data(), alphaMod.size() * 8, (const void**)&shared.alphaMod))) {
+    if ((s = dev_copy(&cv->owned, dst.data(), dst.size(), &shared.dstQ)) ||
+        (s = dev_copy(&cv->owned, mu.data(), mu.size(), &shared.dstMu)) ||
+        (s = dev_copy(&cv->owned, red.data(), red.size(), &shared.dstRed)) ||
+        (s = dev_copy(&cv->owned, alphaMod.data(), alphaMod.size(), &shared.alphaMod))) {
         fhe_conv_destroy(cv);
         return s;
     }
@@ -1721,10 +1719,10 @@ static fhe_status conv_from_tables(fhe_ctx* c, const std::vector<uint64_t>& src,
                 hatMod[(size_t)j * pad + i] = hatModIn[(size_t)(c0 + i) * nDst + j] % dst[j];
         }
         ConvTables tb = shared;
-        if ((s = conv_upload(cv, hatInv.data(), hatInv.size() * sizeof(TwPair), (const void**)&tb.hatInv)) ||
-            (s = conv_upload(cv, hatMod.data(), hatMod.size() * 8, (const void**)&tb.hatMod)) ||
-            (s = conv_upload(cv, srcPad.data(), srcPad.size() * 8, (const void**)&tb.srcQ)) ||
-            (s = conv_upload(cv, qInv.data(), qInv.size() * sizeof(double), (const void**)&tb.srcQInv))) {
+        if ((s = dev_copy(&cv->owned, hatInv.data(), hatInv.size(), &tb.hatInv)) ||
+            (s = dev_copy(&cv->owned, hatMod.data(), hatMod.size(), &tb.hatMod)) ||
+            (s = dev_copy(&cv->owned, srcPad.data(), srcPad.size(), &tb.srcQ)) ||
+            (s = dev_copy(&cv->owned, qInv.data(), qInv.size(), &tb.srcQInv))) {
             fhe_conv_destroy(cv);
             return s;
         }
@@ -1739,9 +1737,9 @@ static fhe_status conv_from_tables(fhe_ctx* c, const std::vector<uint64_t>& src,
             allInv[i]          = TwPair{inv, host::shoup(inv, src[i])};
             allQInv[i]         = qInvIn ? qInvIn[i] : 1.0 / static_cast<double>(src[i]);
         }
-        if ((s = conv_upload(cv, allInv.data(), allInv.size() * sizeof(TwPair), (const void**)&cv->allHatInv)) ||
-            (s = conv_upload(cv, src.data(), src.size() * 8, (const void**)&cv->allSrcQ)) ||
-            (s = conv_upload(cv, allQInv.data(), allQInv.size() * sizeof(double), (const void**)&cv->allQInv))) {
+        if ((s = dev_copy(&cv->owned, allInv.data(), allInv.size(), &cv->allHatInv)) ||
+            (s = dev_copy(&cv->owned, src.data(), src.size(), &cv->allSrcQ)) ||
+            (s = dev_copy(&cv->owned, allQInv.data(), allQInv.size(), &cv->allQInv))) {
             fhe_conv_destroy(cv);
             return s;
         }
@@ -2076,19 +2074,10 @@ static fhe_status ks_level(fhe_ks_plan* p, uint32_t sizeQl, fhe_ks_plan::Level**
             const uint64_t v = host::invmod(host::prod_mod(src, -1, c->q[i]), c->q[i]);
             pinv[i]          = TwPair{v, host::shoup(v, c->q[i])};
         }
-        void* d       = nullptr;
-        const char* e = rt::dmalloc(&d, pinv.size() * sizeof(TwPair));
-        if (!e) {
-            p->owned.push_back(d);
-            e = rt::h2d(d, pinv.data(), pinv.size() * sizeof(TwPair), nullptr);
-        }
-        if (!e)
-            e = rt::sync(nullptr);
-        if (e) {
+        if (dev_copy(&p->owned, pinv.data(), pinv.size(), &lv->d_PInv)) {
             ks_level_free(lv);
-            return fail(FHE_ERR_DEVICE, std::string("fhe_keyswitch: building the level tables: ") + e);
+            return fail(FHE_ERR_DEVICE, "fhe_keyswitch: building the level tables: " + g_lastError);
         }
-        lv->d_PInv = (TwPair*)d;
     }
     p->levels[sizeQl] = lv;
     *out              = lv;
@@ -2641,12 +2630,8 @@ static fhe_status ks_pmodq(fhe_ks_plan* p, fhe_ks_plan::Level* lv, TwPair** d) {
             const uint64_t v = host::prod_mod(pm, -1, c->q[i]);
             h[i]             = TwPair{v, host::shoup(v, c->q[i])};
         }
-        void* dp = nullptr;
-        RT_CHECK(rt::dmalloc(&dp, h.size() * sizeof(TwPair)));
-        p->owned.push_back(dp);
-        RT_CHECK(rt::h2d(dp, h.data(), h.size() * sizeof(TwPair), nullptr));
-        RT_CHECK(rt::sync(nullptr));
-        lv->d_PModq = (TwPair*)dp;
+        if (fhe_status s = dev_copy(&p->owned, h.data(), h.size(), &lv->d_PModq))
+            return s;
     }
     *d = lv->d_PModq;
     return FHE_OK;
@@ -2860,10 +2845,9 @@ extern "C" fhe_status fhe_ckks_bsgs_transform(fhe_ks_plan* p, const uint64_t* c0
                 rt::dfree(kv.second);
             p->bsgsTables.clear();
         }
-        void* dp = nullptr;
-        RT_CHECK(rt::dmalloc(&dp, tab.size() * 8));
-        RT_CHECK(rt::h2d(dp, tab.data(), tab.size() * 8, nullptr));
-        RT_CHECK(rt::sync(nullptr));
+        uint64_t* dp = nullptr;
+        if (fhe_status s = dev_copy(nullptr, tab.data(), tab.size(), &dp))  // (no owner list: the map owns its entries)
+            return s;
         it = p->bsgsTables.emplace(tab, dp).first;
     }
     const uint64_t* const* dTab = (const uint64_t* const*)it->second;
@@ -3005,8 +2989,30 @@ extern "C" fhe_status fhe_approx_mod_down_bgv(fhe_ks_plan* p, const uint64_t* x,
 }
 
 // ------------------------------------------------------------------------------------------------
-// CKKS rescale
+// dropping the last limbs of a tower: CKKS rescale, BGV ModReduce, CKKS rescale by several limbs
 // ------------------------------------------------------------------------------------------------
+// One operation, three members: INTT the dropped limb(s), switch them into every kept limb on the way into the forward transform, store
+// (x - r) * C on the way out.  Everything below shares one set of argument checks (drop_check), one derivation of each table set
+// (host_math.h), one runner for a single dropped limb (drop_last_run) and one place that sets up the fused store (drop_fused_store).
+//
+// When the fused form may replace the member's own steps is a property of the tables, decided once per call by the entry:
+//   * a single CKKS limb fuses for ANY pair with A == -B (host::negated_pair): x*B + r*A is then (x - r)*B whatever B is, so the fused
+//     store computes exactly what the caller's tables say;
+//   * several CKKS limbs in one pass need, at every step, the negated pair of the TRUE inverses (host::true_inverses as well): the chain
+//     kernel, the load's weights and the store's constant are products of q_l^-1 that the library forms itself (host::rescale_multi_tables),
+//     so the caller's values enter the fused form not at all;
+//   * BGV needs the true inverses of distinct moduli and the true negtInvModq: the fused form multiplies by t^-1 mod q_l and t mod q_i where
+//     the member multiplies by negtInvModq and t, which is the same residue only for the values the library would derive itself.
+// Any other tables run the member's formula with the given values, launch by launch.  FHE_RESCALE_UNFUSED / FHE_MOD_REDUCE_UNFUSED (read
+// once per process) force that form for the CKKS / BGV entries.
+static bool rescale_unfused() {
+    static const bool v = env_u32("FHE_RESCALE_UNFUSED", 0) != 0;
+    return v;
+}
+static bool mod_reduce_unfused() {
+    static const bool v = env_u32("FHE_MOD_REDUCE_UNFUSED", 0) != 0;
+    return v;
+}
 extern "C" size_t fhe_rescale_workspace_bytes(const fhe_ctx* c, uint32_t sizeQl, uint32_t batch) {
     if (!c || sizeQl < 2)
         return 0;
@@ -3046,137 +3052,200 @@ static fhe_status const_table(fhe_ctx* c, const uint32_t* limbIdx, const uint64_
                 return fail(FHE_ERR_ARG, "const_table: constant is not reduced modulo its limb");
             h[i] = TwPair{v[i], host::shoup(v[i], qi)};
         }
-        void* d = nullptr;
-        RT_CHECK(rt::dmalloc(&d, n * sizeof(TwPair)));
-        RT_CHECK(rt::h2d(d, h.data(), n * sizeof(TwPair), nullptr));
-        RT_CHECK(rt::sync(nullptr));
-        it = c->constTabs.emplace(std::move(key), (TwPair*)d).first;
+        TwPair* d = nullptr;
+        if (fhe_status s = dev_copy(nullptr, h.data(), n, &d))  // (no owner list: the map owns its entries)
+            return s;
+        it = c->constTabs.emplace(std::move(key), d).first;
     }
     *out = it->second;
     return FHE_OK;
 }
-// DropLastElementAndScale (dcrtpoly-impl.h:693-712) of towers x[batch][sizeQl][N] over context limbs limbIdx[0..sizeQl) (null: the
-// leading ones) -> out[batch][sizeQl-1][N]; dA / dB: device constants QlQlInvModqlDivqlModq / qlInvModq of the kept limbs;
-// negated: dA[i] == -dB[i] mod q_i (true for the reference's own tables).  ws: last[batch][N] (+ tmp[batch][l][N] on
-// the unfused path).
-//   fused (rings of two static passes, negated tables): x*B + NTT(SwitchModulus(last)*(-B)) == (x - NTT(SwitchModulus(last)))*B with
-//   canonical residues on both sides, so the words are the reference's.  4 launches: INTT of the last limb (2), the column pass
-//   that loads every limb from the one INTT row through SwitchModulus, the row pass whose store is (x - r)*B.  Neither the
-//   switched tower nor its transform goes to HBM outside `out`.
-// x1 / out1 != null: the towers are the two elements of one ciphertext, allocated on their own (x, x1 -> out, out1; batch must be 2):
-// the same launches, each over both towers.
-static fhe_status rescale_run(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, const TwPair* dA,
-                              const TwPair* dB, bool negated, uint32_t batch, uint64_t* out, uint64_t* ws, void* st,
-                              const uint64_t* x1 = nullptr, uint64_t* out1 = nullptr) {
+// the moduli of a tower over context limbs limbIdx[0..n) (null: the leading ones)
+static std::vector<uint64_t> tower_moduli(const fhe_ctx* c, const uint32_t* limbIdx, uint32_t n) {
+    std::vector<uint64_t> qs(n);
+    for (uint32_t i = 0; i < n; ++i)
+        qs[i] = c->q[limbIdx ? limbIdx[i] : i];
+    return qs;
+}
+// h += {v[i], Shoup(v[i], q[i])}, i < n
+static void append_pairs(std::vector<TwPair>& h, const uint64_t* v, const uint64_t* q, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i)
+        h.push_back(TwPair{v[i], host::shoup(v[i], q[i])});
+}
+// The argument checks of the family for the entry `who`: a tower of sizeQl limbs over context limbs limbIdx (null: the leading ones;
+// leading: and then within the context's own), of which the last `levels` are dropped and the first nOut produced (the single-limb entries
+// pass 1 and sizeQl - 1), and a workspace of wsNeed bytes for `batch` towers.  nonNull: the entry's own pointers.  The several-limb entries
+// report a limb index outside the context before a short workspace, the single-limb ones after it: callers see which text comes first.
+// "Removing last element ..." is the reference's text (dcrtpoly-impl.h:672-673).
+static fhe_status drop_check(const char* who, const fhe_ctx* c, bool nonNull, const uint32_t* limbIdx, bool leading, uint32_t sizeQl,
+                             uint32_t levels, uint32_t nOut, uint32_t batch, size_t wsBytes, size_t wsNeed, bool several) {
+    const std::string w(who);
+    ARG_CHECK(c && nonNull, w + ": null argument");
+    ARG_CHECK(sizeQl >= 2 && sizeQl <= (leading ? c->L : (uint32_t)kMaxLimbs), "Removing last element of DCRTPoly renders it invalid.");
+    ARG_CHECK(levels >= 1 && levels < sizeQl, w + ": levels must be in [1, sizeQl)");
+    ARG_CHECK(nOut >= 1 && nOut <= sizeQl - levels, w + ": nOut must be in [1, sizeQl - levels]");
+    bool limbsOk = true;
+    for (uint32_t i = 0; i < sizeQl; ++i)
+        limbsOk = limbsOk && (limbIdx ? limbIdx[i] : i) < c->L;
+    ARG_CHECK(limbsOk || !several, w + ": limb index exceeds context size");
+    ARG_CHECK(batch >= 1 && wsBytes >= wsNeed, w + ": workspace too small");
+    RT_CHECK(rt::set_device(c->device));
+    ARG_CHECK(limbsOk, w + ": limb index exceeds context size");
+    return FHE_OK;
+}
+
+// The forward transform of r into nOut limbs whose store is (x - NTT(r_i)) * C_i, r_i being the dropped limb(s) switched into limb i on the
+// way in: the one place that sets up the fused store of the family.
+//   rows   the dropped limbs in COEFFICIENT format, [batch][max(proRows, 1)][N]; row k is a limb modulo q[rowIdx[k]]
+//   proRows == 0: one row, r_i = SwitchModulus(row) (proC null: prologue mode 1) or SwitchModulus(row) * proC[i] (mode 2)
+//   proRows == d: r_i = sum_k SwitchModulus(row k) * proC[k * nOut + i] (mode 3; the caller has asked ntt_prologue_supported)
+//   x      the towers the store reads: xStride rows (or, xDelta != 0, xDelta words) apart, limb i in row i
+//   out0, out1   out1 null: dense out0[batch][nOut][N], the transform works in place there; else tower 0 -> out0, tower 1 -> out1 (batch 2)
+//                and the transform works in `work`, its fused store going to the two output towers
+// Two launches on a ring of two passes: the column pass with the prologue, the row pass with the epilogue.  N = 4096 has one pass and no
+// prologue: SwitchModulus (times proC) as a kernel of its own into the working tower, then the single pass with the fused store.
+static fhe_status drop_fused_store(fhe_ctx* c, const uint64_t* rows, const uint32_t* rowIdx, uint32_t proRows, const TwPair* proC,
+                                   const uint64_t* x, int64_t xDelta, uint32_t xStride, const TwPair* C, const uint32_t* limbIdx,
+                                   uint32_t nOut, uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* work, void* st, const char* who) {
+    NttEpilogue epi;
+    epi.mode = 1, epi.split = out1 ? 1 : batch, epi.aStride = xStride, epi.aFirst = 0, epi.aDelta = xDelta;
+    epi.A = x, epi.C = C, epi.out0 = out0, epi.out1 = out1 ? out1 : out0;
+    uint64_t* dst = out1 ? work : out0;
+    NttOpts fusedStore;
+    fusedStore.epi = &epi;
+    if (ntt_prologue_supported(c)) {
+        fusedStore.src.stride = proRows ? proRows : 1, fusedStore.src.first = 0;
+        fusedStore.proSrcLimb = rowIdx, fusedStore.proRows = proRows, fusedStore.proC = proC;
+        return ntt_run(c, false, rows, dst, limbIdx, nOut, batch, st, fusedStore);
+    }
+    LimbSel sel;
+    if (fhe_status s = make_sel(c, limbIdx, nOut, &sel, who))
+        return s;
+    if (fhe_status s = switch_modulus_run(c, dst, sel, nOut, rows, 1, 0, rowIdx[0], proC, batch, st))
+        return s;
+    return ntt_run(c, false, dst, dst, limbIdx, nOut, batch, st, fusedStore);
+}
+
+// The device constants of dropping ONE limb (one Shoup pair per kept limb unless noted), for the two members:
+//   DropLastElementAndScale (dcrtpoly-impl.h:693-712), CKKS:  out_i = x_i * B_i + NTT(SwitchModulus(last) * A_i)
+//     A = QlQlInvModqlDivqlModq, B = qlInvModq, no T and no row multiplier; evalFormat 1.
+//   ModReduce (dcrtpoly-impl.h:736-755), BGV with plaintext modulus t:
+//     delta = [last limb]_COEFF * (-t^-1 mod q_l);  out_i = (x_i + t * SwitchModulus(delta -> q_i)) * q_l^-1
+//     A = t * qlInvModq, B = qlInvModq, T = t mod q_i, rowUnfused = negtInvModq, rowFused = t^-1 mod q_l.
+struct DropTabs {
+    const TwPair* A;           // unfused: the switched row times A_i goes through the forward transform
+    const TwPair* B;           // the store's constant: x_i * B_i + NTT(..) unfused, (x_i - r_i) * B_i fused
+    const TwPair* T;           // fused: r_i = NTT(SwitchModulus(row) * T_i); null: no constant (prologue mode 1)
+    const TwPair* rowUnfused;  // one pair modulo q_l that the INTT row is multiplied by first; null: no such launch
+    const TwPair* rowFused;    // ... in the fused form
+    bool fusable;              // the rule of the entry (above), its *_UNFUSED switch folded in
+    const char* who;           // the member, for the texts of the launches' own errors
+};
+// x[batch][sizeQl][N] over context limbs limbIdx[0..sizeQl) (null: the leading ones) -> out[batch][sizeQl-1][N].  ws: last[batch][N] +
+// tmp[batch][l][N] (fhe_rescale_workspace_bytes).
+//   unfused (rings below 4096, COEFFICIENT towers, tables that are not fusable): x_i * B_i + NTT(SwitchModulus(row) * A_i), row = INTT of the
+//   last limb (times rowUnfused).  The NTT is linear and every step yields canonical residues, so the words equal the reference's.  Five
+//   launches for a CKKS tower on a ring of two passes, six for an EVALUATION BGV tower.
+//   fused (EVALUATION towers on rings of static passes): the shape (A - r) * C of the transform's epilogue (NttPassArgs::epi*),
+//     row   = INTT(x_l) (* rowFused)                     one row per tower
+//     r_i   = NTT(SwitchModulus(row -> q_i) (* T_i))
+//     out_i = (x_i - r_i) * B_i.
+//   CKKS: x*B + NTT(SwitchModulus(last)*(-B)) == (x - NTT(SwitchModulus(last)))*B with canonical residues on both sides.  4 launches.
+//   BGV: row is the canonical residue of -delta.  SwitchModulus is odd under negation for odd q_l: with h = floor(q_l / 2), v > h holds
+//   exactly when q_l - v <= h (v != 0), so the centred representative of q_l - v is minus that of v and SwitchModulus(q_l - v -> q_i) =
+//   -SwitchModulus(v -> q_i) mod q_i (0 maps to 0).  Hence r_i = -NTT(t * SwitchModulus(delta)) and out_i = (x_i + t * NTT(SwitchModulus(
+//   delta))) * q_l^-1 as residues; every step (the one-row product, the switch, the product by t mod q_i, the transform, the epilogue) yields
+//   the canonical residue, so the words are the reference's.  5 launches: the one-row product by t^-1 is kept a launch of its own (it is one
+//   row per tower, against 16 more multiplications per lane and limb inside the prologue).
+//   Neither the switched tower nor its transform goes to HBM outside `out` (drop_fused_store).
+// x1 / out1 != null: the two elements of one ciphertext, allocated on their own (batch must be 2): the same launches over both towers, or,
+// unfused, element by element.
+static fhe_status drop_last_run(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, const DropTabs& tb, int evalFormat,
+                                uint32_t batch, uint64_t* out, uint64_t* ws, void* st, const uint64_t* x1 = nullptr,
+                                uint64_t* out1 = nullptr) {
     const uint32_t l       = sizeQl - 1;
     const uint32_t lastIdx = limbIdx ? limbIdx[l] : l;
     uint64_t* last         = ws;                                 // [batch][N]
     uint64_t* tmp          = last + ((size_t)batch << c->logN);  // [batch][l][N]
-    static const bool noFuse = env_u32("FHE_RESCALE_UNFUSED", 0) != 0;
-    const bool fused = negated && !noFuse && ntt_epilogue_supported(c);
-    if (x1 && !fused) {  // (small rings, foreign tables: element by element)
-        if (fhe_status s = rescale_run(c, x, limbIdx, sizeQl, dA, dB, negated, 1, out, ws, st))
+    const bool fused       = evalFormat && tb.fusable && ntt_epilogue_supported(c);
+    if (x1 && !fused) {
+        if (fhe_status s = drop_last_run(c, x, limbIdx, sizeQl, tb, evalFormat, 1, out, ws, st))
             return s;
-        return rescale_run(c, x1, limbIdx, sizeQl, dA, dB, negated, 1, out1, ws, st);
+        return drop_last_run(c, x1, limbIdx, sizeQl, tb, evalFormat, 1, out1, ws, st);
     }
     const int64_t xDelta = x1 ? x1 - x : 0;
-    // lastPoly.SetFormat(COEFFICIENT)  (:696-697): INTT of the last limb of every tower, written densely
-    NttOpts lastRow;
-    lastRow.src.stride = sizeQl, lastRow.src.first = l, lastRow.srcDelta = xDelta;
-    if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
-        return s;
-    if (fused) {
-        NttEpilogue epi;
-        epi.mode = 1, epi.split = x1 ? 1 : batch, epi.aStride = sizeQl, epi.aFirst = 0, epi.aDelta = xDelta;
-        epi.A = x, epi.C = dB, epi.out0 = out, epi.out1 = x1 ? out1 : out;
-        // (two elements: the transform works in the workspace, its fused store goes to the two output towers)
-        uint64_t* work = x1 ? tmp : out;
-        NttOpts fusedStore;
-        fusedStore.epi = &epi;
-        if (ntt_prologue_supported(c)) {  // every limb from the one row of `last`
-            fusedStore.src.stride = 1, fusedStore.src.first = 0, fusedStore.proSrcLimb = &lastIdx;
-            return ntt_run(c, false, last, work, limbIdx, l, batch, st, fusedStore);
-        }
-        // the single pass of N = 4096: SwitchModulus as a kernel of its own, then the transform with the fused store
-        LimbSel sel;
-        if (fhe_status s = make_sel(c, limbIdx, l, &sel, "fhe_rescale"))
+    if (evalFormat) {  // lastPoly.SetFormat(COEFFICIENT)  (:696-697, :741): INTT of the last limb of every tower, written densely
+        NttOpts lastRow;
+        lastRow.src.stride = sizeQl, lastRow.src.first = l, lastRow.srcDelta = xDelta;
+        if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
             return s;
-        if (fhe_status s = switch_modulus_run(c, work, sel, l, last, 1, 0, lastIdx, nullptr, batch, st))
-            return s;
-        return ntt_run(c, false, work, work, limbIdx, l, batch, st, fusedStore);
     }
-    // tmp = SwitchModulus(last -> q_i) * QlQlInvModqlDivqlModq[i]   (:703-705)
+    else
+        RT_CHECK(rt::d2d_2d(last, (size_t)8 << c->logN, x + ((size_t)l << c->logN), ((size_t)sizeQl * 8) << c->logN,
+                            (size_t)8 << c->logN, batch, (rt::stream_t)st));
+    if (const TwPair* row = fused ? tb.rowFused : tb.rowUnfused)  // :742
+        if (fhe_status s = elem_run<OP_MUL_CONST>(c, last, last, nullptr, row, &lastIdx, 1, batch, st, tb.who))
+            return s;
+    if (fused)
+        return drop_fused_store(c, last, &lastIdx, 0, tb.T, x, xDelta, sizeQl, tb.B, limbIdx, l, batch, out, out1, tmp, st, tb.who);
+    // tmp = SwitchModulus(row -> q_i) * A_i   (:703-705; :749, :752 with t folded into A_i)
     LimbSel sel;
-    if (fhe_status s = make_sel(c, limbIdx, l, &sel, "fhe_rescale"))
+    if (fhe_status s = make_sel(c, limbIdx, l, &sel, tb.who))
         return s;
-    if (fhe_status s = switch_modulus_run(c, tmp, sel, l, last, 1, 0, lastIdx, dA, batch, st))
+    if (fhe_status s = switch_modulus_run(c, tmp, sel, l, last, 1, 0, lastIdx, tb.A, batch, st))
         return s;
-    // tmp.SwitchFormat()  (:706-707)
-    if (fhe_status s = fhe_ntt_fwd(c, tmp, limbIdx, l, batch, st))
-        return s;
-    // m_vectors[i] = m_vectors[i] * qlInvModq[i] + tmp  (:708-709); x towers are sizeQl rows apart
-    return elem_run<OP_MUL_CONST_ADD>(c, out, x, tmp, dB, limbIdx, l, batch, st, "fhe_rescale", sizeQl, 0);
+    if (evalFormat)  // tmp.SwitchFormat()  (:706-707, :750-751)
+        if (fhe_status s = fhe_ntt_fwd(c, tmp, limbIdx, l, batch, st))
+            return s;
+    // m_vectors[i] = m_vectors[i] * B_i + tmp  (:708-709, :752-753); x towers are sizeQl rows apart
+    return elem_run<OP_MUL_CONST_ADD>(c, out, x, tmp, tb.B, limbIdx, l, batch, st, tb.who, sizeQl, 0);
 }
+
+// ---- CKKS rescale ----
+// towers over the leading limbs, tables derived per sizeQl (and kept: a steady-state call derives and uploads nothing)
 extern "C" fhe_status fhe_rescale(fhe_ctx* c, const uint64_t* x, uint32_t sizeQl, uint32_t batch, uint64_t* out,
                                   void* wsv, size_t wsBytes, void* st) {
-    ARG_CHECK(c && x && out && wsv, "fhe_rescale: null argument");
-    ARG_CHECK(sizeQl >= 2 && sizeQl <= c->L, "Removing last element of DCRTPoly renders it invalid.");  // :672-673
-    ARG_CHECK(batch >= 1 && wsBytes >= fhe_rescale_workspace_bytes(c, sizeQl, batch), "fhe_rescale: workspace too small");
-    RT_CHECK(rt::set_device(c->device));
+    if (fhe_status s = drop_check("fhe_rescale", c, x && out && wsv, nullptr, true, sizeQl, 1, sizeQl - 1, batch, wsBytes,
+                                  fhe_rescale_workspace_bytes(c, sizeQl, batch), false))
+        return s;
     const uint32_t l = sizeQl - 1;
-    // tables (ckksrns-cryptoparameters.cpp:60-81): qlInvModq[i] = q_l^-1 mod q_i,
-    // QlQlInvModqlDivqlModq[i] = floor(Q'*(Q'^-1 mod q_l)/q_l) mod q_i = -(q_l^-1) mod q_i   
     std::unique_lock<std::mutex> lock(c->cacheMutex);
     auto it = c->rescaleTabs.find(sizeQl);
     if (it == c->rescaleTabs.end()) {
-        std::vector<TwPair> hA(l), hB(l);
-        for (uint32_t i = 0; i < l; ++i) {
-            const uint64_t qi = c->q[i];
-            const uint64_t B  = host::invmod(c->q[l] % qi, qi);
-            const uint64_t A  = (qi - B) % qi;
-            hA[i]             = TwPair{A, host::shoup(A, qi)};
-            hB[i]             = TwPair{B, host::shoup(B, qi)};
-        }
-        void *dA = nullptr, *dB = nullptr;
-        RT_CHECK(rt::dmalloc(&dA, l * sizeof(TwPair)));
-        c->owned.push_back(dA);
-        RT_CHECK(rt::dmalloc(&dB, l * sizeof(TwPair)));
-        c->owned.push_back(dB);
-        RT_CHECK(rt::h2d(dA, hA.data(), l * sizeof(TwPair), nullptr));
-        RT_CHECK(rt::h2d(dB, hB.data(), l * sizeof(TwPair), nullptr));
-        RT_CHECK(rt::sync(nullptr));
-        it = c->rescaleTabs.emplace(sizeQl, std::make_pair((TwPair*)dA, (TwPair*)dB)).first;
+        std::vector<uint64_t> A, B;
+        host::rescale_step_tables(c->q.data(), sizeQl, 1, A, B);
+        std::vector<TwPair> hA, hB;
+        append_pairs(hA, A.data(), c->q.data(), l), append_pairs(hB, B.data(), c->q.data(), l);
+        TwPair *dA = nullptr, *dB = nullptr;
+        fhe_status s;
+        if ((s = dev_copy(&c->owned, hA.data(), l, &dA)) || (s = dev_copy(&c->owned, hB.data(), l, &dB)))
+            return s;
+        it = c->rescaleTabs.emplace(sizeQl, std::make_pair(dA, dB)).first;
     }
-    TwPair *dA = it->second.first, *dB = it->second.second;
+    const DropTabs tb{it->second.first, it->second.second, nullptr, nullptr, nullptr, !rescale_unfused(), "fhe_rescale"};
     lock.unlock();
-    return rescale_run(c, x, nullptr, sizeQl, dA, dB, true, batch, out, (uint64_t*)wsv, st);
+    return drop_last_run(c, x, nullptr, sizeQl, tb, 1, batch, out, (uint64_t*)wsv, st);
 }
 // the same with the caller's tables (host arrays of sizeQl-1 residues: CryptoParametersRNS::GetQlQlInvModqlDivqlModq(l) /
 // GetqlInvModq(l)) over any limbs of the context: what the DCRTPoly backend's DropLastElementAndScale calls
 static fhe_status rescale_limbs_run(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
                                     const uint64_t* QlQlInvModqlDivqlModq, const uint64_t* qlInvModq, uint32_t batch, uint64_t* out,
                                     uint64_t* out1, void* wsv, size_t wsBytes, void* st, const char* who) {
-    ARG_CHECK(c && x && out && wsv && QlQlInvModqlDivqlModq && qlInvModq, std::string(who) + ": null argument");
-    ARG_CHECK(sizeQl >= 2 && sizeQl <= (uint32_t)kMaxLimbs, "Removing last element of DCRTPoly renders it invalid.");  // :672-673
-    ARG_CHECK(batch >= 1 && wsBytes >= fhe_rescale_workspace_bytes(c, sizeQl, batch), std::string(who) + ": workspace too small");
-    RT_CHECK(rt::set_device(c->device));
+    if (fhe_status s = drop_check(who, c, x && out && wsv && QlQlInvModqlDivqlModq && qlInvModq, limbIdx, false, sizeQl, 1, sizeQl - 1,
+                                  batch, wsBytes, fhe_rescale_workspace_bytes(c, sizeQl, batch), false))
+        return s;
     const uint32_t l = sizeQl - 1;
-    for (uint32_t i = 0; i < sizeQl; ++i)
-        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, std::string(who) + ": limb index exceeds context size");
-    bool negated = true;
-    for (uint32_t i = 0; i < l; ++i) {
-        const uint64_t qi = c->q[limbIdx ? limbIdx[i] : i];
-        negated           = negated && qlInvModq[i] < qi && QlQlInvModqlDivqlModq[i] == (qi - qlInvModq[i]) % qi;
-    }
-    const TwPair *dA = nullptr, *dB = nullptr;
+    DropTabs tb{};
+    tb.who     = "fhe_rescale";
+    tb.fusable = host::negated_pair(tower_moduli(c, limbIdx, l).data(), QlQlInvModqlDivqlModq, qlInvModq, l) && !rescale_unfused();
     if (fhe_status s = const_tables_trim(c))
         return s;
     std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
-    if (fhe_status s = const_table(c, limbIdx, QlQlInvModqlDivqlModq, l, &dA))
+    if (fhe_status s = const_table(c, limbIdx, QlQlInvModqlDivqlModq, l, &tb.A))
         return s;
-    if (fhe_status s = const_table(c, limbIdx, qlInvModq, l, &dB))
+    if (fhe_status s = const_table(c, limbIdx, qlInvModq, l, &tb.B))
         return s;
-    return rescale_run(c, x, limbIdx, sizeQl, dA, dB, negated, batch, out, (uint64_t*)wsv, st, x1, out1);
+    return drop_last_run(c, x, limbIdx, sizeQl, tb, 1, batch, out, (uint64_t*)wsv, st, x1, out1);
 }
 extern "C" fhe_status fhe_rescale_limbs(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl,
                                         const uint64_t* QlQlInvModqlDivqlModq, const uint64_t* qlInvModq, uint32_t batch,
@@ -3200,7 +3269,7 @@ extern "C" fhe_status fhe_rescale_limbs_pair(fhe_ctx* c, const uint64_t* x0, con
 // (:600-730) puts a scalar product in front and a LevelReduceInternalInPlace behind.  One call here: x[batch][sizeQl][N] EVALUATION, optionally
 // times the scalar's residues scale[sizeQl], rescaled by the last `levels` limbs, of which the first nOut limbs are produced.
 // ws: three regions of batch * sizeQl * N words each —
-//   R0  fused: INTT of the dropped limbs, rows[batch][d][N];  sequential: the workspace of rescale_run
+//   R0  fused: INTT of the dropped limbs, rows[batch][d][N];  sequential: the workspace of drop_last_run
 //   R1, R2  the towers between chunks / steps, alternating; the transform's working tower when the store goes to two output towers
 extern "C" size_t fhe_rescale_multi_workspace_bytes(const fhe_ctx* c, uint32_t sizeQl, uint32_t levels, uint32_t batch) {
     if (!c || sizeQl < 2 || levels < 1 || levels >= sizeQl)
@@ -3210,25 +3279,22 @@ extern "C" size_t fhe_rescale_multi_workspace_bytes(const fhe_ctx* c, uint32_t s
 // the caller's (or the derived) tables of step k: sizeQl-1-k residues at offset sum_{j<k} (sizeQl-1-j)
 static size_t rescale_multi_tab_offset(uint32_t sizeQl, uint32_t k) { return (size_t)k * (sizeQl - 1) - (size_t)k * (k ? k - 1 : 0) / 2; }
 // One chunk of d <= kMaxRescaleDrop limbs, fused: x is a tower of n limbs (towers n rows or xDelta words apart), limbs
-// limbIdx[0..n) of the context; out0 (and out1 != null: tower 1 goes there, batch must be 2) dense [.][nOut][N].  Five launches on a ring of
-// two passes: the two inverse passes over the d dropped limbs, the chain kernel, the column pass whose load sums the d switched rows, the row
-// pass whose store is (x - r) * C.
-static fhe_status rescale_multi_chunk(fhe_ctx* c, const uint64_t* x, int64_t xDelta, const uint32_t* limbIdx, uint32_t n, uint32_t d,
-                                      uint32_t nOut, const uint64_t* scale, uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* rows,
-                                      uint64_t* work, void* st) {
-    uint32_t dropIdx[kMaxRescaleDrop], rowIdx[kMaxRescaleDrop];  // step k drops limb n-1-k; row p of `rows` is limb n-d+p
+// limbIdx[0..n) of the context with moduli qs[0..n); out0 (and out1 != null: tower 1 goes there, batch must be 2) dense [.][nOut][N].  Five
+// launches on a ring of two passes: the two inverse passes over the d dropped limbs, the chain kernel, the column pass whose load sums the d
+// switched rows, the row pass whose store is (x - r) * C.
+static fhe_status rescale_multi_chunk(fhe_ctx* c, const uint64_t* x, int64_t xDelta, const uint32_t* limbIdx, const uint64_t* qs, uint32_t n,
+                                      uint32_t d, uint32_t nOut, const uint64_t* scale, uint32_t batch, uint64_t* out0, uint64_t* out1,
+                                      uint64_t* rows, uint64_t* work, void* st) {
+    uint32_t rowIdx[kMaxRescaleDrop];  // step k drops limb n-1-k; row p of `rows` is limb n-d+p
     uint64_t qDrop[kMaxRescaleDrop], sDrop[kMaxRescaleDrop];
     for (uint32_t k = 0; k < d; ++k) {
-        dropIdx[k] = limbIdx ? limbIdx[n - 1 - k] : n - 1 - k;
-        rowIdx[k]  = limbIdx ? limbIdx[n - d + k] : n - d + k;
-        qDrop[k]   = c->q[dropIdx[k]];
-        sDrop[k]   = scale ? scale[n - 1 - k] : 1;
+        rowIdx[k] = limbIdx ? limbIdx[n - d + k] : n - d + k;
+        qDrop[k]  = qs[n - 1 - k];
+        sDrop[k]  = scale ? scale[n - 1 - k] : 1;
     }
-    std::vector<uint64_t> qKeep(nOut), W(2 * (size_t)d * nOut), C(2 * (size_t)nOut);
-    for (uint32_t i = 0; i < nOut; ++i)
-        qKeep[i] = c->q[limbIdx ? limbIdx[i] : i];
+    std::vector<uint64_t> W(2 * (size_t)d * nOut), C(2 * (size_t)nOut);
     uint64_t B[2 * kMaxRescaleDrop * kMaxRescaleDrop], S[2 * kMaxRescaleDrop];
-    host::rescale_multi_tables(qDrop, d, qKeep.data(), nOut, scale ? sDrop : nullptr, scale, B, W.data(), C.data(), S);
+    host::rescale_multi_tables(qDrop, d, qs, nOut, scale ? sDrop : nullptr, scale, B, W.data(), C.data(), S);
     // device copies: the weights in the order of the rows (row p = step d-1-p), cached by content like every per-call table
     std::vector<uint32_t> wLimb((size_t)d * nOut);
     std::vector<uint64_t> wVal((size_t)d * nOut), cVal(nOut);
@@ -3261,28 +3327,20 @@ static fhe_status rescale_multi_chunk(fhe_ctx* c, const uint64_t* x, int64_t xDe
         FHE_LAUNCH(rescale_chain_kernel, tiles_for(c, batch), st, g);
         LAUNCH_CHECK();
     }
-    NttEpilogue epi;
-    epi.mode = 1, epi.split = out1 ? 1 : batch, epi.aStride = n, epi.aFirst = 0, epi.aDelta = xDelta;
-    epi.A = x, epi.C = dC, epi.out0 = out0, epi.out1 = out1 ? out1 : out0;
-    NttOpts fusedStore;
-    fusedStore.epi        = &epi;
-    fusedStore.src.stride = d, fusedStore.src.first = 0;
-    fusedStore.proSrcLimb = rowIdx, fusedStore.proRows = d, fusedStore.proC = dW;
-    return ntt_run(c, false, rows, out1 ? work : out0, limbIdx, nOut, batch, st, fusedStore);
+    return drop_fused_store(c, rows, rowIdx, d, dW, x, xDelta, n, dC, limbIdx, nOut, batch, out0, out1, work, st, "fhe_rescale_multi");
 }
 // derived: the tables are the negated pair of the true inverses at every step, i.e. what the library would compute itself; only then do the
-// steps collapse into the one-pass form.  tabA / tabB: host tables in the layout of fhe_rescale_multi_limbs.
-static fhe_status rescale_multi_run(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
-                                    uint32_t levels, uint32_t nOut, const uint64_t* scale, const uint64_t* tabA, const uint64_t* tabB,
-                                    bool derived, uint32_t batch, uint64_t* out, uint64_t* out1, uint64_t* ws, void* st) {
+// steps collapse into the one-pass form.  tabA / tabB: host tables in the layout of fhe_rescale_multi_limbs; qs: the tower's moduli.
+static fhe_status rescale_multi_run(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, const uint64_t* qs,
+                                    uint32_t sizeQl, uint32_t levels, uint32_t nOut, const uint64_t* scale, const uint64_t* tabA,
+                                    const uint64_t* tabB, bool derived, uint32_t batch, uint64_t* out, uint64_t* out1, uint64_t* ws, void* st) {
     const size_t region = ((size_t)batch * sizeQl) << c->logN;
     uint64_t *R0 = ws, *R[2] = {ws + region, ws + 2 * region};
-    static const bool noFuse = env_u32("FHE_RESCALE_UNFUSED", 0) != 0;
-    bool fused = derived && !noFuse && ntt_epilogue_supported(c) && ntt_prologue_supported(c);
+    bool fused = derived && !rescale_unfused() && ntt_epilogue_supported(c) && ntt_prologue_supported(c);
     for (uint32_t i = 0; scale && i < sizeQl; ++i)
         fused = fused && scale[i] != 0;  // (a zero residue has no inverse to put into the load's weights)
     if (levels == 1 && !scale && nOut == sizeQl - 1)
-        fused = false;  // the member itself: rescale_run's four launches
+        fused = false;  // the member itself: drop_last_run's four launches
     if (fused) {
         const uint64_t* cur = x;
         int64_t curDelta    = x1 ? x1 - x : 0;
@@ -3292,7 +3350,7 @@ static fhe_status rescale_multi_run(fhe_ctx* c, const uint64_t* x, const uint64_
             const bool lastOne  = left == d;
             const uint32_t keep = lastOne ? nOut : n - d;
             uint64_t* dst       = lastOne ? out : R[j & 1];
-            if (fhe_status s = rescale_multi_chunk(c, cur, curDelta, limbIdx, n, d, keep, j == 0 ? scale : nullptr, batch, dst,
+            if (fhe_status s = rescale_multi_chunk(c, cur, curDelta, limbIdx, qs, n, d, keep, j == 0 ? scale : nullptr, batch, dst,
                                                    lastOne ? out1 : nullptr, R0, R[j & 1], st))
                 return s;
             cur = dst, curDelta = 0, n -= d, left -= d, ++j;
@@ -3300,9 +3358,9 @@ static fhe_status rescale_multi_run(fhe_ctx* c, const uint64_t* x, const uint64_
         return FHE_OK;
     }
     if (x1) {  // element by element
-        if (fhe_status s = rescale_multi_run(c, x, nullptr, limbIdx, sizeQl, levels, nOut, scale, tabA, tabB, derived, 1, out, nullptr, ws, st))
+        if (fhe_status s = rescale_multi_run(c, x, nullptr, limbIdx, qs, sizeQl, levels, nOut, scale, tabA, tabB, derived, 1, out, nullptr, ws, st))
             return s;
-        return rescale_multi_run(c, x1, nullptr, limbIdx, sizeQl, levels, nOut, scale, tabA, tabB, derived, 1, out1, nullptr, ws, st);
+        return rescale_multi_run(c, x1, nullptr, limbIdx, qs, sizeQl, levels, nOut, scale, tabA, tabB, derived, 1, out1, nullptr, ws, st);
     }
     // the reference's loop: EvalMultCoreInPlace's scalar product, DropLastElementAndScale `levels` times, the limbs beyond nOut dropped
     const uint64_t* cur = x;
@@ -3317,19 +3375,16 @@ static fhe_status rescale_multi_run(fhe_ctx* c, const uint64_t* x, const uint64_
     uint32_t n = sizeQl;
     for (uint32_t k = 0; k < levels; ++k, --n) {
         const size_t off = rescale_multi_tab_offset(sizeQl, k);
-        bool negated     = true;
-        for (uint32_t i = 0; i + 1 < n; ++i) {
-            const uint64_t qi = c->q[limbIdx ? limbIdx[i] : i];
-            negated           = negated && tabA[off + i] == (qi - tabB[off + i]) % qi;
-        }
-        const TwPair *dA = nullptr, *dB = nullptr;
-        if (fhe_status s = const_table(c, limbIdx, tabA + off, n - 1, &dA))
+        DropTabs tb{};
+        tb.who     = "fhe_rescale";
+        tb.fusable = host::negated_pair(qs, tabA + off, tabB + off, n - 1) && !rescale_unfused();
+        if (fhe_status s = const_table(c, limbIdx, tabA + off, n - 1, &tb.A))
             return s;
-        if (fhe_status s = const_table(c, limbIdx, tabB + off, n - 1, &dB))
+        if (fhe_status s = const_table(c, limbIdx, tabB + off, n - 1, &tb.B))
             return s;
         const bool direct = k + 1 == levels && nOut == n - 1;
         uint64_t* dst     = direct ? out : R[k & 1];
-        if (fhe_status s = rescale_run(c, cur, limbIdx, n, dA, dB, negated, batch, dst, R0, st))
+        if (fhe_status s = drop_last_run(c, cur, limbIdx, n, tb, 1, batch, dst, R0, st))
             return s;
         cur = dst;
     }
@@ -3344,43 +3399,34 @@ static fhe_status rescale_multi_entry(fhe_ctx* c, const uint64_t* x, const uint6
                                       bool ownTables, uint32_t batch, uint64_t* out, uint64_t* out1, void* wsv, size_t wsBytes, void* st,
                                       const char* who) {
     const std::string w(who);
-    ARG_CHECK(c && x && out && wsv && (ownTables || (tabA && tabB)), w + ": null argument");
-    ARG_CHECK(sizeQl >= 2 && sizeQl <= (uint32_t)kMaxLimbs && (limbIdx || sizeQl <= c->L),
-              "Removing last element of DCRTPoly renders it invalid.");  // dcrtpoly-impl.h:672-673
-    ARG_CHECK(levels >= 1 && levels < sizeQl, w + ": levels must be in [1, sizeQl)");
-    ARG_CHECK(nOut >= 1 && nOut <= sizeQl - levels, w + ": nOut must be in [1, sizeQl - levels]");
-    for (uint32_t i = 0; i < sizeQl; ++i)
-        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, w + ": limb index exceeds context size");
-    ARG_CHECK(batch >= 1 && wsBytes >= fhe_rescale_multi_workspace_bytes(c, sizeQl, levels, batch), w + ": workspace too small");
+    if (fhe_status s = drop_check(who, c, x && out && wsv && (ownTables || (tabA && tabB)), limbIdx, !limbIdx, sizeQl, levels, nOut, batch,
+                                  wsBytes, fhe_rescale_multi_workspace_bytes(c, sizeQl, levels, batch), true))
+        return s;
     ARG_CHECK(out != x && out != x1 && (!out1 || (out1 != x && out1 != x1)), w + ": out must not alias x");
+    const std::vector<uint64_t> qs = tower_moduli(c, limbIdx, sizeQl);
     for (uint32_t i = 0; scale && i < sizeQl; ++i)
-        ARG_CHECK(scale[i] < c->q[limbIdx ? limbIdx[i] : i], w + ": scale is not reduced modulo its limb");
-    std::vector<uint64_t> ownA, ownB;
+        ARG_CHECK(scale[i] < qs[i], w + ": scale is not reduced modulo its limb");
+    std::vector<uint64_t> ownA, ownB;  // ckksrns-cryptoparameters.cpp:60-81 at every step
+    host::rescale_step_tables(qs.data(), sizeQl, levels, ownA, ownB);
     bool derived = true;
-    if (ownTables) {  // ckksrns-cryptoparameters.cpp:60-81 at every step
-        ownA.resize(rescale_multi_tab_offset(sizeQl, levels)), ownB.resize(ownA.size());
-        tabA = ownA.data(), tabB = ownB.data();
-    }
     for (uint32_t k = 0; k < levels; ++k) {
-        const uint64_t ql = c->q[limbIdx ? limbIdx[sizeQl - 1 - k] : sizeQl - 1 - k];
-        const size_t off  = rescale_multi_tab_offset(sizeQl, k);
-        for (uint32_t i = 0; i + 1 + k < sizeQl; ++i) {
-            const uint64_t qi  = c->q[limbIdx ? limbIdx[i] : i];
-            const uint64_t inv = ql % qi ? host::invmod(ql % qi, qi) : 0;
-            if (ownTables) {
-                ARG_CHECK(inv != 0, w + ": the moduli of a tower must be distinct");
-                ownB[off + i] = inv, ownA[off + i] = (qi - inv) % qi;
-                continue;
-            }
-            ARG_CHECK(tabA[off + i] < qi && tabB[off + i] < qi, w + ": table entry is not reduced modulo its limb");
-            derived = derived && inv != 0 && tabB[off + i] == inv && tabA[off + i] == (qi - inv) % qi;
+        const size_t off = rescale_multi_tab_offset(sizeQl, k);
+        const uint32_t n = sizeQl - 1 - k;
+        if (ownTables) {
+            ARG_CHECK(host::true_inverses(&ownB[off], &ownB[off], n), w + ": the moduli of a tower must be distinct");
+            continue;
         }
+        for (uint32_t i = 0; i < n; ++i)
+            ARG_CHECK(tabA[off + i] < qs[i] && tabB[off + i] < qs[i], w + ": table entry is not reduced modulo its limb");
+        derived = derived && host::true_inverses(&ownB[off], tabB + off, n) && host::negated_pair(qs.data(), tabA + off, tabB + off, n);
     }
-    RT_CHECK(rt::set_device(c->device));
+    if (ownTables)
+        tabA = ownA.data(), tabB = ownB.data();
     if (fhe_status s = const_tables_trim(c))
         return s;
     std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
-    return rescale_multi_run(c, x, x1, limbIdx, sizeQl, levels, nOut, scale, tabA, tabB, derived, batch, out, out1, (uint64_t*)wsv, st);
+    return rescale_multi_run(c, x, x1, limbIdx, qs.data(), sizeQl, levels, nOut, scale, tabA, tabB, derived, batch, out, out1, (uint64_t*)wsv,
+                             st);
 }
 extern "C" fhe_status fhe_rescale_multi(fhe_ctx* c, const uint64_t* x, uint32_t sizeQl, uint32_t levels, uint32_t nOut,
                                         const uint64_t* scale, uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes, void* st) {
@@ -3416,169 +3462,67 @@ extern "C" fhe_status fhe_rescale_multi_host_tables(const uint64_t* qDrop, uint3
     return FHE_OK;
 }
 
-// DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755), the BGV modulus switch by the last limb with plaintext modulus t:
-//   delta = [last limb]_COEFF * (-t^-1 mod q_l);  x_i = (x_i + t * SwitchModulus(delta -> q_i)) * q_l^-1,  i < l.
-// The device constants of one call (one Shoup pair per kept limb unless noted):
-struct ModReduceTabs {
-    const TwPair* A;     // t * qlInvModq[i] mod q_i                       (unfused)
-    const TwPair* B;     // qlInvModq[i]
-    const TwPair* T;     // t mod q_i                                      (fused)
-    const TwPair* neg;   // one pair modulo q_l: negtInvModq               (unfused)
-    const TwPair* pos;   // one pair modulo q_l: t^-1 mod q_l = -negtInvModq  (fused)
-    bool derived;        // B and neg are what the library derives from the moduli and t: the fused form computes the member's words
-};
-// x[batch][sizeQl][N] over context limbs limbIdx[0..sizeQl) (null: the leading ones) -> out[batch][sizeQl-1][N].  ws: last[batch][N] +
-// tmp[batch][l][N] (fhe_rescale_workspace_bytes).
-//   unfused (rings below 4096, COEFFICIENT towers, foreign tables): x_i * B_i + NTT(SwitchModulus(delta) * A_i).  The NTT is linear and every
-//   step yields canonical residues, so the words equal the reference's.  Six launches for an EVALUATION tower.
-//   fused (EVALUATION towers on rings of static passes, derived tables): the shape (A - r) * C of the transform's epilogue (NttPassArgs::epi*),
-//     d     = INTT(x_l) * (t^-1 mod q_l)                    one row per tower: the canonical residue of -delta
-//     r_i   = NTT((t mod q_i) * SwitchModulus(d -> q_i))
-//     out_i = (x_i - r_i) * q_l^-1.
-//   SwitchModulus is odd under negation for odd q_l: with h = floor(q_l / 2), v > h holds exactly when q_l - v <= h (v != 0), so the centred
-//   representative of q_l - v is minus that of v and SwitchModulus(q_l - v -> q_i) = -SwitchModulus(v -> q_i) mod q_i (0 maps to 0).  Hence
-//   r_i = -NTT(t * SwitchModulus(delta)) and out_i = (x_i + t * NTT(SwitchModulus(delta))) * q_l^-1 as residues; every step (the one-row
-//   product, the switch, the product by t mod q_i, the transform, the epilogue) yields the canonical residue, so the words are the reference's.
-//   Launches on rings of two passes: the two INTT passes of the dropped limb, the one-row product by t^-1 (kept a launch of its own: it is one
-//   row per tower, against 16 more multiplications per lane and limb inside the prologue), the column pass with prologue mode 2, the row pass
-//   with the epilogue.  Neither the switched tower nor its transform goes to HBM outside `out`.  N = 4096: the stand-alone switch kernel
-//   with the constant t mod q_i, then the single pass with the epilogue.
-// x1 / out1 != null: the two elements of one ciphertext, allocated on their own (batch must be 2): the same launches over both towers.
-static fhe_status mod_reduce_run(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, const ModReduceTabs& tb,
-                                 int evalFormat, uint32_t batch, uint64_t* out, uint64_t* ws, void* st, const uint64_t* x1 = nullptr,
-                                 uint64_t* out1 = nullptr) {
-    const uint32_t l       = sizeQl - 1;
-    const uint32_t lastIdx = limbIdx ? limbIdx[l] : l;
-    uint64_t* last         = ws;                                 // [batch][N]
-    uint64_t* tmp          = last + ((size_t)batch << c->logN);  // [batch][l][N]
-    static const bool noFuse = env_u32("FHE_MOD_REDUCE_UNFUSED", 0) != 0;
-    const bool fused = evalFormat && tb.derived && !noFuse && ntt_epilogue_supported(c);
-    if (x1 && !fused) {  // (small rings, COEFFICIENT towers, foreign tables: element by element)
-        if (fhe_status s = mod_reduce_run(c, x, limbIdx, sizeQl, tb, evalFormat, 1, out, ws, st))
-            return s;
-        return mod_reduce_run(c, x1, limbIdx, sizeQl, tb, evalFormat, 1, out1, ws, st);
-    }
-    const int64_t xDelta = x1 ? x1 - x : 0;
-    if (evalFormat) {  // delta.SetFormat(COEFFICIENT)  :741
-        NttOpts lastRow;
-        lastRow.src.stride = sizeQl, lastRow.src.first = l, lastRow.srcDelta = xDelta;
-        if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
-            return s;
-    }
-    else
-        RT_CHECK(rt::d2d_2d(last, (size_t)8 << c->logN, x + ((size_t)l << c->logN), ((size_t)sizeQl * 8) << c->logN,
-                            (size_t)8 << c->logN, batch, (rt::stream_t)st));
-    if (fhe_status s = elem_run<OP_MUL_CONST>(c, last, last, nullptr, fused ? tb.pos : tb.neg, &lastIdx, 1, batch, st, "fhe_mod_reduce"))  // :742
-        return s;
-    LimbSel sel;
-    if (fhe_status s = make_sel(c, limbIdx, l, &sel, "fhe_mod_reduce"))
-        return s;
-    if (fused) {
-        NttEpilogue epi;
-        epi.mode = 1, epi.split = x1 ? 1 : batch, epi.aStride = sizeQl, epi.aFirst = 0, epi.aDelta = xDelta;
-        epi.A = x, epi.C = tb.B, epi.out0 = out, epi.out1 = x1 ? out1 : out;
-        // (two elements: the transform works in the workspace, its fused store goes to the two output towers)
-        uint64_t* work = x1 ? tmp : out;
-        NttOpts fusedStore;
-        fusedStore.epi = &epi;
-        if (ntt_prologue_supported(c)) {  // every limb from the one row of `last`, times t mod q_i on the way in
-            fusedStore.src.stride = 1, fusedStore.src.first = 0, fusedStore.proSrcLimb = &lastIdx, fusedStore.proC = tb.T;
-            return ntt_run(c, false, last, work, limbIdx, l, batch, st, fusedStore);
-        }
-        // the single pass of N = 4096: SwitchModulus and the product by t mod q_i as a kernel of their own, then the transform with the fused store
-        if (fhe_status s = switch_modulus_run(c, work, sel, l, last, 1, 0, lastIdx, tb.T, batch, st))
-            return s;
-        return ntt_run(c, false, work, work, limbIdx, l, batch, st, fusedStore);
-    }
-    if (fhe_status s = switch_modulus_run(c, tmp, sel, l, last, 1, 0, lastIdx, tb.A, batch, st))  // :749, :752 (t folded into A_i)
-        return s;
-    if (evalFormat)  // :750-751
-        if (fhe_status s = fhe_ntt_fwd(c, tmp, limbIdx, l, batch, st))
-            return s;
-    return elem_run<OP_MUL_CONST_ADD>(c, out, x, tmp, tb.B, limbIdx, l, batch, st, "fhe_mod_reduce", sizeQl, 0);  // :752-753
-}
-// replaces DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755) on towers over the leading limbs, tables derived per (sizeQl, t)
+// ---- BGV ModReduce ----
+// replaces DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755) on towers over the leading limbs, tables derived per (sizeQl, t) and kept
 extern "C" fhe_status fhe_mod_reduce(fhe_ctx* c, const uint64_t* x, uint32_t sizeQl, uint64_t t, int evalFormat,
                                      uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes, void* st) {
-    ARG_CHECK(c && x && out && wsv, "fhe_mod_reduce: null argument");
-    ARG_CHECK(sizeQl >= 2 && sizeQl <= c->L, "Removing last element of DCRTPoly renders it invalid.");  // :672-673
-    ARG_CHECK(batch >= 1 && wsBytes >= fhe_rescale_workspace_bytes(c, sizeQl, batch), "fhe_mod_reduce: workspace too small");
-    RT_CHECK(rt::set_device(c->device));
+    if (fhe_status s = drop_check("fhe_mod_reduce", c, x && out && wsv, nullptr, true, sizeQl, 1, sizeQl - 1, batch, wsBytes,
+                                  fhe_rescale_workspace_bytes(c, sizeQl, batch), false))
+        return s;
     const uint32_t l  = sizeQl - 1;
     const uint64_t ql = c->q[l];
     ARG_CHECK(t >= 2 && t % ql != 0, "fhe_mod_reduce: t must be invertible modulo the dropped limb");
     std::unique_lock<std::mutex> lock(c->cacheMutex);
     auto it = c->modReduceTabs.find({sizeQl, t});
     if (it == c->modReduceTabs.end()) {
-        std::vector<TwPair> h(3 * (size_t)l + 2);
-        for (uint32_t i = 0; i < l; ++i) {
-            const uint64_t qi = c->q[i];
-            const uint64_t B  = host::invmod(ql % qi, qi);      // qlInvModq
-            const uint64_t A  = host::mulmod(t % qi, B, qi);
-            h[i]              = TwPair{A, host::shoup(A, qi)};
-            h[l + i]          = TwPair{B, host::shoup(B, qi)};
-            h[2 * (size_t)l + 2 + i] = TwPair{t % qi, host::shoup(t % qi, qi)};  // (t > q_i: its residue)
-        }
-        const uint64_t tInv    = host::invmod(t % ql, ql);
-        const uint64_t negtInv = (ql - tInv) % ql;  // negtInvModq
-        h[2 * (size_t)l]       = TwPair{negtInv, host::shoup(negtInv, ql)};
-        h[2 * (size_t)l + 1]   = TwPair{tInv, host::shoup(tInv, ql)};
-        void* d = nullptr;
-        RT_CHECK(rt::dmalloc(&d, h.size() * sizeof(TwPair)));
-        c->owned.push_back(d);
-        RT_CHECK(rt::h2d(d, h.data(), h.size() * sizeof(TwPair), nullptr));
-        RT_CHECK(rt::sync(nullptr));
-        it = c->modReduceTabs.emplace(std::make_pair(sizeQl, t), (TwPair*)d).first;
+        const host::ModReduceTables own = host::mod_reduce_tables(c->q.data(), sizeQl, t, nullptr);
+        std::vector<TwPair> h;  // (the layout of fhe_ctx::modReduceTabs)
+        append_pairs(h, own.A.data(), c->q.data(), l), append_pairs(h, own.B.data(), c->q.data(), l);
+        append_pairs(h, &own.negtInv, &ql, 1), append_pairs(h, &own.tInv, &ql, 1), append_pairs(h, own.T.data(), c->q.data(), l);
+        TwPair* d = nullptr;
+        if (fhe_status s = dev_copy(&c->owned, h.data(), h.size(), &d))
+            return s;
+        it = c->modReduceTabs.emplace(std::make_pair(sizeQl, t), d).first;
     }
     const TwPair* d = it->second;
     lock.unlock();
-    const ModReduceTabs tb{d, d + l, d + 2 * (size_t)l + 2, d + 2 * (size_t)l, d + 2 * (size_t)l + 1, true};
-    return mod_reduce_run(c, x, nullptr, sizeQl, tb, evalFormat, batch, out, (uint64_t*)wsv, st);
+    const DropTabs tb{d, d + l, d + 2 * (size_t)l + 2, d + 2 * (size_t)l, d + 2 * (size_t)l + 1, !mod_reduce_unfused(), "fhe_mod_reduce"};
+    return drop_last_run(c, x, nullptr, sizeQl, tb, evalFormat, batch, out, (uint64_t*)wsv, st);
 }
 // the same with the caller's tables over any limbs of the context, as DCRTPoly::ModReduce receives them (t, negtInvModq = -t^-1 mod q_l,
-// qlInvModq[i] = q_l^-1 mod q_i for the sizeQl-1 kept limbs: CryptoParametersBGVRNS::GetNegtInvModq(l) / GetqlInvModq(l)).  Fused exactly
-// when the tables are the ones the library would derive itself (the rule of `negated` in rescale_limbs_run); any other tables run the
-// member's formula with the given values, launch by launch.
+// qlInvModq[i] = q_l^-1 mod q_i for the sizeQl-1 kept limbs: CryptoParametersBGVRNS::GetNegtInvModq(l) / GetqlInvModq(l))
 static fhe_status mod_reduce_limbs_run(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t,
                                        uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint32_t batch, uint64_t* out,
                                        uint64_t* out1, void* wsv, size_t wsBytes, void* st, const char* who) {
-    ARG_CHECK(c && x && out && wsv && qlInvModq, std::string(who) + ": null argument");
-    ARG_CHECK(sizeQl >= 2 && sizeQl <= (uint32_t)kMaxLimbs, "Removing last element of DCRTPoly renders it invalid.");  // :672-673
-    ARG_CHECK(batch >= 1 && wsBytes >= fhe_rescale_workspace_bytes(c, sizeQl, batch), std::string(who) + ": workspace too small");
-    RT_CHECK(rt::set_device(c->device));
-    const uint32_t l = sizeQl - 1;
-    for (uint32_t i = 0; i < sizeQl; ++i)
-        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, std::string(who) + ": limb index exceeds context size");
-    const uint32_t lastIdx = limbIdx ? limbIdx[l] : l;
-    const uint64_t ql      = c->q[lastIdx];
+    if (fhe_status s = drop_check(who, c, x && out && wsv && qlInvModq, limbIdx, false, sizeQl, 1, sizeQl - 1, batch, wsBytes,
+                                  fhe_rescale_workspace_bytes(c, sizeQl, batch), false))
+        return s;
+    const uint32_t l               = sizeQl - 1;
+    const uint32_t lastIdx         = limbIdx ? limbIdx[l] : l;
+    const std::vector<uint64_t> qs = tower_moduli(c, limbIdx, sizeQl);
+    const uint64_t ql              = qs[l];
     ARG_CHECK(t >= 2 && t % ql != 0, std::string(who) + ": t must be invertible modulo the dropped limb");
     ARG_CHECK(negtInvModq < ql, std::string(who) + ": negtInvModq is not reduced modulo the dropped limb");
-    const uint64_t tInv = host::invmod(t % ql, ql);
-    bool derived        = negtInvModq == (ql - tInv) % ql;
-    std::vector<uint64_t> vA(l), vT(l);
-    for (uint32_t i = 0; i < l; ++i) {
-        const uint64_t qi = c->q[limbIdx ? limbIdx[i] : i];
-        ARG_CHECK(qlInvModq[i] < qi, std::string(who) + ": qlInvModq is not reduced modulo its limb");
-        derived = derived && qi != ql && qlInvModq[i] == host::invmod(ql % qi, qi);
-        vT[i]   = t % qi;
-        vA[i]   = host::mulmod(vT[i], qlInvModq[i], qi);
-    }
-    ModReduceTabs tb{};
-    tb.derived = derived;
+    for (uint32_t i = 0; i < l; ++i)
+        ARG_CHECK(qlInvModq[i] < qs[i], std::string(who) + ": qlInvModq is not reduced modulo its limb");
+    const host::ModReduceTables own = host::mod_reduce_tables(qs.data(), sizeQl, t, qlInvModq);  // (A from the caller's inverses)
+    DropTabs tb{};
+    tb.who     = "fhe_mod_reduce";
+    tb.fusable = negtInvModq == own.negtInv && host::true_inverses(own.B.data(), qlInvModq, l) && !mod_reduce_unfused();
     if (fhe_status s = const_tables_trim(c))
         return s;
     std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
-    if (fhe_status s = const_table(c, limbIdx, vA.data(), l, &tb.A))
+    if (fhe_status s = const_table(c, limbIdx, own.A.data(), l, &tb.A))
         return s;
     if (fhe_status s = const_table(c, limbIdx, qlInvModq, l, &tb.B))
         return s;
-    if (fhe_status s = const_table(c, limbIdx, vT.data(), l, &tb.T))
+    if (fhe_status s = const_table(c, limbIdx, own.T.data(), l, &tb.T))
         return s;
-    if (fhe_status s = const_table(c, &lastIdx, &negtInvModq, 1, &tb.neg))
+    if (fhe_status s = const_table(c, &lastIdx, &negtInvModq, 1, &tb.rowUnfused))
         return s;
-    if (fhe_status s = const_table(c, &lastIdx, &tInv, 1, &tb.pos))
+    if (fhe_status s = const_table(c, &lastIdx, &own.tInv, 1, &tb.rowFused))
         return s;
-    return mod_reduce_run(c, x, limbIdx, sizeQl, tb, evalFormat, batch, out, (uint64_t*)wsv, st, x1, out1);
+    return drop_last_run(c, x, limbIdx, sizeQl, tb, evalFormat, batch, out, (uint64_t*)wsv, st, x1, out1);
 }
 extern "C" fhe_status fhe_mod_reduce_limbs(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t,
                                            uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint32_t batch, uint64_t* out,
@@ -3607,16 +3551,6 @@ struct fhe_sr_plan {
     double* d_frac  = nullptr;
     std::vector<void*> owned;
 };
-template <typename T>
-static fhe_status dev_copy(std::vector<void*>& owned, const T* h, size_t n, T** d) {
-    void* p = nullptr;
-    RT_CHECK(rt::dmalloc(&p, n * sizeof(T)));
-    owned.push_back(p);
-    RT_CHECK(rt::h2d(p, h, n * sizeof(T), nullptr));
-    RT_CHECK(rt::sync(nullptr));
-    *d = (T*)p;
-    return FHE_OK;
-}
 extern "C" fhe_status fhe_sr_plan_create(fhe_ctx* c, uint32_t sizeI, const uint32_t* outLimbIdx, uint32_t sizeO,
                                          const uint64_t* tab, const double* frac, fhe_sr_plan** out) {
     ARG_CHECK(c && outLimbIdx && tab && out, "fhe_sr_plan_create: null argument");
@@ -3632,8 +3566,8 @@ extern "C" fhe_status fhe_sr_plan_create(fhe_ctx* c, uint32_t sizeI, const uint3
     fhe_sr_plan* p = new fhe_sr_plan;
     p->ctx = c, p->sizeI = sizeI, p->sizeO = sizeO, p->exact = frac != nullptr;
     fhe_status s;
-    if ((s = dev_copy(p->owned, tab, (size_t)sizeO * (sizeI + 1), &p->d_tab)) || (s = dev_copy(p->owned, o.data(), o.size(), &p->d_o)) ||
-        (s = dev_copy(p->owned, mu.data(), mu.size(), &p->d_mu)) || (frac && (s = dev_copy(p->owned, frac, sizeI, &p->d_frac)))) {
+    if ((s = dev_copy(&p->owned, tab, (size_t)sizeO * (sizeI + 1), &p->d_tab)) || (s = dev_copy(&p->owned, o.data(), o.size(), &p->d_o)) ||
+        (s = dev_copy(&p->owned, mu.data(), mu.size(), &p->d_mu)) || (frac && (s = dev_copy(&p->owned, frac, sizeI, &p->d_frac)))) {
         fhe_sr_plan_destroy(p);
         return s;
     }
@@ -3932,14 +3866,14 @@ extern "C" fhe_status fhe_behz_create(fhe_ctx* c, const uint32_t* qLimbIdx, uint
     fhe_status s;
     uint64_t *dq, *dbsk, *dmuQ, *dmuB, *d1, *d2, *d3, *d4, *d5;
     TwPair *p1, *p2, *p3, *p4, *p5, *p6, *p7;
-    if ((s = dev_copy(h->owned, qPad.data(), qPad.size(), &dq)) || (s = dev_copy(h->owned, bskPad.data(), bskPad.size(), &dbsk)) ||
-        (s = dev_copy(h->owned, muQ.data(), muQ.size(), &dmuQ)) || (s = dev_copy(h->owned, muBsk.data(), muBsk.size(), &dmuB)) ||
-        (s = dev_copy(h->owned, QHatModbsk.data(), QHatModbsk.size(), &d1)) || (s = dev_copy(h->owned, QHatModmt.data(), QHatModmt.size(), &d2)) ||
-        (s = dev_copy(h->owned, qInvModbsk.data(), qInvModbsk.size(), &d3)) || (s = dev_copy(h->owned, BHatModmsk.data(), BHatModmsk.size(), &d4)) ||
-        (s = dev_copy(h->owned, BHatModq.data(), BHatModq.size(), &d5)) || (s = dev_copy(h->owned, mtQHatInv.data(), mtQHatInv.size(), &p1)) ||
-        (s = dev_copy(h->owned, tQHatInv.data(), tQHatInv.size(), &p2)) || (s = dev_copy(h->owned, BModq.data(), BModq.size(), &p3)) ||
-        (s = dev_copy(h->owned, QModbsk.data(), QModbsk.size(), &p4)) || (s = dev_copy(h->owned, mtInvModbsk.data(), mtInvModbsk.size(), &p5)) ||
-        (s = dev_copy(h->owned, tQInvModbsk.data(), tQInvModbsk.size(), &p6)) || (s = dev_copy(h->owned, BHatInv.data(), BHatInv.size(), &p7))) {
+    if ((s = dev_copy(&h->owned, qPad.data(), qPad.size(), &dq)) || (s = dev_copy(&h->owned, bskPad.data(), bskPad.size(), &dbsk)) ||
+        (s = dev_copy(&h->owned, muQ.data(), muQ.size(), &dmuQ)) || (s = dev_copy(&h->owned, muBsk.data(), muBsk.size(), &dmuB)) ||
+        (s = dev_copy(&h->owned, QHatModbsk.data(), QHatModbsk.size(), &d1)) || (s = dev_copy(&h->owned, QHatModmt.data(), QHatModmt.size(), &d2)) ||
+        (s = dev_copy(&h->owned, qInvModbsk.data(), qInvModbsk.size(), &d3)) || (s = dev_copy(&h->owned, BHatModmsk.data(), BHatModmsk.size(), &d4)) ||
+        (s = dev_copy(&h->owned, BHatModq.data(), BHatModq.size(), &d5)) || (s = dev_copy(&h->owned, mtQHatInv.data(), mtQHatInv.size(), &p1)) ||
+        (s = dev_copy(&h->owned, tQHatInv.data(), tQHatInv.size(), &p2)) || (s = dev_copy(&h->owned, BModq.data(), BModq.size(), &p3)) ||
+        (s = dev_copy(&h->owned, QModbsk.data(), QModbsk.size(), &p4)) || (s = dev_copy(&h->owned, mtInvModbsk.data(), mtInvModbsk.size(), &p5)) ||
+        (s = dev_copy(&h->owned, tQInvModbsk.data(), tQInvModbsk.size(), &p6)) || (s = dev_copy(&h->owned, BHatInv.data(), BHatInv.size(), &p7))) {
         fhe_behz_destroy(h);
         return s;
     }
@@ -3966,7 +3900,7 @@ static fhe_status behz_pairs(fhe_behz* h, const uint64_t* v, const uint64_t* mod
         t[i]             = TwPair{w, host::shoup(w, mod[i])};
     }
     TwPair* d = nullptr;
-    if (fhe_status s = dev_copy(h->owned, t.data(), t.size(), &d))
+    if (fhe_status s = dev_copy(&h->owned, t.data(), t.size(), &d))
         return s;
     *slot = d;
     return FHE_OK;
@@ -3979,7 +3913,7 @@ static fhe_status behz_matrix(fhe_behz* h, const uint64_t* m, uint32_t nRow, uin
         for (uint32_t j = 0; j < nCol; ++j)
             t[(size_t)j * W + i] = m[(size_t)i * nCol + j] % colMod[j];
     uint64_t* d = nullptr;
-    if (fhe_status s = dev_copy(h->owned, t.data(), t.size(), &d))
+    if (fhe_status s = dev_copy(&h->owned, t.data(), t.size(), &d))
         return s;
     *slot = d;
     return FHE_OK;
@@ -4007,7 +3941,7 @@ extern "C" fhe_status fhe_behz_override_q_to_bsk(fhe_behz* h, const uint64_t* mt
     std::vector<uint64_t> mt(h->tb.W, 0);
     std::copy(QHatModmtilde, QHatModmtilde + h->numQ, mt.begin());
     uint64_t* d = nullptr;
-    if ((s = dev_copy(h->owned, mt.data(), mt.size(), &d)))
+    if ((s = dev_copy(&h->owned, mt.data(), mt.size(), &d)))
         return s;
     h->tb.QHatModmt    = d;
     h->tb.negQInvModmt = negQInvModmtilde;
@@ -4043,7 +3977,7 @@ extern "C" fhe_status fhe_behz_override_conv_sk(fhe_behz* h, const uint64_t* BHa
     for (uint32_t i = 0; i < numB; ++i)
         bm[i] = BHatModmsk[i] % msk;
     uint64_t* d = nullptr;
-    if ((s = dev_copy(h->owned, bm.data(), bm.size(), &d)))
+    if ((s = dev_copy(&h->owned, bm.data(), bm.size(), &d)))
         return s;
     h->tb.BHatModmsk = d;
     h->tb.BInvModmsk = TwPair{BInvModmsk % msk, host::shoup(BInvModmsk % msk, msk)};
@@ -4360,10 +4294,10 @@ static fhe_status hps_switch_tables(fhe_hps* h, const std::vector<uint64_t>& S, 
     uint64_t *d1, *d2, *d3, *d4, *d5;
     double* f1;
     fhe_status s;
-    if ((s = dev_copy(h->owned, hatInv.data(), W, &p1)) || (s = dev_copy(h->owned, srcQ.data(), W, &d1)) ||
-        (s = dev_copy(h->owned, inv.data(), W, &f1)) || (s = dev_copy(h->owned, hatMod.data(), hatMod.size(), &d2)) ||
-        (s = dev_copy(h->owned, D.data(), nD, &d3)) || (s = dev_copy(h->owned, mu.data(), mu.size(), &d4)) ||
-        (s = dev_copy(h->owned, c.alpha.data(), c.alpha.size(), &d5)))
+    if ((s = dev_copy(&h->owned, hatInv.data(), W, &p1)) || (s = dev_copy(&h->owned, srcQ.data(), W, &d1)) ||
+        (s = dev_copy(&h->owned, inv.data(), W, &f1)) || (s = dev_copy(&h->owned, hatMod.data(), hatMod.size(), &d2)) ||
+        (s = dev_copy(&h->owned, D.data(), nD, &d3)) || (s = dev_copy(&h->owned, mu.data(), mu.size(), &d4)) ||
+        (s = dev_copy(&h->owned, c.alpha.data(), c.alpha.size(), &d5)))
         return s;
     *out = HpsSwitchTables{p1, d1, f1, d2, d3, d4, d5, (uint32_t)nS, (uint32_t)nD};
     return FHE_OK;
@@ -4387,9 +4321,9 @@ static fhe_status hps_scale_tables(fhe_hps* h, const std::vector<uint64_t>& I, c
     TwPair* p1;
     double* f1;
     fhe_status s;
-    if ((s = dev_copy(h->owned, t16.data(), t16.size(), &d1)) || (s = dev_copy(h->owned, last.data(), W, &p1)) ||
-        (s = dev_copy(h->owned, f.data(), W, &f1)) || (s = dev_copy(h->owned, o.data(), W, &d2)) ||
-        (s = dev_copy(h->owned, mu.data(), mu.size(), &d3)))
+    if ((s = dev_copy(&h->owned, t16.data(), t16.size(), &d1)) || (s = dev_copy(&h->owned, last.data(), W, &p1)) ||
+        (s = dev_copy(&h->owned, f.data(), W, &f1)) || (s = dev_copy(&h->owned, o.data(), W, &d2)) ||
+        (s = dev_copy(&h->owned, mu.data(), mu.size(), &d3)))
         return s;
     *out = HpsScaleTables{d1, p1, f1, d2, d3, (uint32_t)nI, (uint32_t)nO};
     return FHE_OK;
@@ -4526,9 +4460,9 @@ extern "C" fhe_status fhe_hps_create(fhe_ctx* c, const uint32_t* qLimbIdx, uint3
             }
             TwPair* p1;
             uint64_t *d1, *d2, *d3, *d4;
-            if ((s = dev_copy(h->owned, hi.data(), W, &p1)) || (s = dev_copy(h->owned, sq.data(), W, &d1)) ||
-                (s = dev_copy(h->owned, hm.data(), hm.size(), &d2)) || (s = dev_copy(h->owned, rr.data(), W, &d3)) ||
-                (s = dev_copy(h->owned, mu.data(), mu.size(), &d4)))
+            if ((s = dev_copy(&h->owned, hi.data(), W, &p1)) || (s = dev_copy(&h->owned, sq.data(), W, &d1)) ||
+                (s = dev_copy(&h->owned, hm.data(), hm.size(), &d2)) || (s = dev_copy(&h->owned, rr.data(), W, &d3)) ||
+                (s = dev_copy(&h->owned, mu.data(), mu.size(), &d4)))
                 break;
             v.exHatInv = p1, v.exSrcQ = d1, v.exHatMod = d2, v.exR = d3, v.exMuR = d4;
         }

@@ -63,6 +63,54 @@ uint64_t min_root_of_unity(uint64_t m, uint64_t q);
 // product of mods[k] (k in sel, k != skip) reduced mod `mod`
 uint64_t prod_mod(const std::vector<uint64_t>& mods, int skip, uint64_t mod);
 
+// ---- the reference's per-level tables of dropping the last limb of a tower over moduli q[0..n) ----
+// q_l^-1 mod q_i, the one value all of them are made of.  0 when q_i == q_l: equal moduli have no inverse, and no table holds a zero otherwise.
+inline uint64_t dropped_inv(uint64_t ql, uint64_t qi) { return invmod(ql % qi, qi); }
+// CKKS (ckksrns-cryptoparameters.cpp:60-81), for the first `levels` steps, step k dropping q[n-1-k]: its n-1-k residues follow those of
+// step k-1 (the layout of fhe_rescale_multi_limbs).  B = qlInvModq[i] = q_l^-1 mod q_i;
+// A = QlQlInvModqlDivqlModq[i] = floor(Q' * (Q'^-1 mod q_l) / q_l) mod q_i = -(q_l^-1) mod q_i   
+inline void rescale_step_tables(const uint64_t* q, uint32_t n, uint32_t levels, std::vector<uint64_t>& A, std::vector<uint64_t>& B) {
+    A.clear(), B.clear();
+    for (uint32_t k = 0; k < levels; ++k)
+        for (uint32_t i = 0; i + 1 + k < n; ++i) {
+            B.push_back(dropped_inv(q[n - 1 - k], q[i]));
+            A.push_back((q[i] - B.back()) % q[i]);
+        }
+}
+// BGV with plaintext modulus t (bgvrns-cryptoparameters.cpp, DCRTPolyImpl::ModReduce): B = qlInvModq[i], T[i] = t mod q_i (t > q_i: its
+// residue), tInv = t^-1 mod q_l, negtInv = negtInvModq = -tInv mod q_l, and A[i] = t * inv_i mod q_i, where inv is callerB (the inverses a
+// caller handed in, reduced) or, when that is null, B.
+struct ModReduceTables {
+    std::vector<uint64_t> A, B, T;
+    uint64_t tInv, negtInv;
+};
+inline ModReduceTables mod_reduce_tables(const uint64_t* q, uint32_t n, uint64_t t, const uint64_t* callerB) {
+    const uint32_t l  = n - 1;
+    const uint64_t ql = q[l];
+    ModReduceTables r{std::vector<uint64_t>(l), std::vector<uint64_t>(l), std::vector<uint64_t>(l), invmod(t % ql, ql), 0};
+    r.negtInv = (ql - r.tInv) % ql;
+    for (uint32_t i = 0; i < l; ++i) {
+        r.B[i] = dropped_inv(ql, q[i]);
+        r.T[i] = t % q[i];
+        r.A[i] = mulmod(r.T[i], callerB ? callerB[i] : r.B[i], q[i]);
+    }
+    return r;
+}
+// A[i] == -B[i] mod q[i], B reduced: the pair for which x*B + r*A == (x - r)*B
+inline bool negated_pair(const uint64_t* q, const uint64_t* A, const uint64_t* B, uint32_t n) {
+    bool ok = true;
+    for (uint32_t i = 0; i < n; ++i)
+        ok = ok && B[i] < q[i] && A[i] == (q[i] - B[i]) % q[i];
+    return ok;
+}
+// B holds the true inverses `own` (dropped_inv of the same moduli), none of them the zero of an equal modulus
+inline bool true_inverses(const uint64_t* own, const uint64_t* B, uint32_t n) {
+    bool ok = true;
+    for (uint32_t i = 0; i < n; ++i)
+        ok = ok && own[i] != 0 && B[i] == own[i];
+    return ok;
+}
+
 // Constants of a rescale by d limbs in one pass (LeveledSHECKKSRNS::ModReduceInternalInPlace, ckksrns-leveledshe.cpp:172-191, as one
 // step).  qDrop[k]: the modulus dropped at step k (the last limb first), qKeep[i]: the limbs that are produced,
 // sKeep / sDrop: residues of the scalar the tower is multiplied by first (null: none; every sKeep[i] must be non-zero).
