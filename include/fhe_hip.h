@@ -487,6 +487,35 @@ fhe_status fhe_mod_reduce_limbs(fhe_ctx* ctx, const uint64_t* x, const uint32_t*
 fhe_status fhe_mod_reduce_limbs_pair(fhe_ctx* ctx, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
                                      uint64_t t, uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint64_t* out0,
                                      uint64_t* out1, void* ws, size_t wsBytes, void* stream);
+/* BGV decryption: the ModReduce chain down to one limb, and its residues modulo t, without a tower between the steps.
+ * PKEBGVRNS::Decrypt (bgvrns-pke.cpp:44-99) and MultipartyBGVRNS::MultipartyDecryptFusion (bgvrns-multiparty.cpp:62-97) switch
+ * b = c0 + c1*s (+ c2*s^2) to COEFFICIENT, call DCRTPolyImpl::ModReduce sizeQl - 1 times and take DecryptionCRTInterpolate(t) of the
+ * limb that is left.  Here one launch of mod_reduce_chain_kernel runs up to 16 of those steps: the deltas of the dropped limbs stay in
+ * registers, every kept limb is read once and written once.  The tables (negtInvModq, qlInvModq, t mod q_i of every step, multiplied
+ * out) are the library's own, derived from the moduli and t and kept per (limb list, t, steps).  All towers are COEFFICIENT, all words in
+ * and out canonical; every comparison with the member's loop is word for word.
+ *
+ * fhe_mod_reduce_chain: `levels` consecutive DCRTPolyImpl::ModReduce calls (dcrtpoly-impl.h:736-755), the words of `levels` calls of
+ * fhe_mod_reduce with evalFormat 0: x [batch][sizeQl][N] over limbIdx[sizeQl] (NULL = the leading limbs), the last limb dropped first;
+ * out [batch][sizeQl-levels][N].  What the COEFFICIENT branch of Decrypt (bgvrns-pke.cpp:73-81) runs on every element.  More than 16
+ * levels run in chunks of 16 through ws (fhe_mod_reduce_chain_workspace_bytes; 0 bytes, and ws may be NULL, up to 16 levels).
+ * fhe_mod_reduce_to_t: the whole chain (sizeQl - 1 steps; sizeQl == 1: none) and then (x_0 > floor(q_0/2) ? x_0 - q_0 : x_0) mod t in
+ * [0, t), NativeVector::Mod(t) of DecryptionCRTInterpolate (mubintvecnat.cpp:145-161, 351-356): out [batch][N].  ws as for
+ * fhe_mod_reduce_chain with levels = sizeQl - 1.  Serves MultipartyDecryptFusion after the caller's sum and inverse transform.
+ * fhe_bgv_decrypt: the EVALUATION branch of Decrypt (bgvrns-pke.cpp:52-60, 96).  c[nElem] (host array, nElem 2 or 3): element e of
+ * `batch` ciphertexts, each [batch][sizeQl][N]; s: the secret key, ONE tower [sizeQl][N]; all EVALUATION over limbIdx.  PKERNS::DecryptCore
+ * (rns-pke.cpp:199-216) with element-wise launches (2, or 4 with s^2 formed for nElem == 3), ONE inverse transform of all limbs of all
+ * towers, then the chain to t.  out [batch][N]; ws of fhe_bgv_decrypt_workspace_bytes.
+ * Errors, each before anything is enqueued: a null argument; levels outside [1, sizeQl); a limb index outside the context; t < 2 (to_t and
+ * decrypt: or t >= 2^63), t a multiple of a dropped limb, equal moduli in the tower; a short workspace; out aliasing x. */
+size_t fhe_mod_reduce_chain_workspace_bytes(const fhe_ctx* ctx, uint32_t sizeQl, uint32_t levels, uint32_t batch);
+fhe_status fhe_mod_reduce_chain(fhe_ctx* ctx, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint32_t levels, uint64_t t,
+                                uint32_t batch, uint64_t* out, void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_mod_reduce_to_t(fhe_ctx* ctx, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t, uint32_t batch,
+                               uint64_t* out, void* ws, size_t wsBytes, void* stream);
+size_t fhe_bgv_decrypt_workspace_bytes(const fhe_ctx* ctx, uint32_t nElem, uint32_t sizeQl, uint32_t batch);
+fhe_status fhe_bgv_decrypt(fhe_ctx* ctx, const uint64_t* const* c, uint32_t nElem, const uint64_t* s, const uint32_t* limbIdx,
+                           uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* out, void* ws, size_t wsBytes, void* stream);
 
 /* ---- a17: ScaleAndRound family (BFV HPS) ----------------------------------------------------------------
  * fhe_sr_plan_create keeps the caller's tables on the device. They are the reference's own

@@ -39,6 +39,8 @@ enum ElemOp : int {
     OP_ADD_CONST = 10,     // out = a + c[row]         (PolyImpl::Plus(Integer) in EVALUATION / Minus(Integer) with c = q - c)
     OP_ADD_CONST_AT0 = 11, // out = a + c[row] at coefficient 0 only (PolyImpl::Plus(Integer) in COEFFICIENT, poly-impl.h:213-214)
     OP_TIMES_QOVERT = 12,  // out = ((a * pre) mod preMod) * c[row]   (DCRTPolyImpl::TimesQovert, dcrtpoly-impl.h:868-885)
+    OP_MUL_ROW = 13,       // out = a * b, b ONE tower [nLimbs][N] that every tower of a meets (the secret key of PKERNS::DecryptCore, rns-pke.cpp:199)
+    OP_MULT_ACC_ROW = 14,  // out = out + a * b, b one tower as above
 };
 
 struct ElemArgs {
@@ -69,6 +71,7 @@ FHE_HD uint64_t elem_apply(uint64_t o, uint64_t a, uint64_t b, const LimbConst l
         case OP_SUB:
             return sub_mod(a, b, q);
         case OP_MUL:
+        case OP_MUL_ROW:
             return mul_mod_barrett(a, b, q, lc.mu, (int)lc.msb);
         case OP_NEG:
             return a == 0 ? 0 : q - a;
@@ -79,6 +82,7 @@ FHE_HD uint64_t elem_apply(uint64_t o, uint64_t a, uint64_t b, const LimbConst l
         case OP_MUL_CONST_ADD:
             return add_mod(mul_shoup(a, c.w, c.wp, q), b, q);
         case OP_MULT_ACC:
+        case OP_MULT_ACC_ROW:
             return add_mod(o, mul_mod_barrett(a, b, q, lc.mu, (int)lc.msb), q);
         case OP_SUB_MUL_CONST_ACC:
             return add_mod(o, mul_shoup(sub_mod(a, b, q), c.w, c.wp, q), q);
@@ -107,10 +111,12 @@ FHE_DEV void elemwise_body(const ElemArgs& g, ConstAt constAt, InWindow inWindow
     const uint64_t base       = (uint64_t)FHE_BID << kTileLog;
     const uint64_t totalWords = (uint64_t)g.rows << g.logN;
     constexpr bool needB = (OP == OP_ADD || OP == OP_SUB || OP == OP_MUL || OP == OP_SUB_MUL_CONST ||
-                            OP == OP_MUL_CONST_ADD || OP == OP_MULT_ACC || OP == OP_SUB_MUL_CONST_ACC);
+                            OP == OP_MUL_CONST_ADD || OP == OP_MULT_ACC || OP == OP_SUB_MUL_CONST_ACC || OP == OP_MUL_ROW ||
+                            OP == OP_MULT_ACC_ROW);
+    constexpr bool rowB  = (OP == OP_MUL_ROW || OP == OP_MULT_ACC_ROW);  // b is one tower, indexed by the place inside the tower alone
     constexpr bool needC = (OP == OP_MUL_CONST || OP == OP_SUB_MUL_CONST || OP == OP_MUL_CONST_ADD || OP == OP_SUB_MUL_CONST_ACC ||
                             OP == OP_ADD_CONST || OP == OP_ADD_CONST_AT0 || OP == OP_TIMES_QOVERT);
-    constexpr bool needO = (OP == OP_MULT_ACC || OP == OP_SUB_MUL_CONST_ACC);
+    constexpr bool needO = (OP == OP_MULT_ACC || OP == OP_SUB_MUL_CONST_ACC || OP == OP_MULT_ACC_ROW);
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const uint64_t off = base + (((uint64_t)m * kThreads + t) << 1);
@@ -136,7 +142,8 @@ FHE_DEV void elemwise_body(const ElemArgs& g, ConstAt constAt, InWindow inWindow
         }
         uint64_t b0 = 0, b1 = 0, o0 = 0, o1 = 0;
         if (needB) {
-            const uint64_t boff = g.bDelta ? (uint64_t)((int64_t)tb * g.bDelta) + inTower
+            const uint64_t boff = rowB ? inTower
+                                  : g.bDelta ? (uint64_t)((int64_t)tb * g.bDelta) + inTower
                                            : g.bStride ? ((((uint64_t)tb * g.bStride + g.bFirst + rit) << g.logN) + ri) : off;
             b0 = g.b[boff];
             b1 = g.b[boff + 1];
@@ -433,6 +440,78 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) rescale_chain_kernel(const RescaleCh
             if (k > 0 || g.hasScale)
                 *pk = v;
         }
+    }
+}
+
+// ---- d consecutive BGV ModReduce steps on a COEFFICIENT tower in one launch ---------------------------------
+// What PKEBGVRNS::Decrypt (bgvrns-pke.cpp:56-60) and MultipartyDecryptFusion (bgvrns-multiparty.cpp:79-83) run sizeQl - 1 times in a row,
+// DCRTPolyImpl::ModReduce (dcrtpoly-impl.h:736-755), without a tower between the steps.  Step k drops limb n-1-k; its delta_k is the value the
+// member would find in that limb after the steps before it, times negtInvModq.  Every row is a weighted sum over the deltas whose
+// weights the host has multiplied out (host::mod_reduce_chain_table, which also states the formula and the table's layout):
+//   v = x * X + sum_k (delta_k * W_k + (delta_k > floor(qd_k / 2) ? Cn_k : 0)) mod q.
+// One lane per coefficient.  The deltas of the (at most kMaxChainDrop) dropped limbs stay in registers, a statically unrolled triangle;
+// the kept limbs are streamed, one load and one store per row with the next row's load under way, so the register need does not depend
+// on the tower's width.  The table is wave-uniform and read through the constant address space.  Partial sums stay below 2q; every
+// stored word is the canonical residue, which is what each step of the member yields, so the words are the reference's.
+// MODT (one limb kept): the store is its centred residue modulo t in [0, t), NativeVector::Mod(t) of DecryptionCRTInterpolate
+// (mubintvecnat.cpp:145-161, 351-356).
+// A workgroup takes kThreads coefficients, not a 4096-word tile: 16 towers of N = 2^14 are 64 such tiles, a quarter of the device's
+// compute units, and each lane already walks the n rows of its coefficient.
+constexpr int kMaxChainDrop = 16;
+struct ModReduceChainArgs {
+    const uint64_t* x;    // [batch][n][N]
+    uint64_t* out;        // [batch][n-d][N]
+    const uint64_t* tab;  // host::mod_reduce_chain_table
+    uint32_t logN, n, d, batch;
+};
+// v (below 2q) plus step k's terms of the row at `w` (its words W_k, Shoup(W_k), Cn_k), again below 2q
+FHE_DEV uint64_t mod_reduce_chain_step(uint64_t v, uint64_t delta, bool upper, const uint64_t* w, uint64_t nq, uint64_t twoq) {
+    v = csub(v + mul_shoup_lazy_nq(delta, FHE_ULOAD64(w, 0), FHE_ULOAD64(w, 1), nq), twoq);
+    return csub(v + (upper ? FHE_ULOAD64(w, 2) : 0), twoq);
+}
+template <bool MODT>
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) mod_reduce_chain_kernel(const ModReduceChainArgs g) {
+    const uint64_t off = (uint64_t)FHE_BID * kThreads + FHE_TID;
+    if (off >= ((uint64_t)g.batch << g.logN))
+        return;
+    const uint64_t tower = off >> g.logN, r = off & (((uint64_t)1 << g.logN) - 1u);
+    const uint32_t nKeep = g.n - g.d, stride = 3u + 3u * g.d;
+    const uint64_t* xp   = g.x + ((tower * g.n) << g.logN) + r;
+    uint64_t* op         = g.out + ((tower * nKeep) << g.logN) + r;
+    uint64_t first       = xp[0];  // (under way while the triangle runs)
+    uint64_t delta[kMaxChainDrop];
+    uint32_t upper = 0;  // bit k: delta_k > floor(qd_k / 2), SwitchModulus takes the negative representative
+#pragma unroll
+    for (int j = 0; j < kMaxChainDrop; ++j) {
+        if ((uint32_t)j >= g.d)  // (a guard, not a break: the loop keeps its constant trip count and unrolls, so delta[] stays in registers)
+            continue;
+        const uint64_t* row = g.tab + (uint32_t)j * stride;
+        const uint64_t q = FHE_ULOAD64(row, 0), nq = 0 - q, twoq = q << 1;
+        uint64_t v = mul_shoup_lazy_nq(xp[(uint64_t)(g.n - 1u - (uint32_t)j) << g.logN], FHE_ULOAD64(row, 1), FHE_ULOAD64(row, 2), nq);
+#pragma unroll
+        for (int k = 0; k < j; ++k)
+            v = mod_reduce_chain_step(v, delta[k], (upper >> k) & 1u, row + 3 + 3 * k, nq, twoq);
+        delta[j] = csub(v, q);
+        upper |= (uint32_t)(delta[j] > (q >> 1)) << j;
+    }
+    for (uint32_t i = 0; i < nKeep; ++i) {
+        const uint64_t x = first;
+        if (i + 1u < nKeep)
+            first = xp[(uint64_t)(i + 1u) << g.logN];
+        const uint64_t* row = g.tab + (uint64_t)(g.d + i) * stride;
+        const uint64_t q = FHE_ULOAD64(row, 0), nq = 0 - q, twoq = q << 1;
+        uint64_t v = mul_shoup_lazy_nq(x, FHE_ULOAD64(row, 1), FHE_ULOAD64(row, 2), nq);
+#pragma unroll
+        for (int k = 0; k < kMaxChainDrop; ++k)
+            if ((uint32_t)k < g.d)
+                v = mod_reduce_chain_step(v, delta[k], (upper >> k) & 1u, row + 3 + 3 * k, nq, twoq);
+        v = csub(v, q);
+        if (MODT) {  // (v > floor(q/2) ? v - q : v) mod t
+            const uint64_t* tail = g.tab + (uint64_t)g.n * stride;
+            const uint64_t t = FHE_ULOAD64(tail, 0), vt = mul_shoup(v, 1, FHE_ULOAD64(tail, 1), t);
+            v = v > (q >> 1) ? sub_mod(vt, FHE_ULOAD64(tail, 2), t) : vt;
+        }
+        op[(uint64_t)i << g.logN] = v;
     }
 }
 

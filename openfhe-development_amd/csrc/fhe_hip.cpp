@@ -288,6 +288,8 @@ struct fhe_ctx {
     std::shared_mutex constTabsGate;  // shared: an entry point between asking for its tables and enqueuing the launches that read them
     // cached ModReduce tables per (sizeQl, t): [0..l) = A_i, [l..2l) = B_i, [2l] = negtInvModq, [2l+1] = t^-1 mod q_l, [2l+2..3l+2) = t mod q_i   (fhe_mod_reduce)
     std::map<std::pair<uint32_t, uint64_t>, TwPair*> modReduceTabs;
+    // cached tables of mod_reduce_chain_kernel by {t, limbs dropped, with the residue modulo t, the tower's context limbs...}
+    std::map<std::vector<uint64_t>, const uint64_t*> chainTabs;
     std::mutex cacheMutex;        // guards the lazily filled caches above (callers may be OpenMP threads)
 };
 
@@ -3538,6 +3540,141 @@ extern "C" fhe_status fhe_mod_reduce_limbs_pair(fhe_ctx* c, const uint64_t* x0, 
     ARG_CHECK(x1 && out1 && x1 != x0 && out1 != out0, "fhe_mod_reduce_limbs_pair: needs two distinct towers");
     return mod_reduce_limbs_run(c, x0, x1, limbIdx, sizeQl, t, negtInvModq, qlInvModq, evalFormat, 2, out0, out1, wsv, wsBytes, st,
                                 "fhe_mod_reduce_limbs_pair");
+}
+
+// ---- BGV ModReduce over several limbs of a COEFFICIENT tower, and decryption ----
+// PKEBGVRNS::Decrypt (bgvrns-pke.cpp:44-99) and MultipartyBGVRNS::MultipartyDecryptFusion (bgvrns-multiparty.cpp:62-97) switch b to
+// COEFFICIENT and call DCRTPolyImpl::ModReduce sizeQl - 1 times, then take the last limb's centred residues modulo t.  One launch of
+// mod_reduce_chain_kernel per kMaxChainDrop dropped limbs does that; the tables are the library's own, derived from the
+// tower's moduli and t (host::mod_reduce_chain_table) and kept per (limb list, t, limbs dropped, with or without the residue modulo t).
+// ws: the towers between chunks, two regions that alternate; none when levels <= kMaxChainDrop.
+extern "C" size_t fhe_mod_reduce_chain_workspace_bytes(const fhe_ctx* c, uint32_t sizeQl, uint32_t levels, uint32_t batch) {
+    if (!c || levels >= sizeQl || levels <= (uint32_t)kMaxChainDrop)
+        return 0;
+    return (((size_t)2 * batch * (sizeQl - kMaxChainDrop)) << c->logN) * 8;
+}
+static fhe_status mod_reduce_chain_table(fhe_ctx* c, const uint32_t* limbIdx, const uint64_t* qs, uint32_t n, uint32_t d, uint64_t t, bool modT,
+                                         const uint64_t** out) {
+    std::vector<uint64_t> key{t, d, modT ? 1u : 0u};
+    for (uint32_t i = 0; i < n; ++i)
+        key.push_back(limbIdx ? limbIdx[i] : i);
+    std::lock_guard<std::mutex> lock(c->cacheMutex);
+    auto it = c->chainTabs.find(key);
+    if (it == c->chainTabs.end()) {
+        const std::vector<uint64_t> h = host::mod_reduce_chain_table(qs, n, d, t, modT);
+        uint64_t* dev = nullptr;
+        if (fhe_status s = dev_copy(&c->owned, h.data(), h.size(), &dev))
+            return s;
+        it = c->chainTabs.emplace(std::move(key), dev).first;
+    }
+    *out = it->second;
+    return FHE_OK;
+}
+// x[batch][sizeQl][N] COEFFICIENT over limbIdx (null: the leading limbs), the last `levels` limbs dropped one by one; toT: levels is
+// sizeQl - 1 (zero included) and out[batch][N] holds the residues modulo t of the limb that is left.  Checks first, then launches.
+static fhe_status mod_reduce_chain_run(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint32_t levels, uint64_t t,
+                                       bool toT, uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes, void* st, const char* who) {
+    const std::string w(who);
+    const size_t need = fhe_mod_reduce_chain_workspace_bytes(c, sizeQl, levels, batch);
+    if (levels == 0) {  // (fhe_mod_reduce_to_t on one limb: no step, no limb to remove)
+        ARG_CHECK(c && x && out, w + ": null argument");
+        ARG_CHECK(batch >= 1, w + ": workspace too small");
+        ARG_CHECK((limbIdx ? limbIdx[0] : 0u) < c->L, w + ": limb index exceeds context size");
+        RT_CHECK(rt::set_device(c->device));
+    }
+    else if (fhe_status s = drop_check(who, c, x && out && (wsv || !need), limbIdx, !limbIdx, sizeQl, levels, sizeQl - levels, batch, wsBytes,
+                                       need, true))
+        return s;
+    const std::vector<uint64_t> qs = tower_moduli(c, limbIdx, sizeQl);
+    ARG_CHECK(t >= 2 && (!toT || t < ((uint64_t)1 << 63)), w + ": t must be in [2, 2^63)");
+    for (uint32_t k = 0; k < levels; ++k) {
+        ARG_CHECK(t % qs[sizeQl - 1 - k] != 0, w + ": t must be invertible modulo every dropped limb");
+        for (uint32_t i = 0; i < sizeQl - 1 - k; ++i)
+            ARG_CHECK(qs[i] != qs[sizeQl - 1 - k], w + ": the moduli of a tower must be distinct");
+    }
+    ARG_CHECK(out != x, w + ": out must not alias x");
+    uint64_t* R[2] = {(uint64_t*)wsv, need ? (uint64_t*)wsv + need / 16 : nullptr};  // (two regions of need / 2 bytes)
+    const uint64_t* cur = x;
+    uint32_t n = sizeQl, left = levels, j = 0;
+    do {
+        const uint32_t d   = std::min<uint32_t>(left, (uint32_t)kMaxChainDrop);
+        const bool lastOne = left == d;
+        ModReduceChainArgs g;
+        g.x = cur, g.out = lastOne ? out : R[j & 1], g.logN = c->logN, g.n = n, g.d = d, g.batch = batch;
+        if (fhe_status s = mod_reduce_chain_table(c, limbIdx, qs.data(), n, d, t, lastOne && toT, &g.tab))
+            return s;
+        const uint32_t grid = (uint32_t)((((uint64_t)batch << c->logN) + kThreads - 1) / kThreads);
+        if (lastOne && toT)
+            FHE_LAUNCH((mod_reduce_chain_kernel<true>), grid, st, g);
+        else
+            FHE_LAUNCH((mod_reduce_chain_kernel<false>), grid, st, g);
+        LAUNCH_CHECK();
+        cur = g.out, n -= d, left -= d, ++j;
+    } while (left);
+    return FHE_OK;
+}
+// replaces `levels` consecutive DCRTPolyImpl::ModReduce calls (dcrtpoly-impl.h:736-755) on a COEFFICIENT tower: the second branch of
+// PKEBGVRNS::Decrypt (bgvrns-pke.cpp:73-81) element by element
+extern "C" fhe_status fhe_mod_reduce_chain(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint32_t levels, uint64_t t,
+                                           uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes, void* st) {
+    ARG_CHECK(levels >= 1, "fhe_mod_reduce_chain: levels must be in [1, sizeQl)");
+    return mod_reduce_chain_run(c, x, limbIdx, sizeQl, levels, t, false, batch, out, wsv, wsBytes, st, "fhe_mod_reduce_chain");
+}
+// replaces the ModReduce loop and DecryptionCRTInterpolate of PKEBGVRNS::Decrypt (bgvrns-pke.cpp:56-60, 96) and of
+// MultipartyBGVRNS::MultipartyDecryptFusion (bgvrns-multiparty.cpp:79-83, 94) on b in COEFFICIENT format
+extern "C" fhe_status fhe_mod_reduce_to_t(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t, uint32_t batch,
+                                          uint64_t* out, void* wsv, size_t wsBytes, void* st) {
+    ARG_CHECK(sizeQl >= 1, "fhe_mod_reduce_to_t: sizeQl must be at least 1");
+    return mod_reduce_chain_run(c, x, limbIdx, sizeQl, sizeQl - 1, t, true, batch, out, wsv, wsBytes, st, "fhe_mod_reduce_to_t");
+}
+// replaces the first branch of PKEBGVRNS::Decrypt (bgvrns-pke.cpp:52-60, 96): PKERNS::DecryptCore (rns-pke.cpp:199-216), b = c0 + c1 * s
+// (+ c2 * s^2), with the element-wise kernels, one inverse transform of all limbs of all towers, the chain down to one limb and its
+// residues modulo t.  c[e]: element e of `batch` ciphertexts, [batch][sizeQl][N]; s: the secret key, ONE tower [sizeQl][N]; all in
+// EVALUATION over limbIdx.  ws: b[batch][sizeQl][N], s^2 (nElem == 3), then the chain's workspace.
+static size_t bgv_decrypt_b_words(const fhe_ctx* c, uint32_t nElem, uint32_t sizeQl, uint32_t batch) {
+    return ((size_t)batch * sizeQl + (nElem == 3 ? sizeQl : 0)) << c->logN;
+}
+extern "C" size_t fhe_bgv_decrypt_workspace_bytes(const fhe_ctx* c, uint32_t nElem, uint32_t sizeQl, uint32_t batch) {
+    if (!c || sizeQl < 1 || nElem < 2 || nElem > 3)
+        return 0;
+    return bgv_decrypt_b_words(c, nElem, sizeQl, batch) * 8 + fhe_mod_reduce_chain_workspace_bytes(c, sizeQl, sizeQl - 1, batch);
+}
+extern "C" fhe_status fhe_bgv_decrypt(fhe_ctx* c, const uint64_t* const* ct, uint32_t nElem, const uint64_t* s, const uint32_t* limbIdx,
+                                      uint32_t sizeQl, uint64_t t, uint32_t batch, uint64_t* out, void* wsv, size_t wsBytes, void* st) {
+    const char* who = "fhe_bgv_decrypt";
+    ARG_CHECK(c && ct && s && out && wsv, "fhe_bgv_decrypt: null argument");
+    ARG_CHECK(nElem == 2 || nElem == 3, "fhe_bgv_decrypt: a ciphertext of 2 or 3 elements expected");
+    for (uint32_t e = 0; e < nElem; ++e)
+        ARG_CHECK(ct[e] && ct[e] != out, "fhe_bgv_decrypt: null argument");
+    ARG_CHECK(sizeQl >= 1 && sizeQl <= (limbIdx ? (uint32_t)kMaxLimbs : c->L), "fhe_bgv_decrypt: sizeQl exceeds context size");
+    for (uint32_t i = 0; i < sizeQl; ++i)
+        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, "fhe_bgv_decrypt: limb index exceeds context size");
+    ARG_CHECK(batch >= 1 && wsBytes >= fhe_bgv_decrypt_workspace_bytes(c, nElem, sizeQl, batch), "fhe_bgv_decrypt: workspace too small");
+    // (the chain's own checks, before anything is enqueued: the same texts under this entry's name)
+    const std::vector<uint64_t> qs = tower_moduli(c, limbIdx, sizeQl);
+    ARG_CHECK(t >= 2 && t < ((uint64_t)1 << 63), "fhe_bgv_decrypt: t must be in [2, 2^63)");
+    for (uint32_t k = 1; k < sizeQl; ++k) {
+        ARG_CHECK(t % qs[k] != 0, "fhe_bgv_decrypt: t must be invertible modulo every dropped limb");
+        for (uint32_t i = 0; i < k; ++i)
+            ARG_CHECK(qs[i] != qs[k], "fhe_bgv_decrypt: the moduli of a tower must be distinct");
+    }
+    uint64_t* b        = (uint64_t*)wsv;
+    uint64_t* s2       = b + (((size_t)batch * sizeQl) << c->logN);
+    uint64_t* chainWs  = b + bgv_decrypt_b_words(c, nElem, sizeQl, batch);
+    const size_t chainBytes = wsBytes - bgv_decrypt_b_words(c, nElem, sizeQl, batch) * 8;
+    if (fhe_status r = elem_run<OP_MUL_ROW>(c, b, ct[1], s, nullptr, limbIdx, sizeQl, batch, st, who))  // c1 * s
+        return r;
+    if (fhe_status r = elem_run<OP_ADD>(c, b, b, ct[0], nullptr, limbIdx, sizeQl, batch, st, who))  // c0 + c1 * s
+        return r;
+    if (nElem == 3) {  // sPower *= s; b += sPower * c2  (rns-pke.cpp:208-213)
+        if (fhe_status r = elem_run<OP_MUL>(c, s2, s, s, nullptr, limbIdx, sizeQl, 1, st, who))
+            return r;
+        if (fhe_status r = elem_run<OP_MULT_ACC_ROW>(c, b, ct[2], s2, nullptr, limbIdx, sizeQl, batch, st, who))
+            return r;
+    }
+    if (fhe_status r = fhe_ntt_inv(c, b, limbIdx, sizeQl, batch, st))  // b.SetFormat(COEFFICIENT), every limb of every tower at once
+        return r;
+    return mod_reduce_chain_run(c, b, limbIdx, sizeQl, sizeQl - 1, t, true, batch, out, chainWs, chainBytes, st, who);
 }
 
 // ------------------------------------------------------------------------------------------------

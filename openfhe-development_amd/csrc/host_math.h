@@ -96,6 +96,43 @@ inline ModReduceTables mod_reduce_tables(const uint64_t* q, uint32_t n, uint64_t
     }
     return r;
 }
+// `d` consecutive ModReduce steps on a COEFFICIENT tower over moduli q[0..n) as ONE pass (mod_reduce_chain_kernel): step k
+// drops limb n-1-k, modulus qd_k.  Unrolling v <- (v + T * SM(delta_k)) * B_k, with SM(delta_k) = delta_k - c_k * qd_k as a residue
+// (c_k = 1 when delta_k > floor(qd_k / 2)), gives for a row modulo q that sees the first s steps
+//   v_s = x * X + sum_{k<s} (delta_k * W_k + c_k * Cn_k)   mod q,
+//   X = M * prod_{j<s} B_j,   W_k = M * (t mod q) * prod_{k<=j<s} B_j,   Cn_k = -(qd_k * W_k),   B_j = qd_j^-1 mod q,
+// M = 1 for a kept limb (s = d) and M = negtInvModq = -t^-1 mod q for the limb dropped at step s, whose v_s is delta_s.
+// Layout, in words: row r at r * (3 + 3d), rows 0..d-1 the dropped limbs in the order of the steps, rows d..n-1 the kept limbs 0..n-d-1;
+// a row holds q, X, Shoup(X), then for k < d: W_k, Shoup(W_k), Cn_k (zero beyond the row's own s).  modT: three more words at the end,
+// t, floor(2^64 / t) and q[0] mod t, for the centred residue modulo t of the one limb that is left (NativeVector::Mod).
+inline std::vector<uint64_t> mod_reduce_chain_table(const uint64_t* q, uint32_t n, uint32_t d, uint64_t t, bool modT) {
+    const size_t stride = 3 + 3 * (size_t)d;
+    std::vector<uint64_t> tab(n * stride + (modT ? 3 : 0), 0);
+    std::vector<uint64_t> suffix(d + 1);
+    for (uint32_t r = 0; r < n; ++r) {
+        const bool dropped = r < d;
+        const uint32_t s   = dropped ? r : d;
+        const uint64_t qr  = q[dropped ? n - 1 - r : r - d];
+        const uint64_t M   = dropped ? (qr - invmod(t % qr, qr)) % qr : 1;
+        const uint64_t MT  = mulmod(M, t % qr, qr);
+        suffix[s]          = 1;  // prod_{k<=j<s} B_j
+        for (uint32_t k = s; k-- > 0;)
+            suffix[k] = mulmod(suffix[k + 1], dropped_inv(q[n - 1 - k], qr), qr);
+        uint64_t* row = &tab[r * stride];
+        const uint64_t X = mulmod(M, suffix[0], qr);
+        row[0] = qr, row[1] = X, row[2] = shoup(X, qr);
+        for (uint32_t k = 0; k < s; ++k) {
+            const uint64_t W = mulmod(MT, suffix[k], qr);
+            row[3 + 3 * k] = W, row[4 + 3 * k] = shoup(W, qr);
+            row[5 + 3 * k] = (qr - mulmod(q[n - 1 - k] % qr, W, qr)) % qr;
+        }
+    }
+    if (modT) {
+        uint64_t* tail = &tab[n * stride];
+        tail[0] = t, tail[1] = shoup(1, t), tail[2] = q[0] % t;
+    }
+    return tab;
+}
 // A[i] == -B[i] mod q[i], B reduced: the pair for which x*B + r*A == (x - r)*B
 inline bool negated_pair(const uint64_t* q, const uint64_t* A, const uint64_t* B, uint32_t n) {
     bool ok = true;

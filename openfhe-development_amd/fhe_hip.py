@@ -166,6 +166,11 @@ class Lib:
         S("fhe_mod_reduce", C.c_int, [vp, vp, u32, u64, C.c_int, u32, vp, vp, C.c_size_t, vp])
         S("fhe_mod_reduce_limbs", C.c_int, [vp, vp, u32p, u32, u64, u64, u64p, C.c_int, u32, vp, vp, C.c_size_t, vp])
         S("fhe_mod_reduce_limbs_pair", C.c_int, [vp, vp, vp, u32p, u32, u64, u64, u64p, C.c_int, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_mod_reduce_chain_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_mod_reduce_chain", C.c_int, [vp, vp, u32p, u32, u32, u64, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_mod_reduce_to_t", C.c_int, [vp, vp, u32p, u32, u64, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_bgv_decrypt_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_bgv_decrypt", C.c_int, [vp, C.POINTER(vp), u32, vp, u32p, u32, u64, u32, vp, vp, C.c_size_t, vp])
         S("fhe_bgv_keyswitch_hybrid", C.c_int, [vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_bgv_keyswitch_hybrid_acc", C.c_int, [vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_bgv_eval_mult", C.c_int, [vp, vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
@@ -1094,6 +1099,55 @@ def mod_reduce_pair(ctx, x0, x1, t, negt_inv_modq, ql_inv_modq, stream=None):
     finally:
         ctx.free(ws)
     return o0, o1
+
+
+def mod_reduce_chain(ctx, x, levels, t, stream=None):
+    """`levels` consecutive DCRTPoly::ModReduce calls (dcrtpoly-impl.h:736-755) on a COEFFICIENT Tower, its last limb first, in one
+    launch per 16 levels (fhe_mod_reduce_chain): what the COEFFICIENT branch of PKEBGVRNS::Decrypt runs on every element."""
+    sizeQl = x.n_limbs
+    need = ctx.lib.L.fhe_mod_reduce_chain_workspace_bytes(ctx.h, sizeQl, levels, x.batch)
+    ws = ctx.malloc(need) if need else None
+    kept = None if x.limb_idx is None else x.limb_idx[:max(sizeQl - levels, 1)]
+    out = ctx.empty(x.batch, max(sizeQl - levels, 1), kept, COEFFICIENT)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_mod_reduce_chain(ctx.h, x.ptr, x._li(), sizeQl, levels, t, x.batch, out.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        if ws:
+            ctx.free(ws)
+    return out
+
+
+def mod_reduce_to_t(ctx, x, t, stream=None):
+    """the ModReduce chain of a COEFFICIENT Tower down to one limb and DecryptionCRTInterpolate(t) of it (fhe_mod_reduce_to_t): the tail of
+    PKEBGVRNS::Decrypt and MultipartyDecryptFusion; returns uint64 [batch][N] in [0, t)"""
+    sizeQl = x.n_limbs
+    need = ctx.lib.L.fhe_mod_reduce_chain_workspace_bytes(ctx.h, sizeQl, sizeQl - 1, x.batch)
+    ws = ctx.malloc(need) if need else None
+    d = ctx.malloc(x.batch * ctx.N * 8)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_mod_reduce_to_t(ctx.h, x.ptr, x._li(), sizeQl, t, x.batch, d, ws, need, stream))
+        return ctx.download(d, (x.batch, ctx.N), stream)
+    finally:
+        ctx.free(d)
+        if ws:
+            ctx.free(ws)
+
+
+def bgv_decrypt(ctx, elements, s, t, stream=None):
+    """PKEBGVRNS::Decrypt on EVALUATION ciphertexts (bgvrns-pke.cpp:52-60, 96) through fhe_bgv_decrypt: elements = 2 or 3 Towers
+    [batch][sizeQl][N], s = the secret key, one Tower [1][sizeQl][N] over the same limbs; returns the NativePoly words, uint64 [batch][N]"""
+    c0 = elements[0]
+    need = ctx.lib.L.fhe_bgv_decrypt_workspace_bytes(ctx.h, len(elements), c0.n_limbs, c0.batch)
+    ws = ctx.malloc(max(need, 8))
+    d = ctx.malloc(c0.batch * ctx.N * 8)
+    ptrs = (vp * len(elements))(*[e.ptr.value if hasattr(e.ptr, "value") else e.ptr for e in elements])
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_bgv_decrypt(ctx.h, ptrs, len(elements), s.ptr, c0._li(), c0.n_limbs, t, c0.batch, d, ws, need, stream))
+        return ctx.download(d, (c0.batch, ctx.N), stream)
+    finally:
+        ctx.free(d)
+        ctx.free(ws)
 
 
 def scale_and_round_native(ctx, x, t, tab_modt, frac, tab_bmodt=None, bfrac=None, stream=None):

@@ -258,6 +258,54 @@ public:
         x0 = std::move(o0);
         x1 = std::move(o1);
     }
+    // ModReduce `levels` times on a COEFFICIENT tower, its last limb first, in one launch per 16 limbs: what the COEFFICIENT branch of
+    // PKEBGVRNS::Decrypt (bgvrns-pke.cpp:73-81) does to every element (fhe_mod_reduce_chain; the tables are derived from the moduli and t)
+    void ModReduceChain(uint32_t levels, uint64_t t) {
+        if (m_format != COEFFICIENT)
+            throw Error("ModReduceChain: COEFFICIENT format expected");
+        if (levels < 1 || levels >= m_limbs)
+            throw Error("ModReduceChain: levels must be in [1, limbs)");
+        std::vector<uint32_t> kept(m_idx.begin(), m_idx.empty() ? m_idx.end() : m_idx.end() - levels);
+        DCRTPolyHip out(m_params, m_limbs - levels, m_format, m_batch, kept);
+        size_t wsb = fhe_mod_reduce_chain_workspace_bytes(m_params->ctx(), m_limbs, levels, m_batch);
+        void* ws   = nullptr;
+        if (wsb)
+            check(fhe_malloc(m_params->ctx(), wsb, &ws));
+        fhe_status s = fhe_mod_reduce_chain(m_params->ctx(), m_data, idx(), m_limbs, levels, t, m_batch, out.m_data, ws, wsb, nullptr);
+        fhe_stream_sync(m_params->ctx(), nullptr);
+        if (ws)
+            fhe_free(m_params->ctx(), ws);
+        check(s);
+        *this = std::move(out);
+    }
+    // the whole chain down to one limb and DecryptionCRTInterpolate(t) of it: the NativePoly words, [batch][N] in [0, t), of PKEBGVRNS::Decrypt
+    // (bgvrns-pke.cpp:56-60, 96) and MultipartyDecryptFusion (bgvrns-multiparty.cpp:79-83, 94) for b in COEFFICIENT format (fhe_mod_reduce_to_t)
+    std::vector<uint64_t> ModReduceToT(uint64_t t) const {
+        if (m_format != COEFFICIENT)
+            throw Error("ModReduceToT: COEFFICIENT format expected");
+        return toT([&](uint64_t* out, void* ws, size_t wsb) {
+            return fhe_mod_reduce_to_t(m_params->ctx(), m_data, idx(), m_limbs, t, m_batch, out, ws, wsb, nullptr);
+        }, fhe_mod_reduce_chain_workspace_bytes(m_params->ctx(), m_limbs, m_limbs - 1, m_batch));
+    }
+    // PKEBGVRNS::Decrypt of `batch` EVALUATION ciphertexts of 2 or 3 elements under the secret key s (one tower over the same limbs): the
+    // NativePoly words before decoding, [batch][N] (fhe_bgv_decrypt)
+    static std::vector<uint64_t> BgvDecrypt(const std::vector<const DCRTPolyHip*>& elements, const DCRTPolyHip& s, uint64_t t) {
+        if (elements.size() < 2 || elements.size() > 3)
+            throw Error("BgvDecrypt: a ciphertext of 2 or 3 elements expected");
+        const DCRTPolyHip& c0 = *elements[0];
+        std::vector<const uint64_t*> ptrs;
+        for (const DCRTPolyHip* e : elements) {
+            if (e->m_limbs != c0.m_limbs || e->m_batch != c0.m_batch || e->m_idx != c0.m_idx || e->m_format != EVALUATION)
+                throw Error("BgvDecrypt: EVALUATION elements over the same limbs expected");
+            ptrs.push_back(e->m_data);
+        }
+        if (s.m_limbs != c0.m_limbs || s.m_batch != 1 || s.m_idx != c0.m_idx || s.m_format != EVALUATION)
+            throw Error("BgvDecrypt: the secret key must be one EVALUATION tower over the elements' limbs");
+        const uint32_t nElem = (uint32_t)elements.size();
+        return c0.toT([&](uint64_t* out, void* ws, size_t wsb) {
+            return fhe_bgv_decrypt(c0.m_params->ctx(), ptrs.data(), nElem, s.m_data, c0.idx(), c0.m_limbs, t, c0.m_batch, out, ws, wsb, nullptr);
+        }, fhe_bgv_decrypt_workspace_bytes(c0.m_params->ctx(), nElem, c0.m_limbs, c0.m_batch));
+    }
     // ExpandCRTBasis / ExpandCRTBasisReverseOrder to this basis + the context limbs `extra` (dcrtpoly-impl.h:1088-1148)
     DCRTPolyHip ExpandCRTBasis(const std::vector<uint32_t>& extra, Format resultFormat, bool reverseOrder = false) const {
         std::vector<uint32_t> src = m_idx;
@@ -317,6 +365,28 @@ private:
         compatible(r);
         check(f(m_params->ctx(), m_data, m_data, r.m_data, idx(), m_limbs, m_batch, nullptr));
         return *this;
+    }
+    // one [batch][N] result of `run(out, ws, wsBytes)` brought to the host (ModReduceToT, BgvDecrypt)
+    template <typename Run>
+    std::vector<uint64_t> toT(Run run, size_t wsb) const {
+        fhe_ctx* c       = m_params->ctx();
+        const size_t outb = (size_t)m_batch * GetRingDimension() * sizeof(uint64_t);
+        void *ws = nullptr, *out = nullptr;
+        check(fhe_malloc(c, outb, &out));
+        if (wsb && fhe_malloc(c, wsb, &ws) != FHE_OK) {
+            fhe_free(c, out);
+            throw Error(fhe_last_error());
+        }
+        std::vector<uint64_t> h(outb / sizeof(uint64_t));
+        fhe_status s = run(static_cast<uint64_t*>(out), ws, wsb);
+        if (s == FHE_OK)
+            s = fhe_memcpy_d2h(c, h.data(), out, outb, nullptr);
+        fhe_stream_sync(c, nullptr);
+        if (ws)
+            fhe_free(c, ws);
+        fhe_free(c, out);
+        check(s);
+        return h;
     }
     const uint32_t* idx() const { return m_idx.empty() ? nullptr : m_idx.data(); }
     size_t words() const { return (size_t)m_batch * m_limbs * m_params->GetRingDimension(); }
