@@ -487,6 +487,50 @@ fhe_status fhe_mod_reduce_limbs(fhe_ctx* ctx, const uint64_t* x, const uint32_t*
 fhe_status fhe_mod_reduce_limbs_pair(fhe_ctx* ctx, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
                                      uint64_t t, uint64_t negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint64_t* out0,
                                      uint64_t* out1, void* ws, size_t wsBytes, void* stream);
+/* ---- BGV level alignment of the automatic scaling modes in one pass ---------------------------------------------------
+ * Under FLEXIBLEAUTO / FLEXIBLEAUTOEXT every EvalMult, EvalAdd and EvalSub first calls LeveledSHEBGVRNS::AdjustLevelsAndDepth[ToOne]InPlace
+ * (bgvrns-leveledshe.cpp:83-233), which on one operand is some of: cv[i] *= scalar, ModReduceInternalInPlace (:44-75, DCRTPolyImpl::ModReduce
+ * on every element, dcrtpoly-impl.h:736-755), a LevelReduce, ModReduceInternalInPlace again.  One call here.  The result is the words of
+ *   multiply every row by scalar mod q_i; then, for k = 0 .. levels-1, discard the rows above dropRows[k] and call ModReduce on row
+ *   dropRows[k]; keep rows 0 .. nOut-1:
+ *   x[batch][sizeQl][N] in `evalFormat` -> out[batch][nOut][N] in the same format.
+ *   dropRows: NULL = the last `levels` rows, the last one first.  Otherwise strictly decreasing, each < sizeQl, the lowest >= 1, and
+ *             levels <= 4.  1 <= nOut <= dropRows[levels-1].  More than 4 levels (trailing rows only) run in chunks of 4, the scalar in
+ *             the first chunk.
+ *   scalar:   the integer of the scalar product (1: none); its residues are taken inside.  t may exceed a limb (its residue is used).
+ * An EVALUATION tower on a ring of two static passes (N >= 8192) takes the fused form: the dropped rows to COEFFICIENT, a
+ * chain kernel that leaves rho_k, the canonical residue of -delta_k of every step, the forward column pass whose load sums the switched
+ * rho_k times (t mod q_i) * scalar^-1 * prod_{j<k} q_{r_j}, the row pass whose store is (x_i - r_i) * scalar * prod_k q_{r_k}^-1.
+ * Launches: 5 when the dropped rows are adjacent, 5 + 2 * (runs - 1) when they form `runs` groups of adjacent rows (each group is an inverse
+ * transform of two passes): 7 for ModReduce, LevelReduce, ModReduce, which is all the reference's case table asks for.
+ * Everything else runs the member's formula step by step with the launches of fhe_mul_const and fhe_mod_reduce: rings below 8192,
+ * COEFFICIENT towers, a scalar whose residue is zero modulo some row, tables that are not the derived ones, FHE_MOD_REDUCE_UNFUSED=1, and
+ * the plain case levels == 1, scalar == 1, nOut == dropRows[0], which is fhe_mod_reduce itself on rows 0 .. dropRows[0].
+ * fhe_mod_reduce_multi_limbs: any limbs of the context (limbIdx[sizeQl], NULL = the leading ones) with the CALLER's tables as the steps
+ * receive them: negtInvModq[k] = -t^-1 mod q_{dropRows[k]} and, for step k, the dropRows[k] residues of qlInvModq at offset
+ * sum_{j<k} dropRows[j].  Fused only when they equal what the library derives (the rule of fhe_mod_reduce_limbs).
+ * Errors, each before anything is enqueued: a null argument; levels outside [1, sizeQl); a malformed dropRows; nOut out of range; a limb
+ * index outside the context; t < 2 or a multiple of a dropped modulus; equal moduli in the tower; a table entry that is not reduced; a
+ * workspace below fhe_mod_reduce_multi_workspace_bytes; out aliasing x. */
+size_t     fhe_mod_reduce_multi_workspace_bytes(const fhe_ctx* ctx, uint32_t sizeQl, uint32_t levels, uint32_t batch);
+fhe_status fhe_mod_reduce_multi(fhe_ctx* ctx, const uint64_t* x, uint32_t sizeQl, uint64_t t, uint64_t scalar, const uint32_t* dropRows,
+                                uint32_t levels, uint32_t nOut, int evalFormat, uint32_t batch, uint64_t* out, void* ws, size_t wsBytes,
+                                void* stream);
+fhe_status fhe_mod_reduce_multi_limbs(fhe_ctx* ctx, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t,
+                                      uint64_t scalar, const uint32_t* dropRows, uint32_t levels, uint32_t nOut,
+                                      const uint64_t* negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint32_t batch, uint64_t* out,
+                                      void* ws, size_t wsBytes, void* stream);
+/* both elements of a ciphertext (towers x0, x1 -> out0, out1, each allocated on its own) in the same launches;
+ * ws of fhe_mod_reduce_multi_workspace_bytes(ctx, sizeQl, levels, 2) */
+fhe_status fhe_mod_reduce_multi_limbs_pair(fhe_ctx* ctx, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
+                                           uint64_t t, uint64_t scalar, const uint32_t* dropRows, uint32_t levels, uint32_t nOut,
+                                           const uint64_t* negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint64_t* out0,
+                                           uint64_t* out1, void* ws, size_t wsBytes, void* stream);
+/* The host-side constants of one fused pass of d <= 4 steps (host_math.h mod_reduce_multi_tables; nothing touches a device): the layout of
+ * fhe_rescale_multi_host_tables, with S[k] = sDrop[k] * t^-1 mod qDrop[k] and W[k][i] times t mod qKeep[i]. */
+fhe_status fhe_mod_reduce_multi_host_tables(const uint64_t* qDrop, uint32_t d, const uint64_t* qKeep, uint32_t nKeep, uint64_t t,
+                                            const uint64_t* sDrop, const uint64_t* sKeep, uint64_t* B, uint64_t* W, uint64_t* C,
+                                            uint64_t* S);
 /* BGV decryption: the ModReduce chain down to one limb, and its residues modulo t, without a tower between the steps.
  * PKEBGVRNS::Decrypt (bgvrns-pke.cpp:44-99) and MultipartyBGVRNS::MultipartyDecryptFusion (bgvrns-multiparty.cpp:62-97) switch
  * b = c0 + c1*s (+ c2*s^2) to COEFFICIENT, call DCRTPolyImpl::ModReduce sizeQl - 1 times and take DecryptionCRTInterpolate(t) of the

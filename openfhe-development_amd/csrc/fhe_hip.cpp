@@ -3161,10 +3161,12 @@ struct DropTabs {
 //   row per tower, against 16 more multiplications per lane and limb inside the prologue).
 //   Neither the switched tower nor its transform goes to HBM outside `out` (drop_fused_store).
 // x1 / out1 != null: the two elements of one ciphertext, allocated on their own (batch must be 2): the same launches over both towers, or,
-// unfused, element by element.
+// unfused, element by element.  xRows != 0: the towers of x are xRows >= sizeQl rows apart and the rows beyond sizeQl are not read (the
+// LevelReduce in front of a step of fhe_mod_reduce_multi).
 static fhe_status drop_last_run(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, const DropTabs& tb, int evalFormat,
                                 uint32_t batch, uint64_t* out, uint64_t* ws, void* st, const uint64_t* x1 = nullptr,
-                                uint64_t* out1 = nullptr) {
+                                uint64_t* out1 = nullptr, uint32_t xRows = 0) {
+    const uint32_t xs      = xRows ? xRows : sizeQl;  // rows between the towers of x
     const uint32_t l       = sizeQl - 1;
     const uint32_t lastIdx = limbIdx ? limbIdx[l] : l;
     uint64_t* last         = ws;                                 // [batch][N]
@@ -3178,18 +3180,18 @@ static fhe_status drop_last_run(fhe_ctx* c, const uint64_t* x, const uint32_t* l
     const int64_t xDelta = x1 ? x1 - x : 0;
     if (evalFormat) {  // lastPoly.SetFormat(COEFFICIENT)  (:696-697, :741): INTT of the last limb of every tower, written densely
         NttOpts lastRow;
-        lastRow.src.stride = sizeQl, lastRow.src.first = l, lastRow.srcDelta = xDelta;
+        lastRow.src.stride = xs, lastRow.src.first = l, lastRow.srcDelta = xDelta;
         if (fhe_status s = ntt_run(c, true, x, last, &lastIdx, 1, batch, st, lastRow))
             return s;
     }
     else
-        RT_CHECK(rt::d2d_2d(last, (size_t)8 << c->logN, x + ((size_t)l << c->logN), ((size_t)sizeQl * 8) << c->logN,
+        RT_CHECK(rt::d2d_2d(last, (size_t)8 << c->logN, x + ((size_t)l << c->logN), ((size_t)xs * 8) << c->logN,
                             (size_t)8 << c->logN, batch, (rt::stream_t)st));
     if (const TwPair* row = fused ? tb.rowFused : tb.rowUnfused)  // :742
         if (fhe_status s = elem_run<OP_MUL_CONST>(c, last, last, nullptr, row, &lastIdx, 1, batch, st, tb.who))
             return s;
     if (fused)
-        return drop_fused_store(c, last, &lastIdx, 0, tb.T, x, xDelta, sizeQl, tb.B, limbIdx, l, batch, out, out1, tmp, st, tb.who);
+        return drop_fused_store(c, last, &lastIdx, 0, tb.T, x, xDelta, xs, tb.B, limbIdx, l, batch, out, out1, tmp, st, tb.who);
     // tmp = SwitchModulus(row -> q_i) * A_i   (:703-705; :749, :752 with t folded into A_i)
     LimbSel sel;
     if (fhe_status s = make_sel(c, limbIdx, l, &sel, tb.who))
@@ -3200,7 +3202,7 @@ static fhe_status drop_last_run(fhe_ctx* c, const uint64_t* x, const uint32_t* l
         if (fhe_status s = fhe_ntt_fwd(c, tmp, limbIdx, l, batch, st))
             return s;
     // m_vectors[i] = m_vectors[i] * B_i + tmp  (:708-709, :752-753); x towers are sizeQl rows apart
-    return elem_run<OP_MUL_CONST_ADD>(c, out, x, tmp, tb.B, limbIdx, l, batch, st, tb.who, sizeQl, 0);
+    return elem_run<OP_MUL_CONST_ADD>(c, out, x, tmp, tb.B, limbIdx, l, batch, st, tb.who, xs, 0);
 }
 
 // ---- CKKS rescale ----
@@ -3540,6 +3542,247 @@ extern "C" fhe_status fhe_mod_reduce_limbs_pair(fhe_ctx* c, const uint64_t* x0, 
     ARG_CHECK(x1 && out1 && x1 != x0 && out1 != out0, "fhe_mod_reduce_limbs_pair: needs two distinct towers");
     return mod_reduce_limbs_run(c, x0, x1, limbIdx, sizeQl, t, negtInvModq, qlInvModq, evalFormat, 2, out0, out1, wsv, wsBytes, st,
                                 "fhe_mod_reduce_limbs_pair");
+}
+
+// ---- BGV level alignment of the automatic scaling modes: scalar, ModReduce, LevelReduce, ModReduce as one call ----
+// LeveledSHEBGVRNS::AdjustLevelsAndDepth[ToOne]InPlace (bgvrns-leveledshe.cpp:83-233) does to one operand, under FLEXIBLEAUTO[EXT], some of:
+// cv[i] *= scalar, ModReduceInternalInPlace (:44-75, DCRTPolyImpl::ModReduce on every element, dcrtpoly-impl.h:736-755), LevelReduce, and
+// ModReduceInternalInPlace again.  One call here: every row times scalar mod q_i; then, for k = 0 .. levels-1, the rows above drop[k]
+// discarded and ModReduce on row drop[k]; rows 0 .. nOut-1 kept.  x[batch][sizeQl][N] -> out[batch][nOut][N], same format.
+// The steps collapse as those of the CKKS rescale do: the chain kernel leaves rho_k, the canonical residue of -delta_k, in
+// the coefficient domain (its s[k] slot holds scalar * t^-1), prologue mode 3 sums the switched rows times (t mod q_i) * ..., and the row pass
+// stores (x - r) * C; the constants are host::mod_reduce_multi_tables.  ws: the three regions of fhe_rescale_multi_workspace_bytes.
+extern "C" size_t fhe_mod_reduce_multi_workspace_bytes(const fhe_ctx* c, uint32_t sizeQl, uint32_t levels, uint32_t batch) {
+    return fhe_rescale_multi_workspace_bytes(c, sizeQl, levels, batch);
+}
+// One fused chunk of d <= kMaxRescaleDrop steps: x holds towers of which rows 0 .. drop[0] are read (xRows rows or xDelta words apart), limbs
+// limbIdx[.] of the context with moduli qs[.]; drop[0] > drop[1] > ... are the rows of the steps; scale: the scalar's residues per row, or
+// null.  out0 (and out1 != null: tower 1 goes there, batch must be 2) dense [.][nOut][N].  On a ring of two passes: two inverse passes per run
+// of adjacent dropped rows (each run lands in its place in `rows`, ascending as the chain kernel reads them), the chain kernel, the column
+// pass whose load sums the d switched rows, the row pass whose store is (x - r) * C: five launches for adjacent rows, seven for two runs.
+static fhe_status mod_reduce_multi_chunk(fhe_ctx* c, const uint64_t* x, int64_t xDelta, uint32_t xRows, const uint32_t* limbIdx,
+                                         const uint64_t* qs, const uint32_t* drop, uint32_t d, uint32_t nOut, uint64_t t,
+                                         const uint64_t* scale, uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* rows, uint64_t* work,
+                                         void* st) {
+    uint32_t rowIdx[kMaxRescaleDrop];  // row p of `rows` is the row of step d-1-p
+    uint64_t qDrop[kMaxRescaleDrop], sDrop[kMaxRescaleDrop];
+    for (uint32_t k = 0; k < d; ++k) {
+        rowIdx[d - 1 - k] = limbIdx ? limbIdx[drop[k]] : drop[k];
+        qDrop[k]          = qs[drop[k]];
+        sDrop[k]          = scale ? scale[drop[k]] : 1;
+    }
+    std::vector<uint64_t> W(2 * (size_t)d * nOut), C(2 * (size_t)nOut);
+    uint64_t B[2 * kMaxRescaleDrop * kMaxRescaleDrop], S[2 * kMaxRescaleDrop];
+    host::mod_reduce_multi_tables(qDrop, d, qs, nOut, t, scale ? sDrop : nullptr, scale, B, W.data(), C.data(), S);
+    std::vector<uint32_t> wLimb((size_t)d * nOut);
+    std::vector<uint64_t> wVal((size_t)d * nOut), cVal(nOut);
+    for (uint32_t p = 0; p < d; ++p)
+        for (uint32_t i = 0; i < nOut; ++i) {
+            wLimb[(size_t)p * nOut + i] = limbIdx ? limbIdx[i] : i;
+            wVal[(size_t)p * nOut + i]  = W[2 * ((size_t)(d - 1 - p) * nOut + i)];
+        }
+    for (uint32_t i = 0; i < nOut; ++i)
+        cVal[i] = C[2 * i];
+    const TwPair *dW = nullptr, *dC = nullptr;
+    if (fhe_status s = const_table(c, wLimb.data(), wVal.data(), d * nOut, &dW))
+        return s;
+    if (fhe_status s = const_table(c, wLimb.data(), cVal.data(), nOut, &dC))
+        return s;
+    // lastPoly.SetFormat(COEFFICIENT) of every step (dcrtpoly-impl.h:741): one inverse transform per run of adjacent dropped rows
+    for (uint32_t k0 = 0; k0 < d;) {
+        uint32_t k1 = k0;
+        while (k1 + 1 < d && drop[k1 + 1] + 1 == drop[k1])
+            ++k1;
+        const uint32_t cnt = k1 - k0 + 1, p0 = d - 1 - k1;
+        NttOpts run;
+        run.src.stride = xRows, run.src.first = drop[k1], run.srcDelta = xDelta;
+        if (cnt != d)
+            run.dst.stride = d, run.dst.first = p0;
+        if (fhe_status s = ntt_run(c, true, x, rows, rowIdx + p0, cnt, batch, st, run))
+            return s;
+        k0 = k1 + 1;
+    }
+    RescaleChainArgs g;
+    g.rows = rows, g.logN = c->logN, g.d = d, g.batch = batch, g.hasScale = 1u;  // (s[k] = scalar * t^-1: never absent)
+    for (uint32_t k = 0; k < (uint32_t)kMaxRescaleDrop; ++k) {
+        g.q[k] = k < d ? qDrop[k] : 1;
+        g.s[k] = k < d ? TwPair{S[2 * k], S[2 * k + 1]} : TwPair{0, 0};
+        for (uint32_t j = 0; j < (uint32_t)kMaxRescaleDrop; ++j)
+            g.B[k][j] = (k < d && j < d) ? TwPair{B[2 * (k * d + j)], B[2 * (k * d + j) + 1]} : TwPair{0, 0};
+    }
+    FHE_LAUNCH(rescale_chain_kernel, tiles_for(c, batch), st, g);
+    LAUNCH_CHECK();
+    return drop_fused_store(c, rows, rowIdx, d, dW, x, xDelta, xRows, dC, limbIdx, nOut, batch, out0, out1, work, st, "fhe_mod_reduce_multi");
+}
+// the tables of one step as DCRTPolyImpl::ModReduce receives them, and whether they are the ones the library derives
+struct ModReduceStep {
+    host::ModReduceTables own;  // A from the caller's inverses; B, T, tInv, negtInv derived
+    uint64_t negtInv;           // the caller's (or the derived) negtInvModq
+    const uint64_t* inv;        // the caller's (or the derived) qlInvModq, drop[k] residues
+    bool derived;
+};
+static fhe_status mod_reduce_multi_run(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, const uint64_t* qs,
+                                       uint32_t sizeQl, const uint32_t* drop, uint32_t levels, uint32_t nOut, uint64_t t,
+                                       const uint64_t* scale, const std::vector<ModReduceStep>& steps, int evalFormat, uint32_t batch,
+                                       uint64_t* out, uint64_t* out1, uint64_t* ws, void* st) {
+    const size_t region = ((size_t)batch * sizeQl) << c->logN;
+    uint64_t *R0 = ws, *R[2] = {ws + region, ws + 2 * region};
+    bool fused = evalFormat && !mod_reduce_unfused() && ntt_epilogue_supported(c) && ntt_prologue_supported(c);
+    for (uint32_t k = 0; k < levels; ++k)
+        fused = fused && steps[k].derived;
+    for (uint32_t i = 0; scale && i < sizeQl; ++i)
+        fused = fused && scale[i] != 0;  // (a zero residue has no inverse to put into the load's weights)
+    if (levels == 1 && !scale && nOut == drop[0])
+        fused = false;  // the member itself on the rows below: drop_last_run's five launches
+    if (fused) {
+        const uint64_t* cur = x;
+        int64_t curDelta    = x1 ? x1 - x : 0;
+        uint32_t curRows    = sizeQl;
+        for (uint32_t k = 0, j = 0; k < levels; ++j) {
+            const uint32_t d    = std::min<uint32_t>(levels - k, (uint32_t)kMaxRescaleDrop);
+            const bool lastOne  = k + d == levels;
+            const uint32_t keep = lastOne ? nOut : drop[k + d - 1];
+            uint64_t* dst       = lastOne ? out : R[j & 1];
+            if (fhe_status s = mod_reduce_multi_chunk(c, cur, curDelta, curRows, limbIdx, qs, drop + k, d, keep, t, j == 0 ? scale : nullptr,
+                                                      batch, dst, lastOne ? out1 : nullptr, R0, R[j & 1], st))
+                return s;
+            cur = dst, curDelta = 0, curRows = keep, k += d;
+        }
+        return FHE_OK;
+    }
+    if (x1) {  // element by element
+        if (fhe_status s = mod_reduce_multi_run(c, x, nullptr, limbIdx, qs, sizeQl, drop, levels, nOut, t, scale, steps, evalFormat, 1, out,
+                                                nullptr, ws, st))
+            return s;
+        return mod_reduce_multi_run(c, x1, nullptr, limbIdx, qs, sizeQl, drop, levels, nOut, t, scale, steps, evalFormat, 1, out1, nullptr, ws,
+                                    st);
+    }
+    // the reference's steps: the scalar product on the rows that are read at all, then ModReduce on ever shorter towers
+    const uint64_t* cur = x;
+    uint32_t curRows    = sizeQl;
+    if (scale) {
+        const TwPair* dS = nullptr;
+        if (fhe_status s = const_table(c, limbIdx, scale, drop[0] + 1, &dS))
+            return s;
+        if (fhe_status s = elem_run<OP_MUL_CONST>(c, R[1], x, nullptr, dS, limbIdx, drop[0] + 1, batch, st, "fhe_mod_reduce_multi", sizeQl, 0))
+            return s;
+        cur = R[1], curRows = drop[0] + 1;
+    }
+    for (uint32_t k = 0; k < levels; ++k) {
+        const uint32_t n = drop[k] + 1, l = drop[k], lastIdx = limbIdx ? limbIdx[l] : l;
+        const ModReduceStep& sp = steps[k];
+        DropTabs tb{};
+        tb.who     = "fhe_mod_reduce";
+        tb.fusable = sp.derived && !mod_reduce_unfused();
+        if (fhe_status s = const_table(c, limbIdx, sp.own.A.data(), l, &tb.A))
+            return s;
+        if (fhe_status s = const_table(c, limbIdx, sp.inv, l, &tb.B))
+            return s;
+        if (fhe_status s = const_table(c, limbIdx, sp.own.T.data(), l, &tb.T))
+            return s;
+        if (fhe_status s = const_table(c, &lastIdx, &sp.negtInv, 1, &tb.rowUnfused))
+            return s;
+        if (fhe_status s = const_table(c, &lastIdx, &sp.own.tInv, 1, &tb.rowFused))
+            return s;
+        const bool direct = k + 1 == levels && nOut == l;
+        uint64_t* dst     = direct ? out : R[k & 1];
+        if (fhe_status s = drop_last_run(c, cur, limbIdx, n, tb, evalFormat, batch, dst, R0, st, nullptr, nullptr, curRows))
+            return s;
+        cur = dst, curRows = l;
+    }
+    if (cur != out)  // LevelReduce: the first nOut rows of every tower
+        RT_CHECK(rt::d2d_2d(out, ((size_t)nOut * 8) << c->logN, cur, ((size_t)curRows * 8) << c->logN, ((size_t)nOut * 8) << c->logN, batch,
+                            (rt::stream_t)st));
+    return FHE_OK;
+}
+// argument checks and tables of the entry points; negtInv / tabB null: the library's own tables over the leading limbs
+static fhe_status mod_reduce_multi_entry(fhe_ctx* c, const uint64_t* x, const uint64_t* x1, const uint32_t* limbIdx, uint32_t sizeQl,
+                                         uint64_t t, uint64_t scalar, const uint32_t* dropRows, uint32_t levels, uint32_t nOut,
+                                         const uint64_t* negtInv, const uint64_t* tabB, bool ownTables, int evalFormat, uint32_t batch,
+                                         uint64_t* out, uint64_t* out1, void* wsv, size_t wsBytes, void* st, const char* who) {
+    const std::string w(who);
+    if (fhe_status s = drop_check(who, c, x && out && wsv && (ownTables || (negtInv && tabB)), limbIdx, !limbIdx, sizeQl, levels, nOut, batch,
+                                  wsBytes, fhe_mod_reduce_multi_workspace_bytes(c, sizeQl, levels, batch), true))
+        return s;
+    ARG_CHECK(!dropRows || levels <= (uint32_t)kMaxRescaleDrop, w + ": a row list takes at most 4 levels");
+    std::vector<uint32_t> drop(levels);
+    bool rowsOk = true;
+    for (uint32_t k = 0; k < levels; ++k) {
+        drop[k] = dropRows ? dropRows[k] : sizeQl - 1 - k;
+        rowsOk  = rowsOk && drop[k] >= 1 && drop[k] < (k ? drop[k - 1] : sizeQl);
+    }
+    ARG_CHECK(rowsOk, w + ": dropRows must be strictly decreasing, below sizeQl and at least 1");
+    ARG_CHECK(nOut <= drop[levels - 1], w + ": nOut must be in [1, dropRows[levels - 1]]");
+    ARG_CHECK(out != x && out != x1 && (!out1 || (out1 != x && out1 != x1)), w + ": out must not alias x");
+    const std::vector<uint64_t> qs = tower_moduli(c, limbIdx, sizeQl);
+    ARG_CHECK(t >= 2, w + ": t must be invertible modulo the dropped limbs");
+    std::vector<ModReduceStep> steps(levels);
+    for (uint32_t k = 0; k < levels; ++k) {  // bgvrns-cryptoparameters.cpp at every step
+        ARG_CHECK(t % qs[drop[k]] != 0, w + ": t must be invertible modulo the dropped limbs");
+        steps[k].own = host::mod_reduce_tables(qs.data(), drop[k] + 1, t, nullptr);
+        ARG_CHECK(host::true_inverses(steps[k].own.B.data(), steps[k].own.B.data(), drop[k]), w + ": the moduli of a tower must be distinct");
+    }
+    size_t off = 0;
+    for (uint32_t k = 0; k < levels; off += drop[k], ++k) {
+        const uint32_t l  = drop[k];
+        ModReduceStep& sp = steps[k];
+        if (ownTables) {
+            sp.negtInv = sp.own.negtInv, sp.inv = sp.own.B.data(), sp.derived = true;
+            continue;
+        }
+        const host::ModReduceTables own = sp.own;
+        ARG_CHECK(negtInv[k] < qs[l], w + ": table entry is not reduced modulo its limb");
+        for (uint32_t i = 0; i < l; ++i)
+            ARG_CHECK(tabB[off + i] < qs[i], w + ": table entry is not reduced modulo its limb");
+        sp.own     = host::mod_reduce_tables(qs.data(), l + 1, t, tabB + off);
+        sp.negtInv = negtInv[k], sp.inv = tabB + off;
+        sp.derived = negtInv[k] == own.negtInv && host::true_inverses(own.B.data(), tabB + off, l);
+    }
+    std::vector<uint64_t> scale;
+    if (scalar != 1)
+        for (uint32_t i = 0; i < sizeQl; ++i)
+            scale.push_back(scalar % qs[i]);
+    if (fhe_status s = const_tables_trim(c))
+        return s;
+    std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
+    return mod_reduce_multi_run(c, x, x1, limbIdx, qs.data(), sizeQl, drop.data(), levels, nOut, t, scalar != 1 ? scale.data() : nullptr, steps,
+                                evalFormat, batch, out, out1, (uint64_t*)wsv, st);
+}
+extern "C" fhe_status fhe_mod_reduce_multi(fhe_ctx* c, const uint64_t* x, uint32_t sizeQl, uint64_t t, uint64_t scalar,
+                                           const uint32_t* dropRows, uint32_t levels, uint32_t nOut, int evalFormat, uint32_t batch,
+                                           uint64_t* out, void* wsv, size_t wsBytes, void* st) {
+    return mod_reduce_multi_entry(c, x, nullptr, nullptr, sizeQl, t, scalar, dropRows, levels, nOut, nullptr, nullptr, true, evalFormat, batch,
+                                  out, nullptr, wsv, wsBytes, st, "fhe_mod_reduce_multi");
+}
+extern "C" fhe_status fhe_mod_reduce_multi_limbs(fhe_ctx* c, const uint64_t* x, const uint32_t* limbIdx, uint32_t sizeQl, uint64_t t,
+                                                 uint64_t scalar, const uint32_t* dropRows, uint32_t levels, uint32_t nOut,
+                                                 const uint64_t* negtInvModq, const uint64_t* qlInvModq, int evalFormat, uint32_t batch,
+                                                 uint64_t* out, void* wsv, size_t wsBytes, void* st) {
+    return mod_reduce_multi_entry(c, x, nullptr, limbIdx, sizeQl, t, scalar, dropRows, levels, nOut, negtInvModq, qlInvModq, false, evalFormat,
+                                  batch, out, nullptr, wsv, wsBytes, st, "fhe_mod_reduce_multi_limbs");
+}
+// the two elements of one ciphertext (towers x0, x1 -> out0, out1, each allocated on its own) in the same launches; ws for batch 2
+extern "C" fhe_status fhe_mod_reduce_multi_limbs_pair(fhe_ctx* c, const uint64_t* x0, const uint64_t* x1, const uint32_t* limbIdx,
+                                                      uint32_t sizeQl, uint64_t t, uint64_t scalar, const uint32_t* dropRows, uint32_t levels,
+                                                      uint32_t nOut, const uint64_t* negtInvModq, const uint64_t* qlInvModq, int evalFormat,
+                                                      uint64_t* out0, uint64_t* out1, void* wsv, size_t wsBytes, void* st) {
+    ARG_CHECK(x1 && out1, "fhe_mod_reduce_multi_limbs_pair: null argument");
+    ARG_CHECK(x1 != x0 && out1 != out0, "fhe_mod_reduce_multi_limbs_pair: needs two distinct towers");
+    return mod_reduce_multi_entry(c, x0, x1, limbIdx, sizeQl, t, scalar, dropRows, levels, nOut, negtInvModq, qlInvModq, false, evalFormat, 2,
+                                  out0, out1, wsv, wsBytes, st, "fhe_mod_reduce_multi_limbs_pair");
+}
+// the host-side constants of one fused chunk (host::mod_reduce_multi_tables) as the library derives them, for checks against exact integers
+extern "C" fhe_status fhe_mod_reduce_multi_host_tables(const uint64_t* qDrop, uint32_t d, const uint64_t* qKeep, uint32_t nKeep, uint64_t t,
+                                                       const uint64_t* sDrop, const uint64_t* sKeep, uint64_t* B, uint64_t* W, uint64_t* C,
+                                                       uint64_t* S) {
+    ARG_CHECK(qDrop && qKeep && B && W && C && S && (!sDrop == !sKeep), "fhe_mod_reduce_multi_host_tables: null argument");
+    ARG_CHECK(d >= 1 && d <= (uint32_t)kMaxRescaleDrop && nKeep >= 1, "fhe_mod_reduce_multi_host_tables: bad sizes");
+    for (uint32_t k = 0; k < d; ++k)
+        ARG_CHECK(t >= 2 && t % qDrop[k] != 0, "fhe_mod_reduce_multi_host_tables: t must be invertible modulo the dropped limbs");
+    for (uint32_t i = 0; sKeep && i < nKeep; ++i)
+        ARG_CHECK(sKeep[i] % qKeep[i] != 0, "fhe_mod_reduce_multi_host_tables: a zero scalar residue has no inverse");
+    host::mod_reduce_multi_tables(qDrop, d, qKeep, nKeep, t, sDrop, sKeep, B, W, C, S);
+    return FHE_OK;
 }
 
 // ---- BGV ModReduce over several limbs of a COEFFICIENT tower, and decryption ----

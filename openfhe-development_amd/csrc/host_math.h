@@ -180,6 +180,24 @@ inline void rescale_multi_tables(const uint64_t* qDrop, uint32_t d, const uint64
         C[2 * i] = cst, C[2 * i + 1] = shoup(cst, qi);
     }
 }
+// The BGV twin: d DCRTPolyImpl::ModReduce steps (dcrtpoly-impl.h:736-755) with plaintext modulus t as one pass, the scalar s of
+// LeveledSHEBGVRNS::AdjustLevelsAndDepthInPlace (bgvrns-leveledshe.cpp:83-233) in front.  The tables above with two changes:
+//   S[k]    = sDrop[k] * t^-1 mod qDrop[k]                           the chain's rows are the canonical residues of -delta_k
+//   W[k][i] = (t mod qKeep[i]) * sKeep[i]^-1 * prod_{j<k} qDrop[j]   the switched rows enter the sum times t
+// B and C are unchanged.  t must be invertible modulo every qDrop[k].
+inline void mod_reduce_multi_tables(const uint64_t* qDrop, uint32_t d, const uint64_t* qKeep, uint32_t nKeep, uint64_t t,
+                                    const uint64_t* sDrop, const uint64_t* sKeep, uint64_t* B, uint64_t* W, uint64_t* C, uint64_t* S) {
+    rescale_multi_tables(qDrop, d, qKeep, nKeep, sDrop, sKeep, B, W, C, S);
+    for (uint32_t k = 0; k < d; ++k) {
+        S[2 * k]     = mulmod(S[2 * k], invmod(t % qDrop[k], qDrop[k]), qDrop[k]);
+        S[2 * k + 1] = shoup(S[2 * k], qDrop[k]);
+    }
+    for (uint32_t k = 0; k < d; ++k)
+        for (uint32_t i = 0; i < nKeep; ++i) {
+            uint64_t* w = &W[2 * ((size_t)k * nKeep + i)];
+            w[0] = mulmod(w[0], t % qKeep[i], qKeep[i]), w[1] = shoup(w[0], qKeep[i]);
+        }
+}
 
 }  // namespace host
 }  // namespace fhe

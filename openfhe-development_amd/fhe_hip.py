@@ -166,6 +166,13 @@ class Lib:
         S("fhe_mod_reduce", C.c_int, [vp, vp, u32, u64, C.c_int, u32, vp, vp, C.c_size_t, vp])
         S("fhe_mod_reduce_limbs", C.c_int, [vp, vp, u32p, u32, u64, u64, u64p, C.c_int, u32, vp, vp, C.c_size_t, vp])
         S("fhe_mod_reduce_limbs_pair", C.c_int, [vp, vp, vp, u32p, u32, u64, u64, u64p, C.c_int, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_mod_reduce_multi_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_mod_reduce_multi", C.c_int, [vp, vp, u32, u64, u64, u32p, u32, u32, C.c_int, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_mod_reduce_multi_limbs", C.c_int, [vp, vp, u32p, u32, u64, u64, u32p, u32, u32, u64p, u64p, C.c_int, u32, vp, vp, C.c_size_t,
+                                                  vp])
+        S("fhe_mod_reduce_multi_limbs_pair", C.c_int, [vp, vp, vp, u32p, u32, u64, u64, u32p, u32, u32, u64p, u64p, C.c_int, vp, vp, vp,
+                                                       C.c_size_t, vp])
+        S("fhe_mod_reduce_multi_host_tables", C.c_int, [u64p, u32, u64p, u32, u64, u64p, u64p, u64p, u64p, u64p, u64p])
         S("fhe_mod_reduce_chain_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
         S("fhe_mod_reduce_chain", C.c_int, [vp, vp, u32p, u32, u32, u64, u32, vp, vp, C.c_size_t, vp])
         S("fhe_mod_reduce_to_t", C.c_int, [vp, vp, u32p, u32, u64, u32, vp, vp, C.c_size_t, vp])
@@ -1099,6 +1106,184 @@ def mod_reduce_pair(ctx, x0, x1, t, negt_inv_modq, ql_inv_modq, stream=None):
     finally:
         ctx.free(ws)
     return o0, o1
+
+
+def _drop_rows(sizeQl, levels, drop_rows):
+    """(levels, the row list and its ctypes pointer or None, the lowest dropped row)"""
+    if drop_rows is None:
+        return levels, None, None, sizeQl - levels
+    rows = np.ascontiguousarray(drop_rows, dtype=np.uint32)
+    return len(rows), rows, rows.ctypes.data_as(u32p), int(rows[-1]) if len(rows) else 0
+
+
+def mod_reduce_multi(ctx, x, t, levels=1, scalar=1, drop_rows=None, n_out=None, stream=None):
+    """The level alignment of BGV's automatic scaling modes on one operand (LeveledSHEBGVRNS::AdjustLevelsAndDepthInPlace,
+    bgvrns-leveledshe.cpp:83-233) as one call, fhe_mod_reduce_multi: every row of a Tower over context limbs [0, sizeQl) times `scalar`, then
+    DCRTPoly::ModReduce on the rows drop_rows (strictly decreasing; None: the last `levels` rows) with the rows above each discarded, of
+    which the first n_out rows (default: all below the lowest dropped row) are produced."""
+    sizeQl = x.n_limbs
+    levels, rows, rp, lowest = _drop_rows(sizeQl, levels, drop_rows)
+    n_out = lowest if n_out is None else n_out
+    need = ctx.lib.L.fhe_mod_reduce_multi_workspace_bytes(ctx.h, sizeQl, levels, x.batch)
+    ws = ctx.malloc(max(need, 8))
+    out = ctx.empty(x.batch, max(n_out, 1), None, x.fmt)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_mod_reduce_multi(ctx.h, x.ptr, sizeQl, t, scalar, rp, levels, n_out, 1 if x.fmt == EVALUATION else 0,
+                                                     x.batch, out.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
+    return out
+
+
+def mod_reduce_multi_limbs(ctx, x, t, negt_inv_modq, ql_inv_modq, levels=1, scalar=1, drop_rows=None, n_out=None, stream=None):
+    """the same on a Tower over ANY limbs of the context (x.limb_idx) with the caller's tables: negt_inv_modq[k] and, one after the other,
+    step k's drop_rows[k] residues of qlInvModq (CryptoParametersBGVRNS::GetNegtInvModq / GetqlInvModq of that row)."""
+    sizeQl = x.n_limbs
+    levels, rows, rp, lowest = _drop_rows(sizeQl, levels, drop_rows)
+    n_out = lowest if n_out is None else n_out
+    need = ctx.lib.L.fhe_mod_reduce_multi_workspace_bytes(ctx.h, sizeQl, levels, x.batch)
+    ws = ctx.malloc(max(need, 8))
+    kept = None if x.limb_idx is None else x.limb_idx[:n_out]
+    out = ctx.empty(x.batch, max(n_out, 1), kept, x.fmt)
+    a, ap = _u64_or_null(negt_inv_modq)
+    b, bp = _u64_or_null(ql_inv_modq)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_mod_reduce_multi_limbs(ctx.h, x.ptr, x._li(), sizeQl, t, scalar, rp, levels, n_out, ap, bp,
+                                                           1 if x.fmt == EVALUATION else 0, x.batch, out.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
+    return out
+
+
+def mod_reduce_multi_pair(ctx, x0, x1, t, negt_inv_modq, ql_inv_modq, levels=1, scalar=1, drop_rows=None, n_out=None, stream=None):
+    """the two elements of a ciphertext (two Towers of batch 1, allocated on their own) through fhe_mod_reduce_multi_limbs_pair"""
+    sizeQl = x0.n_limbs
+    levels, rows, rp, lowest = _drop_rows(sizeQl, levels, drop_rows)
+    n_out = lowest if n_out is None else n_out
+    need = ctx.lib.L.fhe_mod_reduce_multi_workspace_bytes(ctx.h, sizeQl, levels, 2)
+    ws = ctx.malloc(max(need, 8))
+    kept = None if x0.limb_idx is None else x0.limb_idx[:n_out]
+    o0, o1 = ctx.empty(1, max(n_out, 1), kept, x0.fmt), ctx.empty(1, max(n_out, 1), kept, x0.fmt)
+    a, ap = _u64_or_null(negt_inv_modq)
+    b, bp = _u64_or_null(ql_inv_modq)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_mod_reduce_multi_limbs_pair(ctx.h, x0.ptr, x1.ptr, x0._li(), sizeQl, t, scalar, rp, levels, n_out, ap, bp,
+                                                                1 if x0.fmt == EVALUATION else 0, o0.ptr, o1.ptr, ws, need, stream))
+        ctx.sync(stream)
+    finally:
+        ctx.free(ws)
+    return o0, o1
+
+
+def mod_reduce_multi_tables(qs, t, drop_rows):
+    """the tables fhe_mod_reduce_multi_limbs takes, as CryptoParametersBGVRNS holds them for a tower over moduli qs: negtInvModq of every
+    dropped row and, one after the other, the rows' qlInvModq"""
+    negt, inv = [], []
+    for r in drop_rows:
+        ql = int(qs[r])
+        negt.append((-pow(t % ql, -1, ql)) % ql)
+        inv += [pow(ql % int(qs[i]), -1, int(qs[i])) for i in range(r)]
+    return np.array(negt, np.uint64), np.array(inv, np.uint64)
+
+
+class BgvOperand:
+    """what AdjustLevelsAndDepthInPlace reads of a ciphertext, and what bgv_adjust_plan decides for it: `scalar` (1: none), drop_rows (the
+    rows ModReduce is called on, strictly decreasing) and n_out (the rows that are left)"""
+
+    def __init__(self, level, noise_scale_deg, size_ql, scaling_factor_int):
+        self.level, self.noise_scale_deg, self.size_ql, self.scaling_factor_int = level, noise_scale_deg, size_ql, int(scaling_factor_int)
+        self.scalar, self.drop_rows, self.n_out = 1, [], size_ql
+
+    def untouched(self):
+        return self.scalar == 1 and not self.drop_rows and self.n_out == self.size_ql
+
+    # the three members, as bookkeeping (bgvrns-leveledshe.cpp:44-81, 235-247)
+    def _eval_mult_core(self, scalar, t):
+        assert self.scalar == 1 and not self.drop_rows and self.n_out == self.size_ql, "the scalar product comes first"
+        self.scalar = int(scalar)
+        self.noise_scale_deg += 1
+        self.scaling_factor_int = self.scaling_factor_int * int(scalar) % t
+
+    def _mod_reduce(self, t, mod_reduce_factor_int):
+        r = self.n_out - 1
+        assert r >= 1, "Too few towers to support ModReduce."
+        self.drop_rows.append(r)
+        self.n_out, self.level, self.noise_scale_deg = r, self.level + 1, self.noise_scale_deg - 1
+        self.scaling_factor_int = self.scaling_factor_int * pow(int(mod_reduce_factor_int[r]) % t, -1, t) % t
+
+    def _level_reduce(self, levels):
+        self.n_out, self.level = self.n_out - levels, self.level + levels
+
+
+def bgv_adjust_plan(ct1, ct2, t, mod_reduce_factor_int, scaling_factor_int_big, to_one=False):
+    """LeveledSHEBGVRNS::AdjustLevelsAndDepthInPlace (bgvrns-leveledshe.cpp:83-224; to_one: AdjustLevelsAndDepthToOneInPlace, :226-233) under
+    FLEXIBLEAUTO / FLEXIBLEAUTOEXT as a plan: nothing touches a device.  ct1 / ct2: (level, noiseScaleDeg, sizeQl, scalingFactorInt);
+    mod_reduce_factor_int[i] = GetModReduceFactorInt(i), scaling_factor_int_big[i] = GetScalingFactorIntBig(i).  Returns two BgvOperand with
+    the new (level, noise_scale_deg, scaling_factor_int) and the (scalar, drop_rows, n_out) that bgv_adjust runs."""
+    a, b = BgvOperand(*ct1), BgvOperand(*ct2)
+    mrf, big = mod_reduce_factor_int, scaling_factor_int_big
+    inv = lambda v: pow(int(v) % t, -1, t)
+    if a.level != b.level:
+        lo, hi = (a, b) if a.level < b.level else (b, a)  # the branches for c1lvl > c2lvl are those for c1lvl < c2lvl with the names swapped
+        gap = hi.level - lo.level
+        if lo.noise_scale_deg == 2:
+            if hi.noise_scale_deg == 2:
+                lo._eval_mult_core(hi.scaling_factor_int * inv(lo.scaling_factor_int) % t * (int(mrf[lo.size_ql - 1]) % t) % t, t)
+                lo._mod_reduce(t, mrf)
+                if gap > 1:
+                    lo._level_reduce(gap - 1)
+                lo.scaling_factor_int = hi.scaling_factor_int
+            elif gap == 1:
+                lo._mod_reduce(t, mrf)
+            else:
+                lo._eval_mult_core(int(big[hi.level - 1]) % t * inv(lo.scaling_factor_int) % t * (int(mrf[lo.size_ql - 1]) % t) % t, t)
+                lo._mod_reduce(t, mrf)
+                if gap > 2:
+                    lo._level_reduce(gap - 2)
+                lo._mod_reduce(t, mrf)
+                lo.scaling_factor_int = hi.scaling_factor_int
+        elif hi.noise_scale_deg == 2:
+            lo._eval_mult_core(hi.scaling_factor_int * inv(lo.scaling_factor_int) % t, t)
+            lo._level_reduce(gap)
+            lo.scaling_factor_int = hi.scaling_factor_int
+        else:
+            lo._eval_mult_core(int(big[hi.level - 1]) % t * inv(lo.scaling_factor_int) % t, t)
+            if gap > 1:
+                lo._level_reduce(gap - 1)
+            lo._mod_reduce(t, mrf)
+            lo.scaling_factor_int = hi.scaling_factor_int
+    elif a.noise_scale_deg < b.noise_scale_deg:
+        a._eval_mult_core(a.scaling_factor_int, t)
+    elif b.noise_scale_deg < a.noise_scale_deg:
+        b._eval_mult_core(b.scaling_factor_int, t)
+    if to_one and a.noise_scale_deg == 2:
+        a._mod_reduce(t, mrf)
+        b._mod_reduce(t, mrf)
+    return a, b
+
+
+def bgv_adjust(ctx, c0, c1, plan, t, qs=None, stream=None):
+    """run one operand's plan on the two elements of its ciphertext (Towers of batch 1, allocated on their own): nothing when the plan
+    leaves it alone, fhe_mul_const on the n_out rows that are left when no ModReduce is in it, else ONE fhe_mod_reduce_multi_limbs_pair.
+    qs: the moduli of the tower's rows (default: those of its context limbs).  Returns the two Towers (the inputs when untouched)."""
+    if plan.untouched():
+        return c0, c1
+    sizeQl = c0.n_limbs
+    if qs is None:
+        qs = ctx.q[:sizeQl] if c0.limb_idx is None else ctx.q[c0.limb_idx]
+    qs = [int(v) for v in qs]
+    kept = None if c0.limb_idx is None else c0.limb_idx[:plan.n_out]
+    if not plan.drop_rows:
+        consts = np.array([plan.scalar % q for q in qs[:plan.n_out]], np.uint64)
+        o0, o1 = ctx.empty(1, plan.n_out, kept, c0.fmt), ctx.empty(1, plan.n_out, kept, c0.fmt)
+        ctx.lib.check(ctx.lib.L.fhe_mul_const_pair(ctx.h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, consts.ctypes.data_as(u64p),
+                                                   None if kept is None else kept.ctypes.data_as(u32p), plan.n_out, stream))
+        ctx.sync(stream)
+        return o0, o1
+    negt, inv = mod_reduce_multi_tables(qs, t, plan.drop_rows)
+    return mod_reduce_multi_pair(ctx, c0, c1, t, negt, inv, scalar=plan.scalar, drop_rows=plan.drop_rows, n_out=plan.n_out, stream=stream)
 
 
 def mod_reduce_chain(ctx, x, levels, t, stream=None):

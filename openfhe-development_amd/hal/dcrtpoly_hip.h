@@ -258,6 +258,86 @@ public:
         x0 = std::move(o0);
         x1 = std::move(o1);
     }
+    // The level alignment of BGV's automatic scaling modes on one operand (LeveledSHEBGVRNS::AdjustLevelsAndDepthInPlace,
+    // bgvrns-leveledshe.cpp:83-233) as one call: every row times `scalar` (1: none), then ModReduce (dcrtpoly-impl.h:736-755) on the rows
+    // dropRows (strictly decreasing; empty: the last row) with the rows above each discarded, of which the leading nOut rows (0: all below the
+    // lowest dropped row) are left.  Tables derived from the moduli and t; the tower must use the leading context limbs (fhe_mod_reduce_multi)
+    void ModReduceMulti(uint64_t t, uint64_t scalar = 1, std::vector<uint32_t> dropRows = {}, uint32_t nOut = 0) {
+        if (!m_idx.empty())
+            throw Error("ModReduceMulti: tower must use the leading context limbs");
+        if (dropRows.empty())
+            dropRows.push_back(m_limbs - 1);
+        if (nOut == 0)
+            nOut = dropRows.back();
+        if (nOut < 1 || nOut >= m_limbs)
+            throw Error("ModReduceMulti: nOut out of range");
+        const uint32_t levels = (uint32_t)dropRows.size();
+        DCRTPolyHip out(m_params, nOut, m_format, m_batch);
+        size_t wsb = fhe_mod_reduce_multi_workspace_bytes(m_params->ctx(), m_limbs, levels, m_batch);
+        void* ws   = nullptr;
+        check(fhe_malloc(m_params->ctx(), wsb ? wsb : 8, &ws));
+        fhe_status s = fhe_mod_reduce_multi(m_params->ctx(), m_data, m_limbs, t, scalar, dropRows.data(), levels, nOut, m_format == EVALUATION,
+                                            m_batch, out.m_data, ws, wsb, nullptr);
+        fhe_stream_sync(m_params->ctx(), nullptr);
+        fhe_free(m_params->ctx(), ws);
+        check(s);
+        *this = std::move(out);
+    }
+    // ... of the two elements of one ciphertext (batch 1 each, allocated on their own, over any limbs of the context) in the same launches,
+    // with the caller's tables: negtInvModq[k] of row dropRows[k] and, one after the other, the rows' qlInvModq (dropRows[k] residues each)
+    // (fhe_mod_reduce_multi_limbs_pair)
+    static void ModReduceMultiPair(DCRTPolyHip& x0, DCRTPolyHip& x1, uint64_t t, uint64_t scalar, const std::vector<uint32_t>& dropRows,
+                                   uint32_t nOut, const std::vector<uint64_t>& negtInvModq, const std::vector<uint64_t>& qlInvModq) {
+        if (x0.m_batch != 1 || x1.m_batch != 1 || x0.m_limbs != x1.m_limbs || x0.m_format != x1.m_format || x0.m_idx != x1.m_idx)
+            throw Error("ModReduceMultiPair: two single towers over the same limbs in the same format expected");
+        size_t entries = 0;
+        for (uint32_t r : dropRows)
+            entries += r;
+        if (dropRows.empty() || negtInvModq.size() < dropRows.size() || qlInvModq.size() < entries)
+            throw Error("ModReduceMultiPair: one negtInvModq entry per dropped row and dropRows[k] qlInvModq entries per step expected");
+        if (nOut < 1 || nOut > dropRows.back())
+            throw Error("ModReduceMultiPair: nOut out of range");
+        const auto& P = x0.m_params;
+        std::vector<uint32_t> kept(x0.m_idx.begin(), x0.m_idx.empty() ? x0.m_idx.end() : x0.m_idx.begin() + nOut);
+        DCRTPolyHip o0(P, nOut, x0.m_format, 1, kept), o1(P, nOut, x0.m_format, 1, kept);
+        const uint32_t levels = (uint32_t)dropRows.size();
+        size_t wsb = fhe_mod_reduce_multi_workspace_bytes(P->ctx(), x0.m_limbs, levels, 2);
+        void* ws   = nullptr;
+        check(fhe_malloc(P->ctx(), wsb ? wsb : 8, &ws));
+        fhe_status s = fhe_mod_reduce_multi_limbs_pair(P->ctx(), x0.m_data, x1.m_data, x0.idx(), x0.m_limbs, t, scalar, dropRows.data(), levels,
+                                                       nOut, negtInvModq.data(), qlInvModq.data(), x0.m_format == EVALUATION, o0.m_data,
+                                                       o1.m_data, ws, wsb, nullptr);
+        fhe_stream_sync(P->ctx(), nullptr);
+        fhe_free(P->ctx(), ws);
+        check(s);
+        x0 = std::move(o0);
+        x1 = std::move(o1);
+    }
+    // the leading nOut rows of the two elements of one ciphertext times `scalar`: the EvalMultCoreInPlace and LevelReduceInternalInPlace of
+    // a plan without a ModReduce (fhe_mul_const_pair on nOut rows)
+    static void TimesScalarPair(DCRTPolyHip& x0, DCRTPolyHip& x1, uint64_t scalar, uint32_t nOut) {
+        if (x0.m_batch != 1 || x1.m_batch != 1 || x0.m_limbs != x1.m_limbs || x0.m_format != x1.m_format || x0.m_idx != x1.m_idx)
+            throw Error("TimesScalarPair: two single towers over the same limbs in the same format expected");
+        if (nOut < 1 || nOut > x0.m_limbs)
+            throw Error("TimesScalarPair: nOut out of range");
+        const auto& P = x0.m_params;
+        std::vector<uint32_t> kept(x0.m_idx.begin(), x0.m_idx.empty() ? x0.m_idx.end() : x0.m_idx.begin() + nOut);
+        std::vector<uint64_t> consts(nOut);
+        for (uint32_t i = 0; i < nOut; ++i)
+            consts[i] = scalar % P->GetModuli()[x0.m_idx.empty() ? i : x0.m_idx[i]];
+        DCRTPolyHip o0(P, nOut, x0.m_format, 1, kept), o1(P, nOut, x0.m_format, 1, kept);
+        check(fhe_mul_const_pair(P->ctx(), o0.m_data, o1.m_data, x0.m_data, x1.m_data, consts.data(), o0.idx(), nOut, nullptr));
+        check(fhe_stream_sync(P->ctx(), nullptr));
+        x0 = std::move(o0);
+        x1 = std::move(o1);
+    }
+    // the moduli of the tower's rows
+    std::vector<uint64_t> GetRowModuli() const {
+        std::vector<uint64_t> qs(m_limbs);
+        for (uint32_t i = 0; i < m_limbs; ++i)
+            qs[i] = m_params->GetModuli()[m_idx.empty() ? i : m_idx[i]];
+        return qs;
+    }
     // ModReduce `levels` times on a COEFFICIENT tower, its last limb first, in one launch per 16 limbs: what the COEFFICIENT branch of
     // PKEBGVRNS::Decrypt (bgvrns-pke.cpp:73-81) does to every element (fhe_mod_reduce_chain; the tables are derived from the moduli and t)
     void ModReduceChain(uint32_t levels, uint64_t t) {
@@ -398,6 +478,121 @@ private:
     std::vector<uint32_t> m_idx;
     uint64_t* m_data = nullptr;
 };
+
+// ---- BGV automatic scaling: the case table of LeveledSHEBGVRNS::AdjustLevelsAndDepth[ToOne]InPlace (bgvrns-leveledshe.cpp:83-233) as a plan
+// (host arithmetic modulo t only), and its executor.
+// What the reference reads of a ciphertext, and what the plan decides for it.
+struct BgvOperand {
+    uint32_t level = 0, noiseScaleDeg = 1, sizeQl = 0;
+    uint64_t scalingFactorInt = 1;
+    // the plan: scalar (1: none), the rows ModReduce is called on (strictly decreasing), the rows that are left
+    uint64_t scalar = 1;
+    std::vector<uint32_t> dropRows;
+    uint32_t nOut = 0;
+    BgvOperand() = default;
+    BgvOperand(uint32_t lvl, uint32_t depth, uint32_t rows, uint64_t scf)
+        : level(lvl), noiseScaleDeg(depth), sizeQl(rows), scalingFactorInt(scf), nOut(rows) {}
+    bool Untouched() const { return scalar == 1 && dropRows.empty() && nOut == sizeQl; }
+};
+namespace bgvplan {
+inline uint64_t mulmod(uint64_t a, uint64_t b, uint64_t t) { return (uint64_t)((unsigned __int128)(a % t) * (b % t) % t); }
+inline uint64_t invmod(uint64_t a, uint64_t t) {  // NativeInteger::ModInverse: extended Euclid, t need not be prime
+    __int128 r0 = t, r1 = a % t, s0 = 0, s1 = 1;
+    while (r1) {
+        const __int128 qt = r0 / r1, r2 = r0 - qt * r1, s2 = s0 - qt * s1;
+        r0 = r1, r1 = r2, s0 = s1, s1 = s2;
+    }
+    if (r0 != 1)
+        throw Error("BgvAdjustPlan: a scaling factor is not invertible modulo t");
+    return (uint64_t)((s0 % (__int128)t + t) % t);
+}
+// the three members as bookkeeping (bgvrns-leveledshe.cpp:44-81, 235-247)
+inline void evalMultCore(BgvOperand& c, uint64_t scalar, uint64_t t) {
+    if (!c.Untouched())
+        throw Error("BgvAdjustPlan: the scalar product comes first");
+    c.scalar = scalar;
+    c.noiseScaleDeg += 1;
+    c.scalingFactorInt = mulmod(c.scalingFactorInt, scalar, t);
+}
+inline void modReduce(BgvOperand& c, uint64_t t, const std::vector<uint64_t>& modReduceFactorInt) {
+    if (c.nOut < 2)
+        throw Error("Too few towers to support ModReduce.");
+    const uint32_t r = c.nOut - 1;
+    c.dropRows.push_back(r);
+    c.nOut = r, c.level += 1, c.noiseScaleDeg -= 1;
+    c.scalingFactorInt = mulmod(c.scalingFactorInt, invmod(modReduceFactorInt.at(r), t), t);
+}
+inline void levelReduce(BgvOperand& c, uint32_t levels) { c.nOut -= levels, c.level += levels; }
+}  // namespace bgvplan
+// modReduceFactorInt[i] = CryptoParametersBGVRNS::GetModReduceFactorInt(i), scalingFactorIntBig[i] = GetScalingFactorIntBig(i); ct1 / ct2 come
+// in with (level, noiseScaleDeg, sizeQl, scalingFactorInt) and leave with the new values and their plans.  toOne: AdjustLevelsAndDepthToOneInPlace.
+inline void BgvAdjustPlan(BgvOperand& ct1, BgvOperand& ct2, uint64_t t, const std::vector<uint64_t>& modReduceFactorInt,
+                          const std::vector<uint64_t>& scalingFactorIntBig, bool toOne = false) {
+    using namespace bgvplan;
+    const auto& mrf = modReduceFactorInt;
+    if (ct1.level != ct2.level) {
+        // the branches for c1lvl > c2lvl are those for c1lvl < c2lvl with the names swapped
+        BgvOperand &lo = ct1.level < ct2.level ? ct1 : ct2, &hi = ct1.level < ct2.level ? ct2 : ct1;
+        const uint32_t gap = hi.level - lo.level;
+        const uint64_t scf1Inv = invmod(lo.scalingFactorInt, t);
+        if (lo.noiseScaleDeg == 2) {
+            if (hi.noiseScaleDeg == 2) {
+                evalMultCore(lo, mulmod(mulmod(hi.scalingFactorInt, scf1Inv, t), mrf.at(lo.sizeQl - 1), t), t);
+                modReduce(lo, t, mrf);
+                if (gap > 1)
+                    levelReduce(lo, gap - 1);
+                lo.scalingFactorInt = hi.scalingFactorInt;
+            }
+            else if (gap == 1)
+                modReduce(lo, t, mrf);
+            else {
+                evalMultCore(lo, mulmod(mulmod(scalingFactorIntBig.at(hi.level - 1), scf1Inv, t), mrf.at(lo.sizeQl - 1), t), t);
+                modReduce(lo, t, mrf);
+                if (gap > 2)
+                    levelReduce(lo, gap - 2);
+                modReduce(lo, t, mrf);
+                lo.scalingFactorInt = hi.scalingFactorInt;
+            }
+        }
+        else if (hi.noiseScaleDeg == 2) {
+            evalMultCore(lo, mulmod(hi.scalingFactorInt, scf1Inv, t), t);
+            levelReduce(lo, gap);
+            lo.scalingFactorInt = hi.scalingFactorInt;
+        }
+        else {
+            evalMultCore(lo, mulmod(scalingFactorIntBig.at(hi.level - 1), scf1Inv, t), t);
+            if (gap > 1)
+                levelReduce(lo, gap - 1);
+            modReduce(lo, t, mrf);
+            lo.scalingFactorInt = hi.scalingFactorInt;
+        }
+    }
+    else if (ct1.noiseScaleDeg < ct2.noiseScaleDeg)
+        evalMultCore(ct1, ct1.scalingFactorInt, t);
+    else if (ct2.noiseScaleDeg < ct1.noiseScaleDeg)
+        evalMultCore(ct2, ct2.scalingFactorInt, t);
+    if (toOne && ct1.noiseScaleDeg == 2) {
+        modReduce(ct1, t, mrf);
+        modReduce(ct2, t, mrf);
+    }
+}
+// runs one operand's plan on the two elements of its ciphertext: nothing, fhe_mul_const on the nOut rows that are left when no ModReduce is in
+// the plan, else ONE fhe_mod_reduce_multi_limbs_pair with the tables of CryptoParametersBGVRNS (GetNegtInvModq / GetqlInvModq) derived here
+inline void BgvAdjust(DCRTPolyHip& c0, DCRTPolyHip& c1, const BgvOperand& plan, uint64_t t) {
+    if (plan.Untouched())
+        return;
+    if (plan.dropRows.empty())
+        return DCRTPolyHip::TimesScalarPair(c0, c1, plan.scalar, plan.nOut);
+    const std::vector<uint64_t> qs = c0.GetRowModuli();
+    std::vector<uint64_t> negt, inv;
+    for (uint32_t r : plan.dropRows) {
+        const uint64_t ql = qs.at(r);
+        negt.push_back((ql - bgvplan::invmod(t % ql, ql)) % ql);
+        for (uint32_t i = 0; i < r; ++i)
+            inv.push_back(bgvplan::invmod(ql % qs[i], qs[i]));
+    }
+    DCRTPolyHip::ModReduceMultiPair(c0, c1, t, plan.scalar, plan.dropRows, plan.nOut, negt, inv);
+}
 
 // KeySwitchHYBRID over a context holding Q then P limbs (keyswitch-hybrid.cpp:308-435)
 class KeySwitchHybrid {
