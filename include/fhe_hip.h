@@ -799,7 +799,8 @@ fhe_status fhe_checksum(fhe_ctx* ctx, const uint64_t* x, uint32_t rows, uint64_t
 /* Kernel launches issued by this library since it was loaded, by kernel: writes lines "<kernel> <launches>\n" (most frequent first)
  * into buf (at most cap bytes, NUL-terminated when cap > 0) and returns the length the full text needs; *total, when given, receives
  * the sum.  (Tuning aid: the launch count of one pke operation is the difference of two calls.)  The hand-over instances of the inverse
- * NTT passes are counted under their kernels' names and once more on lines "<kernel><HAND> <launches>". */
+ * NTT passes are counted under their kernels' names and once more on lines "<kernel><HAND> <launches>", the two passes of
+ * the forward 6 + 10 split at N = 2^16 likewise on lines "<kernel><SPLIT6> <launches>". */
 size_t fhe_launch_stats(char* buf, size_t cap, uint64_t* total);
 
 /* ---- host-side parameter helpers (no device work) -------------------------------------------------

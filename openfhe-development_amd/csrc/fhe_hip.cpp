@@ -562,11 +562,16 @@ static uint32_t env_u32(const char* name, uint32_t dflt) {
 //   FHE_NTT_HANDOVER = 0 / 1    forces the hand-over between the passes of an inverse transform off / on; any other value is
 //                               reported and means off
 //   FHE_NTT_T1 = 4 / 5          another split of a two-pass ring (ntt_t1)
+//   FHE_NTT_SPLIT6 = 0 / 1 / fwd / inv   the 6 + 10 split of N = 2^16 (ntt_run) off / on / forward transforms only / inverse only.  Only the
+//                               forward direction has the pair (profiles/ntt_split6.md), so 1 and fwd are the default and inv is 0; any
+//                               other value is reported and means off
 constexpr bool kHandoverDefault = true;
+constexpr bool kSplit6Default = true;
 struct NttSwitches {
     int row8 = -1, row8X1 = -1;  // -1: not forced
     uint32_t row8Batch = 0, t1 = 0;  // 0: not forced
     bool handover = kHandoverDefault;
+    bool split6 = kSplit6Default;
 };
 static const NttSwitches& ntt_switches() {
     static const NttSwitches sw = [] {
@@ -585,6 +590,12 @@ static const NttSwitches& ntt_switches() {
                 fprintf(stderr, "fhe_hip: FHE_NTT_HANDOVER=%s is neither 0 nor 1: hand-over is off\n", v);
         }
         s.t1 = env_u32("FHE_NTT_T1", 0);
+        if (const char* v = std::getenv("FHE_NTT_SPLIT6")) {
+            const std::string w = v;
+            s.split6 = w == "1" || w == "fwd";
+            if (!s.split6 && w != "0" && w != "inv")
+                fprintf(stderr, "fhe_hip: FHE_NTT_SPLIT6=%s is none of 0, 1, fwd, inv: the 6 + 10 split is off\n", v);
+        }
         return s;
     }();
     return sw;
@@ -814,6 +825,12 @@ static bool static_handover_instance(const NttPass& p, const NttPassArgs* a, voi
                                                               kThreads, true, stream, *a))
     return false;
 }
+// ... the forward 4-stage column pass of the 6 + 10 split (ntt_run): six stages for the towers below a->split6Batch, four for the rest
+static bool static_split6_instance(const NttPass& p, const NttPassArgs* a, void* stream) {
+    FHE_INSTANCE(FHE_PASS_IS(true, false, 4, 1), FHE_LAUNCH_AS("SPLIT6", (ntt_static_kernel<true, false, 4, 1, false, 0, false, true>),
+                                                               pass_tiles(*a), kThreads, true, stream, *a))
+    return false;
+}
 // ntt_row8.h: tiles of 2^T words on 2^(T-9) waves, groups of P polynomials.  Its instances take the arguments in this form: rows and XCD order
 // for that tile size
 static NttPassArgs row8_args(const NttPassArgs& a, uint32_t P) {
@@ -833,9 +850,16 @@ static bool row8_instance(const NttPass& p, const NttPassArgs* a, void* stream) 
 #undef FHE_CASE
     return false;
 }
-// 12-stage row passes, P polynomials per workgroup; hand: the inverse instances that hand the last stage's twiddle products over
-static bool row8_batched_instance(const NttPass& p, uint32_t P, bool hand, const NttPassArgs* a, void* stream) {
+// 12-stage row passes, P polynomials per workgroup; hand: the inverse instances that hand the last stage's twiddle products over; split6: the
+// forward instance behind the six-stage column pass (ten stages in the 12-stage tile)
+static bool row8_batched_instance(const NttPass& p, uint32_t P, bool hand, bool split6, const NttPassArgs* a, void* stream) {
     const bool x1p = row8_x1_regions(P);
+    if (split6) {
+        FHE_INSTANCE(FHE_PASS_IS(false, false, 12, 9) && P == 2 && !x1p && !hand,
+                     FHE_LAUNCH_AS("SPLIT6", (r8::ntt_row8_batched_kernel<false, 3, 9, 2, false, false, true>), a->rows << (a->logN - 12), 512u,
+                                   true, stream, *a))
+        return false;
+    }
 #define FHE_CASE(INV, MODE, PP, X1P)                                                                                                  \
     FHE_INSTANCE(FHE_PASS_IS(false, INV, 12, MODE) && P == PP && x1p == X1P && !hand,                                                 \
                  FHE_LAUNCH_BARRIER_N((r8::ntt_row8_batched_kernel<INV, 3, MODE, PP, X1P>), a->rows << (a->logN - 12), 512u, stream, *a))      \
@@ -904,6 +928,7 @@ static void fill_pass_args(const fhe_ctx* c, const NttPass& p, const uint64_t* x
     a.proMode = o.proSrcLimb ? (o.proRows ? 3 : o.proC ? 2 : 1) : 0, a.proSrcLimb = o.proSrcLimb ? *o.proSrcLimb : 0;
     a.proC = o.proSrcLimb ? o.proC : nullptr;
     a.proRows = o.proSrcLimb ? o.proRows : 0;
+    a.split6Batch = 0;
     for (uint32_t k = 0; k < 4; ++k)
         a.proSrcLimbs[k] = k < a.proRows ? o.proSrcLimb[k] : 0;
 }
@@ -924,7 +949,7 @@ static NttPassArgs split_head(NttPassArgs& a, uint32_t n) {
 // ntt_run decides it once (handP = that kernel's P) and only for a plain transform with canonical output, and both passes are then launched in the
 // same two parts, the P-aligned one with hand-over and the remainder on the kernels every other consumer of the intermediate tower uses.
 static fhe_status launch_pass(const fhe_ctx* c, const NttPass& p, const uint64_t* xin, uint64_t* xout, const LimbSel& sel, uint32_t nLimbs,
-                              uint32_t batch, void* stream, const NttOpts& o = NttOpts(), uint32_t handP = 0) {
+                              uint32_t batch, void* stream, const NttOpts& o = NttOpts(), uint32_t handP = 0, uint32_t splitP = 0) {
     NttPassArgs a;
     fill_pass_args(c, p, xin, xout, sel, nLimbs, batch, o, a);
     // the route of this pass for this batch: a head of whole groups of headP polynomials on a kernel of its own, the rest on another
@@ -946,11 +971,22 @@ static fhe_status launch_pass(const fhe_ctx* c, const NttPass& p, const uint64_t
         const uint32_t P = p.kind == NttPass::Row ? row8_batch_for(p.T) : 1u;
         // a transform with hand-over: both passes must land on the hand-over instances, or the intermediate tower is misread
         if (handP && !(batch >= handP && (p.layoutA() ? static_handover_instance(p, nullptr, nullptr)
-                                                      : P == handP && row8_batched_instance(p, P, true, nullptr, nullptr))))
+                                                      : P == handP && row8_batched_instance(p, P, true, false, nullptr, nullptr))))
             return fail(FHE_ERR_UNSUPPORTED, "ntt: no hand-over kernel for this pass shape");
+        // ... and so must the two passes of a forward transform on the 6 + 10 split
+        if (splitP && !(batch >= splitP && (p.layoutA() ? static_split6_instance(p, nullptr, nullptr)
+                                                        : P == splitP && row8_batched_instance(p, P, false, true, nullptr, nullptr))))
+            return fail(FHE_ERR_UNSUPPORTED, "ntt: no kernel of the 6 + 10 split for this pass shape");
+        if (splitP && p.layoutA()) {
+            // ONE launch for the whole batch: six stages for the part that the batched row kernel takes, four for the remainder
+            a.split6Batch = batch / splitP * splitP;
+            static_split6_instance(p, &a, stream);
+            LAUNCH_CHECK();
+            return FHE_OK;
+        }
         if (handP && p.layoutA())
             headP = handP;  // the column pass of the part of the batch that the batched row kernel takes
-        else if (P > 1 && batch >= P && row8_batched_instance(p, P, handP != 0, nullptr, nullptr))
+        else if (P > 1 && batch >= P && row8_batched_instance(p, P, handP != 0, splitP != 0, nullptr, nullptr))
             headP = P;
         if (p.kind == NttPass::Row && row8_for(p.T) && row8_instance(p, nullptr, nullptr))
             rest = Row8;
@@ -962,7 +998,7 @@ static fhe_status launch_pass(const fhe_ctx* c, const NttPass& p, const uint64_t
         if (p.layoutA())
             static_handover_instance(p, &h, stream);
         else
-            h = row8_args(h, headP), row8_batched_instance(p, headP, handP != 0, &h, stream);
+            h = row8_args(h, headP), row8_batched_instance(p, headP, handP != 0, splitP != 0, &h, stream);
     }
     if (a.batch)
         switch (rest) {
@@ -998,18 +1034,30 @@ static fhe_status ntt_run(fhe_ctx* c, bool inverse, const uint64_t* xin, uint64_
     // them), and the epilogue and prologue instances keep the plain intermediate tower.
     const uint32_t rowP  = inverse ? row8_batch_for(ps.p[0].T) : 1u;
     const uint32_t handP = (o.canonOut && !(o.epi && o.epi->mode) && !o.proSrcLimb && ntt_switches().handover && rowP >= 2 &&
-                            batch >= rowP && row8_batched_instance(ps.p[0], rowP, true, nullptr, nullptr) &&
+                            batch >= rowP && row8_batched_instance(ps.p[0], rowP, true, false, nullptr, nullptr) &&
                             static_handover_instance(ps.p[1], nullptr, nullptr))
                                ? rowP
                                : 0u;
+    // THE decision on the 6 + 10 split of N = 2^16, forward transforms only: the column pass runs six stages (ntt_static.h, SPLIT),
+    // the batched row pass ten in its 12-stage tile (ntt_row8.h, SPLIT).  Taken for exactly the part of a plain transform -- no load prologue, no
+    // fused epilogue; canonical or lazy output -- that the batched row kernel takes at its default P = 2; a forced FHE_NTT_ROW8, FHE_NTT_T1 or
+    // another P keep 4 + 12, and so does every other consumer of the intermediate tower.  (The inverse pair, 10 + 6 behind the hand-over, was
+    // built and measured slower than the hand-over pair: profiles/ntt_split6.md.)
+    const NttSwitches& sw = ntt_switches();
+    const uint32_t fwdP   = inverse ? 1u : row8_batch_for(ps.p[1].T);
+    const uint32_t splitP = (!inverse && sw.split6 && c->logN == 16u && !(o.epi && o.epi->mode) && !o.proSrcLimb && sw.row8 < 0 && !sw.t1 &&
+                             fwdP == 2u && batch >= fwdP && static_split6_instance(ps.p[0], nullptr, nullptr) &&
+                             row8_batched_instance(ps.p[1], fwdP, false, true, nullptr, nullptr))
+                                ? fwdP
+                                : 0u;
     // the first pass reads the source into the destination's rows and leaves them lazy; the second runs in place there and ends the transform
     NttOpts first = o, second;
     first.epi = nullptr, first.canonOut = false;
     second.src = second.dst = o.dst;
     second.epi = o.epi, second.canonOut = o.canonOut;
-    if (fhe_status s = launch_pass(c, ps.p[0], xin, xout, sel, nLimbs, batch, stream, first, handP))
+    if (fhe_status s = launch_pass(c, ps.p[0], xin, xout, sel, nLimbs, batch, stream, first, handP, splitP))
         return s;
-    return launch_pass(c, ps.p[1], xout, xout, sel, nLimbs, batch, stream, second, handP);
+    return launch_pass(c, ps.p[1], xout, xout, sel, nLimbs, batch, stream, second, handP, splitP);
 }
 
 extern "C" fhe_status fhe_ntt_fwd(fhe_ctx* c, uint64_t* x, const uint32_t* li, uint32_t nl, uint32_t b, void* st) {
@@ -5377,7 +5425,7 @@ extern "C" size_t fhe_launch_stats(char* buf, size_t cap, uint64_t* total) {
         k = k.substr(0, k.find('<'));
         k.erase(std::remove(k.begin(), k.end(), '('), k.end());
         byKernel[k] += s->n.load();
-        if (s->label[0])  // a labelled site (the hand-over instances of the NTT passes: <HAND>) once more, on a line of its own (not in the total twice)
+        if (s->label[0])  // a labelled site (the NTT passes' hand-over instances: <HAND>; those of the 6 + 10 split: <SPLIT6>) once more, on a line of its own (not in the total twice)
             byKernel[k + "<" + s->label + ">"] += s->n.load();
         sum += s->n.load();
     }

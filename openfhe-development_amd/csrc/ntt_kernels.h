@@ -104,6 +104,9 @@ struct NttPassArgs {
     // != 0: consecutive towers of the pass's first load / of the epilogue's operand A are this many WORDS apart (signed: towers
     // allocated on their own — the two elements of a ciphertext); overrides inStride / epiAStride (static kernels only)
     int64_t inDelta, epiADelta;
+    // the forward column pass of the 6 + 10 split (ntt_static.h, SPLIT): towers [0, split6Batch) of the batch run its six stages, the rest of
+    // the launch the plain four (what the batched row kernel leaves of a batch); 0 for every other kernel
+    uint32_t split6Batch;
 };
 // SwitchModulus of one residue (mubintvecnat.cpp:109-122): v modulo qs, centred, to the modulus qn
 FHE_HD uint64_t switch_modulus_word(uint64_t v, uint64_t qs, uint64_t halfQs, uint64_t qn) {

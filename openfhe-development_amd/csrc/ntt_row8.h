@@ -323,9 +323,10 @@ FHE_HD void inv_step(uint64_t (&r)[8], const TwPair* tw, uint32_t hi, uint32_t F
 
 // forward lazy-range schedule of the pass (units of q): a radix-8 step of NB stages adds 3 NB; a step whose stages would pass 16
 // sweeps first (its first stage's `a` inputs below 2q).  Steps: w (WB stages), c, k, m (3 each).
-template <int WB, int BIN>
+// TA: the stages the w-step runs (the 6 + 10 split: its last one only)
+template <int WB, int BIN, int TA_ = WB>
 struct FwdSched {
-    static constexpr int TA = WB;
+    static constexpr int TA = TA_;
     static constexpr int stages(int i) { return i == 0 ? TA : 3; }
     static constexpr int before(int i) {
         int b = BIN;
@@ -635,12 +636,31 @@ FHE_HD void inv_step_b(uint64_t (&r)[P][8], const TwPair* tw, uint32_t hi, uint3
     FHE_R8_BANKS_END
 }
 
+// The w-step of the forward 6 + 10 split (SPLIT): the column pass (ntt_static.h, ntt_col6_fwd_body) has run the stages on the field's upper two
+// bits, so the step is its LAST stage alone -- register bit 0, coefficient bit 9 -- and the twiddles of the other two are not fetched.
+template <int P>
+FHE_HD void fwd_step_last_b(uint64_t (&r)[P][8], const TwPair* tw, uint32_t hi, uint32_t F, uint32_t logN, const BflyConst c, uint32_t inBound) {
+    uint32_t bnd[P][8];
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < 8; ++k)
+            bnd[p][k] = inBound;
+    TwPair w0[4];
+    load_tw<true, 0>(w0, tw, hi, F, logN);
+    FHE_R8_BANKS(p)
+        fwd_stage<true, 0, p>(r[p], w0, c, bnd[p]);
+    FHE_R8_BANKS_END
+}
+
 // a.batch / a.rows count GROUPS of P polynomials (the host passes batch / P): the tile order of tile_at, in units of P polynomials
 // HAND (inverse only): the pass's last stage, on coefficient bit T2 - 1, leaves its twiddle product to the column pass that follows
 // (ntt_static.h, HAND): the intermediate tower between the two is NOT the one the other kernels exchange.  (The forward counterpart was built
 // and measured, and did not clear the bar on its own: profiles/r12_handover.md.)
-template <bool INV, int WB, int MODE, int P, bool X1P, bool HAND = false>
+// SPLIT (forward only): the pass behind the six-stage column pass of the 6 + 10 split (ntt_static.h, ntt_col6_fwd_body): ten stages in its
+// 12-stage tile (fwd_step_last_b), and the lazy-range schedule of ten stages (one sweep fewer).  Tile, waves, exchanges and barriers are those of
+// the 12-stage pass.  (The inverse counterpart was built and measured, and removed: profiles/ntt_split6.md.)
+template <bool INV, int WB, int MODE, int P, bool X1P, bool HAND = false, bool SPLIT = false>
 FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
+    static_assert(!SPLIT || (!INV && P == 2), "row8 6 + 10 split: the forward pass at two polynomials per workgroup only");
     static_assert(WB == 3, "row8 batched: 8 waves per tile (12 stages): the banked blocks exist for full radix-8 steps only");
     static_assert(P >= 2 && P <= 4, "row8 batched: register banks 0..3");
     static_assert(!(INV && MODE != 0), "row8: the inverse pass that ends a transform is ntt_static.h's");
@@ -692,7 +712,7 @@ FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
     } while (0)
 
     if constexpr (!INV) {
-        using S = FwdSched<WB, (MODE == 9 ? 2 : MODE)>;
+        using S = FwdSched<WB, (MODE == 9 ? 2 : MODE), (SPLIT ? 1 : WB)>;
         {   // the loads of all P polynomials first: polynomial 0's butterflies wait for its own eight only
             FHE_R8_LANE();
             FHE_R8_BANKS(p)
@@ -702,7 +722,12 @@ FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
                     r[p][k] = FHE_GLD(&s0[threads * (uint32_t)k]);
             FHE_R8_BANKS_END
         }
-        fwd_step_b<true, WB, S::sweep(0), P>(r, tw, at.tr, 6 + WB, logN, c, S::sweep(0) ? 2u : (uint32_t)S::before(0));
+        if constexpr (SPLIT) {
+            static_assert(!S::sweep(0), "row8 6 + 10 split: the one stage of the w-step takes what the column pass leaves (below 2q)");
+            fwd_step_last_b<P>(r, tw, at.tr, 6 + WB, logN, c, (uint32_t)S::before(0));
+        }
+        else
+            fwd_step_b<true, WB, S::sweep(0), P>(r, tw, at.tr, 6 + WB, logN, c, S::sweep(0) ? 2u : (uint32_t)S::before(0));
         {   // X1: 576 w + 64 c + 8 k + m, the only exchange between waves
             FHE_R8_LANE();
             FHE_R8_BANKS(p)
@@ -812,10 +837,10 @@ FHE_DEV void ntt_row8_batched_core(const NttPassArgs& a, uint64_t* lds) {
 // 16 P + 48 VGPRs: P = 2 at 80 (6 waves per SIMD: 3 workgroups, 6 tiles per CU), P = 4 at no more than 128 (4 waves: 2 workgroups,
 // 8 tiles); with a set of X1 regions per polynomial LDS sets the residency (P x 36 KiB: 2 workgroups / 1 workgroup per CU)
 constexpr int batched_waves(int P, bool X1P) { return X1P ? (P == 2 ? 4 : 2) : (P == 2 ? 6 : 4); }
-template <bool INV, int WB, int MODE, int P, bool X1P, bool HAND = false>
+template <bool INV, int WB, int MODE, int P, bool X1P, bool HAND = false, bool SPLIT = false>
 FHE_GLOBAL void FHE_LAUNCH_BOUNDS2(64 << WB, batched_waves(P, X1P)) ntt_row8_batched_kernel(const NttPassArgs a) {
     FHE_SHARED_U64(lds, (X1P ? P : 1) * (1 << WB) * kRegion);
-    ntt_row8_batched_core<INV, WB, MODE, P, X1P, HAND>(a, lds);
+    ntt_row8_batched_core<INV, WB, MODE, P, X1P, HAND, SPLIT>(a, lds);
 }
 
 }  // namespace r8

@@ -854,16 +854,130 @@ FHE_DEV void ntt_static_body(const NttPassArgs& a, uint32_t bid, uint64_t* lds) 
     ntt_static_core<LA, INV, T, MODE, EPI, false, false, PRO, HAND>(a, bid, lds, r);
 }
 
-template <bool LA, bool INV, int T, int MODE, bool EPI = false, int PRO = 0, bool HAND = false>
+// ---- the forward column pass of the 6 + 10 split (N = 2^16): the transform's first SIX stages, 4 + 2 -----------------------------
+// The 12-stage row pass is short of its memory time because of its butterflies, the 4-stage column pass has HBM time to spare
+// (profiles/r06_sweeps.md): this pass takes two of the row pass's stages.  A workgroup's tile is 64 rows x 64 columns (4096 words, as ever);
+// the rows are the coefficient index's top six bits, N / 64 words apart.  Wave w, lane i loads rows 4k + w (k = register 0..15) of column
+// jbase + i -- 512 contiguous bytes per wave instruction -- so the register is the row's top four bits and the first four stages are the
+// 4-stage pass's one step, same twiddles.  ONE exchange through LDS between the four waves (32 KiB, word row * 64 + i: a wave instruction
+// touches 64 consecutive words either way; one barrier, nothing staged): lane (w', i) then holds rows 16 w' + k', register k' = row's low
+// four bits, and the stages on coefficient bits logN - 5 and logN - 6 are butterflies on register bits 1 and 0 whose twiddles
+// Table[2^4 + 4 w' + g], Table[2^5 + 8 w' + g] depend on the wave only (scalar loads).  Lazy ranges: the first step leaves 13q, one sweep
+// brings the `a` inputs of the stage on bit 1 below 2q, the two stages end below 8q, the pass below 2q (run_red16) as the 4-stage pass does.
+// Its partner is ntt_row8.h's batched kernel with SPLIT, which runs the w-step's last stage only; no other kernel reads this
+// intermediate tower.
+FHE_DEV uint32_t static_tile(const NttPassArgs& a, uint32_t bid, uint32_t tilesPerRow) {
+    uint32_t tile = bid;
+    if (a.xcdSwizzle) {
+        const uint32_t xcd = tile & 7u, i = tile >> 3;
+        const uint32_t b = i % a.batch, pairIdx = i / a.batch;
+        const uint32_t pair = pairIdx * 8u + xcd;
+        tile = (b * a.nLimbs + pair / tilesPerRow) * tilesPerRow + pair % tilesPerRow;
+    }
+    return tile;
+}
+FHE_DEV void ntt_col6_fwd_body(const NttPassArgs& a, uint32_t tile, uint64_t* lds) {
+    const uint32_t t    = FHE_TID;
+    const uint32_t logN = a.logN;
+    const uint32_t tilesPerRow = 1u << (logN - (uint32_t)kTileLog);
+    const uint32_t row = tile / tilesPerRow, tr = tile % tilesPerRow;
+    const uint32_t jbase = tr << 6;
+    const uint64_t S     = (uint64_t)1 << (logN - 6u);  // words between two rows of the tile
+    const uint32_t tb = row / a.nLimbs, rit = row % a.nLimbs;
+    const uint64_t inRow  = a.inStride ? ((uint64_t)tb * a.inStride + a.inFirst + rit) : (uint64_t)row;
+    const uint64_t outRow = a.outStride ? ((uint64_t)tb * a.outStride + a.outFirst + rit) : (uint64_t)row;
+    const uint32_t limb = FHE_UNIFORM(a.sel.idx[rit]);
+    const uint64_t q    = FHE_ULOAD64(a.q, limb);
+    const uint64_t twoq = q << 1, nq = 0 - q;
+    TwSrc ts;
+    ts.tw         = a.tw + ((uint64_t)limb << logN);
+    ts.fin        = nullptr;
+    ts.rowLane    = nullptr;
+    ts.shared     = nullptr;
+    ts.sharedLane = 0;
+    const uint64_t redc = FHE_ULOAD64(a.red, limb);
+    const BflyConst c{(uint32_t)nq, (uint32_t)(nq >> 32), q, twoq, 0 - twoq, twoq + q, (uint32_t)redc, (uint32_t)(redc >> 32)};
+    BflyZero z{0, 0};
+#ifdef FHE_PINNED_ASM
+    asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "={v65}"(z.z0), "={v81}"(z.z1));
+#endif
+    const uint64_t* src = (a.inDelta ? a.xin + (int64_t)tb * a.inDelta + ((uint64_t)(a.inFirst + rit) << logN) : a.xin + (inRow << logN)) + jbase;
+    uint64_t* dst       = a.x + (outRow << logN) + jbase;
+    const uint32_t wv = FHE_UNIFORM(t >> 6), l = t & 63u;
+    uint64_t r[16];
+    {
+        const uint64_t* s0 = src + (uint64_t)wv * S + l;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            r[k] = FHE_GLD(&s0[(uint64_t)(4 * k) * S]);
+    }
+    // register = coefficient bits logN-1 .. logN-4: the one step of the 4-stage column pass (canonical input)
+    using P4 = SPlan<true, false, 4>;
+    static_assert(!P4::sweep(0, 1) && P4::outBound(1) == 13, "the first four stages take a canonical input to 13q without a sweep");
+    run_step<true, false, 4, 0, false, false>(r, ts, jbase, logN, c, z, 1u);
+    {
+        uint64_t* Lw = lds + wv * 64u + l;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            FHE_LDS_ST(Lw[256 * k], r[k]);
+        FHE_SSYNC();
+        const uint64_t* Lr = lds + wv * 1024u + l;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            FHE_LDS_LD(r[k], Lr[64 * k]);
+    }
+    // register = coefficient bits logN-3 .. logN-6; butterflies on its bits 1 and 0
+    uint32_t bnd[16];
+    for (int k = 0; k < 16; ++k)
+        bnd[k] = (k & 2) ? (uint32_t)P4::outBound(1) : 2u;
+    TwPair w1[8], w0[8];
+    {
+        const uint64_t* p1 = reinterpret_cast<const uint64_t*>(ts.tw + 16u + 4u * wv);
+        const uint64_t* p0 = reinterpret_cast<const uint64_t*>(ts.tw + 32u + 8u * wv);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(p1), "+s"(p0));  // (the scalar loads are issued here, behind the first step's)
+#endif
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            w1[g] = TwPair{FHE_ULOAD64(p1, 2 * g), FHE_ULOAD64(p1, 2 * g + 1)};
+#pragma unroll
+        for (int g = 0; g < 8; ++g)
+            w0[g] = TwPair{FHE_ULOAD64(p0, 2 * g), FHE_ULOAD64(p0, 2 * g + 1)};
+    }
+    run_red8_a<1>(r, c);
+    run_stage<false, true, 1, 0>(r, w1, c, z, bnd);
+    run_stage<false, true, 0, 0>(r, w0, c, z, bnd);
+    run_red16(r, c);  // the row pass takes values below 2q
+    uint64_t* d0 = dst + (uint64_t)(16u * wv) * S + l;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        FHE_GST(&d0[(uint64_t)k * S], r[k]);
+}
+
+// SPLIT (the plain forward 4-stage column instance only): towers [0, a.split6Batch) of the batch run ntt_col6_fwd_body, the others -- what the
+// batched row kernel leaves of the batch -- this instance's own four stages, in the one launch the column pass of a forward transform is.
+// (The inverse counterpart, 2 + 4 stages behind the hand-over, was built and measured: its column pass lost more than its row pass
+// gained, profiles/ntt_split6.md.)
+template <bool LA, bool INV, int T, int MODE, bool EPI = false, int PRO = 0, bool HAND = false, bool SPLIT = false>
 FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) ntt_static_kernel(const NttPassArgs a) {
     // a single-step pass without staging (the 4-stage column pass) never touches LDS: do not reserve any, so that
     // more workgroups fit on a CU
     using P = SPlan<LA, INV, T>;
     constexpr bool needsLds = P::nst > 1 || P::stageFirst || P::stageLast;
+    static_assert(!SPLIT || (LA && !INV && T == 4 && MODE == 1 && !EPI && !PRO && !HAND && !needsLds),
+                  "the 6 + 10 split exists for the plain forward 4-stage column pass only");
 #ifndef FHE_ABL_LDSPAD  // timing experiment: extra LDS words per workgroup (fewer workgroups per CU)
 #define FHE_ABL_LDSPAD 0
 #endif
-    FHE_SHARED_U64(lds, needsLds ? kLdsPadWords + kSharedTwWords + FHE_ABL_LDSPAD : 1);
+    FHE_SHARED_U64(lds, SPLIT ? kTile : needsLds ? kLdsPadWords + kSharedTwWords + FHE_ABL_LDSPAD : 1);
+    if constexpr (SPLIT) {
+        const uint32_t tilesPerRow = 1u << (a.logN - (uint32_t)kTileLog);
+        const uint32_t tile        = static_tile(a, FHE_BID, tilesPerRow);
+        if (tile / tilesPerRow / a.nLimbs < a.split6Batch) {  // (one answer per workgroup)
+            ntt_col6_fwd_body(a, tile, lds);
+            return;
+        }
+    }
     ntt_static_body<LA, INV, T, MODE, EPI, PRO, HAND>(a, FHE_BID, lds);
 }
 
