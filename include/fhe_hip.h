@@ -279,6 +279,8 @@ fhe_status fhe_fast_expand_crt_basis_p_over_q(fhe_conv* toPl, fhe_conv* toQl, co
 fhe_status fhe_ks_plan_create(fhe_ctx* ctx, uint32_t sizeQ, uint32_t sizeP, uint32_t numPartQ, fhe_ks_plan** out);
 void       fhe_ks_plan_destroy(fhe_ks_plan* plan);
 uint32_t   fhe_ks_plan_alpha(const fhe_ks_plan* plan);
+/* how many levels sizeQl the plan has built its tables for so far (a level is built on first use, or all at once by fhe_bfv_hybrid_create) */
+uint32_t   fhe_ks_plan_levels_built(fhe_ks_plan* plan);
 fhe_status fhe_ks_key_alloc(fhe_ks_plan* plan, fhe_ks_key** out);
 fhe_status fhe_ks_key_upload(fhe_ks_plan* plan, const uint64_t* keyB, const uint64_t* keyA, fhe_ks_key** out);
 /* adopt key vectors that already live in device memory (not owned: destroy leaves them alone). This is the
@@ -657,8 +659,9 @@ fhe_status fhe_bfv_eval_mult_relin_behz(fhe_behz* plan, fhe_ks_plan* ks, const f
  * 64-bit modular arithmetic.  numQ + numR <= 256.  fhe_hps_table reads a derived table back (ids and layouts: see the definition
  * in fhe_hip.cpp; doubles as bit patterns); it returns the table's length in 64-bit words, 0 if the plan has no such table.
  * fhe_bfv_eval_mult_hps: inputs [batch][numQ][N] EVALUATION -> outputs [batch][numQ][N], COEFFICIENT as the reference leaves
- * them, or EVALUATION when outEval != 0 (then fhe_keyswitch_hybrid_acc relinearises with a HYBRID key, fhe_keyswitch_bv with accumulate != 0
- * with a BV key; fhe_bfv_eval_mult_relin_hps_bv is the whole BV sequence).  sizeQl = l + 1 is the number of Q limbs the
+ * them, or EVALUATION when outEval != 0 (then fhe_keyswitch_hybrid_acc relinearises with a HYBRID key at numQ limbs, fhe_keyswitch_bv with
+ * accumulate != 0 with a BV key; fhe_bfv_eval_mult_relin_hps_bv is the whole BV sequence, fhe_bfv_eval_mult_relin_hps_hybrid the whole HYBRID
+ * one at any level the reference drops to).  sizeQl = l + 1 is the number of Q limbs the
  * product is computed over: numQ for HPS and HPSPOVERQ; for HPSPOVERQLEVELED the caller's numQ - levelsDropped (FindLevelsToDrop is
  * host-side noise estimation and stays in pke).  A wrong sizeQl or too small a workspace is an error and enqueues nothing.  The call
  * builds nothing lazily, allocates nothing and does not synchronise: it can be captured into a graph.
@@ -789,6 +792,62 @@ size_t     fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes(const fhe_hps*
 fhe_status fhe_bfv_eval_mult_relin_hps_bv_leveled(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* a0, const uint64_t* a1,
                                                   const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1, uint32_t sizeQlMult,
                                                   uint32_t sizeQlRelin, uint32_t batch, void* ws, size_t wsBytes, void* stream);
+
+/* ---- BFV, HPS family, on HYBRID keys: rotations and relinearisation at dropped levels -----------------------------
+ * The BFV block above with KeySwitchHYBRID (src/pke/lib/keyswitch/keyswitch-hybrid.cpp) in the middle.  Under HPSPOVERQLEVELED the reference
+ * runs every relinearisation and rotation at sizeQl = l + 1 <= numQ limbs whatever the key-switch technique (bfvrns-leveledshe.cpp:767-938):
+ * ScaleAndRound Q -> Q_l, the key switch at sizeQl limbs, ExpandCRTBasisQlHat back to Q; fhe_keyswitch_hybrid_acc on the output of
+ * fhe_bfv_eval_mult_hps(outEval = 1) is that sequence at sizeQl == numQ only.
+ * The plan pairs an fhe_hps plan with an fhe_ks_plan of the same context: the HPS plan's Q must be the context's leading limbs (as for the BV
+ * block) and the key-switch plan's sizeQ == numQ, so the context holds Q, then P, then whatever R needs beyond them.  P and R need not be
+ * disjoint (the reference draws both downwards from the last q_i, bfvrns-cryptoparameters.cpp:75, 135-139, rns-cryptoparameters.cpp:128-176):
+ * a modulus common to both is ONE context limb that the P range and the R index list both name.  Both parents must outlive the plan.
+ * fhe_bfv_hybrid_create builds every level of the key-switch plan the technique can use (1 ... numQ for HPSPOVERQLEVELED, numQ otherwise) and,
+ * per level below numQ, the device table C'_i = [P^-1]_{q_i} * QlHatModq(l)[i] mod q_i: ApproxModDown's last product run with C' returns the
+ * ModDown result already multiplied by QlHatModq(l), i.e. ExpandCRTBasisQlHat's low rows, at no cost.  After creation every call builds
+ * nothing, allocates nothing and does not synchronise: it can be captured into a graph.
+ * All towers are [batch][numQ][N].  sizeQl: 1 ... numQ for HPSPOVERQLEVELED, numQ only for HPS and HPSPOVERQ (the reference's condition,
+ * :795, :859, :903, is false there).  At sizeQl == numQ scaling and expansion are the identity and are skipped, as in the BV block: the results
+ * equal fhe_eval_fast_rotation / fhe_eval_automorphism / fhe_keyswitch_hybrid_acc word for word.  FindLevelsToDrop stays with the caller.
+ * An error enqueues nothing and leaves the outputs untouched: a null argument, an even k ("Automorphism index not odd"), sizeQl outside the
+ * technique's range, too small a workspace, a key of another fhe_ks_plan, rotation outputs that alias c0, c1 or ws.
+ * The tail -- zero-extension from sizeQl to numQ rows, the addition(s) and the automorphism of both elements -- is ONE kernel
+ * (bfv_hybrid_tail_kernel): a call below the top level is the launches of the key switch at sizeQl plus that one.
+ *   fhe_bfv_hybrid_workspace_bytes            covers every call below but the last two (0: sizeQl outside the technique's range)
+ *   fhe_bfv_fast_rotation_precompute_hybrid   = LeveledSHEBFVRNS::EvalFastRotationPrecompute (:782-813): c1 EVALUATION -> COEFFICIENT over numQ rows
+ *                                -> ScaleAndRound Q -> Q_l into the key switch's coefficient buffer -> its EVALUATION copy (one transform of
+ *                                sizeQl rows) and EvalKeySwitchPrecomputeCore (keyswitch-hybrid.cpp:314-379) from the coefficient buffer.  The
+ *                                digits stay in ws for any number of fast rotations (hoisting); the complementary rows are kept lazy (< 16 q).
+ *   fhe_bfv_eval_fast_rotation_hybrid         = LeveledSHEBFVRNS::EvalFastRotation (:815-882): EvalFastKeySwitchCore (keyswitch-hybrid.cpp:381-435) on
+ *                                those digits, both results expanded, += c0, both through AutomorphismTransform(k).  c1 is the tower the
+ *                                precompute saw; it is read only at sizeQl == numQ (the digits' own limbs are c1 itself there; below, the
+ *                                scaled EVALUATION copy in ws is read).  The ModDown scratch in ws is overwritten by every call.
+ *   fhe_bfv_eval_automorphism_hybrid          = LeveledSHEBFVRNS::EvalAutomorphism (:767-780) = the two calls above
+ *   fhe_bfv_relinearize_hybrid                = LeveledSHEBFVRNS::RelinearizeCore on three elements (:888-938): c_e = d_e + Expand(ks_e(d2)),
+ *                                EVALUATION.  inEval == 0: d0, d1, d2 are COEFFICIENT as EvalMultNoRelin leaves them (d2 goes straight into
+ *                                ScaleAndRound, d0 / d1 are transformed once into c0 / c1); otherwise EVALUATION.  c_e may be d_e (in place).
+ *   fhe_bfv_eval_mult_relin_hps_hybrid        = LeveledSHEBFVRNS::EvalMult(ct, ct, key) (:735-741): fhe_bfv_eval_mult_hps(outEval = 0) at sizeQlMult,
+ *                                then fhe_bfv_relinearize_hybrid(inEval = 0) at sizeQlRelin.  Its own _workspace_bytes. */
+typedef struct fhe_bfv_hybrid fhe_bfv_hybrid;
+fhe_status fhe_bfv_hybrid_create(fhe_hps* hps, fhe_ks_plan* ks, fhe_bfv_hybrid** out);
+void       fhe_bfv_hybrid_destroy(fhe_bfv_hybrid* plan);
+size_t     fhe_bfv_hybrid_workspace_bytes(const fhe_bfv_hybrid* plan, uint32_t sizeQl, uint32_t batch);
+fhe_status fhe_bfv_fast_rotation_precompute_hybrid(fhe_bfv_hybrid* plan, const uint64_t* c1, uint32_t sizeQl, uint32_t batch, void* ws,
+                                                   size_t wsBytes, void* stream);
+fhe_status fhe_bfv_eval_fast_rotation_hybrid(fhe_bfv_hybrid* plan, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k,
+                                             uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes,
+                                             void* stream);
+fhe_status fhe_bfv_eval_automorphism_hybrid(fhe_bfv_hybrid* plan, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1, uint32_t k,
+                                            uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1, void* ws, size_t wsBytes,
+                                            void* stream);
+fhe_status fhe_bfv_relinearize_hybrid(fhe_bfv_hybrid* plan, const fhe_ks_key* key, const uint64_t* d0, const uint64_t* d1, const uint64_t* d2,
+                                      int inEval, uint32_t sizeQl, uint32_t batch, uint64_t* c0, uint64_t* c1, void* ws, size_t wsBytes,
+                                      void* stream);
+size_t     fhe_bfv_eval_mult_relin_hps_hybrid_workspace_bytes(const fhe_bfv_hybrid* plan, uint32_t sizeQlMult, uint32_t sizeQlRelin,
+                                                              uint32_t batch);
+fhe_status fhe_bfv_eval_mult_relin_hps_hybrid(fhe_bfv_hybrid* plan, const fhe_ks_key* key, const uint64_t* a0, const uint64_t* a1,
+                                              const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1, uint32_t sizeQlMult,
+                                              uint32_t sizeQlRelin, uint32_t batch, void* ws, size_t wsBytes, void* stream);
 
 /* ---- parity helper: whole-tower checksums ----------------------------------------------------------------
  * out[row] = { sum_i w_i, sum_i (2i + 1) * w_i } mod 2^64 over the row's N words, for every limb-row of x[rows][N] (rows = batch *

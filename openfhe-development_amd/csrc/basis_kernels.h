@@ -691,6 +691,77 @@ FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads)
     }
 }
 
+// ---- BFV on HYBRID keys: the tail of a rotation or a relinearisation below the top level ----------------------------
+// LeveledSHEBFVRNS::EvalFastRotation / RelinearizeCore (bfvrns-leveledshe.cpp:864-877, 918-935) after the two ApproxModDowns: both
+// results from the sizeQl limbs of Q_l to the outRows limbs of Q (ExpandCRTBasisQlHat), += the ciphertext's own elements,
+// AutomorphismTransform(k) of both.  The expansion's product by QlHatModq(l)[i] is already in t_e: the ModDown ran with the constant
+// [P^-1]_{q_i} * QlHatModq(l)[i] (fhe_bfv_hybrid_create), so what is left is
+//   v_e = (i < sizeQl ? t_e[b][i][r] : 0) + add_e[b][i][r]   (mod q_i),      out_e[b][i][dst(r)] = v_e
+// one launch for both elements, all outRows rows and the whole batch.  As in the BV output stage above, the permuted side is the
+// STORE (dst = the map of kInv = k^-1 mod 2N, a scatter): the up to four input streams are read contiguously, 16 bytes per lane, and
+// only the two output streams are permuted -- a gather would permute every input stream instead, and a lane waits for its loads, not
+// for its stores.  The tile property stated there holds here too: the 4096 words of a workgroup's tile land in one 4096-word tile of
+// the same output row, which no other workgroup touches, so the 8-byte stores of a tile merge in L2.  k = 1 (relinearisation) is the
+// identity: 16-byte stores, and out_e may be add_e (each lane reads the words it writes).  Rows i >= sizeQl are a permuted copy of
+// the addend (zeros where there is none).
+struct BfvHybridTailArgs {
+    const uint64_t* t0;    // [batch][sizeQl][N] EVAL, canonical: ModDown of the first accumulator, times QlHatModq(l)
+    const uint64_t* t1;
+    const uint64_t* add0;  // [batch][outRows][N] (c0, or d0)
+    const uint64_t* add1;  // [batch][outRows][N] (d1) or null
+    uint64_t* out0;        // [batch][outRows][N]
+    uint64_t* out1;
+    const LimbConst* lc;   // [ctxLimbs]; row i is context limb i
+    uint32_t logN, batch, sizeQl, outRows, kInv;
+};
+template <int CPL>
+FHE_GLOBAL void FHE_LAUNCH_BOUNDS(kThreads) bfv_hybrid_tail_kernel(const BfvHybridTailArgs g) {
+    const uint32_t t           = FHE_TID;
+    const uint32_t N           = 1u << g.logN;
+    const uint32_t tilesPerRow = N >> kTileLog ? (N >> kTileLog) : 1u;
+    const uint32_t tr          = FHE_BID % tilesPerRow;
+    const uint32_t row         = FHE_BID / tilesPerRow;
+    const uint32_t i = row % g.outRows, b = row / g.outRows;
+    if (b >= g.batch)
+        return;
+    const uint64_t q    = g.lc[i].q;
+    const bool low      = i < g.sizeQl;
+    const uint32_t rEnd = ((tr + 1u) << kTileLog) < N ? ((tr + 1u) << kTileLog) : N;
+    const uint64_t toff = ((uint64_t)b * g.sizeQl + i) << g.logN, ooff = ((uint64_t)b * g.outRows + i) << g.logN;
+    for (uint32_t r = (tr << kTileLog) + CPL * t; r < rEnd; r += CPL * kThreads) {
+        uint64_t v0[CPL], v1[CPL], p[CPL];
+#pragma unroll
+        for (int u = 0; u < CPL; ++u)
+            v0[u] = v1[u] = 0;
+        if (low) {
+            ld_cpl<CPL>(g.t0 + toff + r, v0);
+            ld_cpl<CPL>(g.t1 + toff + r, v1);
+        }
+        ld_cpl<CPL>(g.add0 + ooff + r, p);
+#pragma unroll
+        for (int u = 0; u < CPL; ++u)
+            v0[u] = add_mod(v0[u], p[u], q);
+        if (g.add1) {
+            ld_cpl<CPL>(g.add1 + ooff + r, p);
+#pragma unroll
+            for (int u = 0; u < CPL; ++u)
+                v1[u] = add_mod(v1[u], p[u], q);
+        }
+        if (g.kInv == 1u) {
+            st_cpl<CPL>(g.out0 + ooff + r, v0);
+            st_cpl<CPL>(g.out1 + ooff + r, v1);
+        }
+        else {
+#pragma unroll
+            for (int u = 0; u < CPL; ++u) {
+                const uint32_t dst = automorph_source(bitrev32(r + u, g.logN), g.kInv, g.logN);
+                g.out0[ooff + dst] = v0[u];
+                g.out1[ooff + dst] = v1[u];
+            }
+        }
+    }
+}
+
 // ---- baby-step/giant-step inner sums (double hoisting) --------------------------------------------
 // inner_i[e][b][l][r] = sum_j rot_j[e][b][l][r] * diag_{i,j}[l][r]  over the extended basis Q_l u P, for ALL outer steps i
 // in one pass: the EvalMultExt / EvalAddExtInPlace chains of FHECKKSRNS::EvalLinearTransform (ckksrns-fhe.cpp:1855-1859,

@@ -2071,6 +2071,15 @@ extern "C" void fhe_ks_plan_destroy(fhe_ks_plan* p) {
     delete p;
 }
 extern "C" uint32_t fhe_ks_plan_alpha(const fhe_ks_plan* p) { return p ? p->alpha : 0; }
+extern "C" uint32_t fhe_ks_plan_levels_built(fhe_ks_plan* p) {
+    if (!p)
+        return 0;
+    std::lock_guard<std::mutex> lock(p->cacheMutex);
+    uint32_t n = 0;
+    for (auto* lv : p->levels)
+        n += lv != nullptr;
+    return n;
+}
 
 static fhe_status ks_level(fhe_ks_plan* p, uint32_t sizeQl, fhe_ks_plan::Level** out) {
     ARG_CHECK(sizeQl >= 1 && sizeQl <= p->sizeQ, "fhe_keyswitch: sizeQl out of range");
@@ -2244,14 +2253,16 @@ static fhe_status mod_down_core(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const ui
     fused.epi = epi;
     return ntt_run(c, false, md, md, nullptr, sizeQl, nTow, st, fused);
 }
+// C: the per-limb constant of (:1002) as device Shoup pairs [sizeQl]; null: the level's own [P^-1]_{q_i}
 static fhe_status mod_down_tail(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const uint64_t* x, const uint64_t* md, uint32_t nTow,
-                                uint64_t* out, bool accumulate, void* st) {
+                                uint64_t* out, bool accumulate, void* st, const TwPair* C = nullptr) {
     const uint32_t sizeQl = lv->sizeQl, sizeQlP = sizeQl + p->sizeP;
+    if (!C)
+        C = lv->d_PInv;
     // (:1002); x towers are sizeQlP rows apart
     if (accumulate)
-        return elem_run<OP_SUB_MUL_CONST_ACC>(p->ctx, out, x, md, lv->d_PInv, nullptr, sizeQl, nTow, st, "fhe_approx_mod_down",
-                                              sizeQlP, 0);
-    return elem_run<OP_SUB_MUL_CONST>(p->ctx, out, x, md, lv->d_PInv, nullptr, sizeQl, nTow, st, "fhe_approx_mod_down", sizeQlP, 0);
+        return elem_run<OP_SUB_MUL_CONST_ACC>(p->ctx, out, x, md, C, nullptr, sizeQl, nTow, st, "fhe_approx_mod_down", sizeQlP, 0);
+    return elem_run<OP_SUB_MUL_CONST>(p->ctx, out, x, md, C, nullptr, sizeQl, nTow, st, "fhe_approx_mod_down", sizeQlP, 0);
 }
 static fhe_status mod_down_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const uint64_t* x, uint32_t nTow, uint64_t* out,
                                uint64_t* pcoef, uint64_t* md, void* st) {
@@ -2262,18 +2273,18 @@ static fhe_status mod_down_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const uin
 
 // EvalKeySwitchPrecomputeCore (keyswitch-hybrid.cpp:314-379): digit decomposition + ModUp of every digit into the
 // workspace's digit buffers (the digit's own limbs are NOT copied: the inner product reads them from `cin`)
-static fhe_status ks_precompute_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const uint64_t* cin, uint32_t batch,
-                                    uint64_t* ws, const KsLayout& w, void* st) {
+// ... in its two parts: the digits cut from a COEFFICIENT tower `coef` [batch][sizeQl][N] (the workspace's own copy, or a caller's tower:
+// it is only read), and in front of it the inverse transform that fills the workspace's copy
+static fhe_status ks_precompute_from_coef(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const uint64_t* coef, uint32_t batch, uint64_t* ws,
+                                          const KsLayout& w, void* st) {
     fhe_ctx* c            = p->ctx;
     const uint32_t sizeQl = lv->sizeQl;
-    if (fhe_status s = fhe_ntt_inv_oop(c, cin, ws + w.coef, nullptr, sizeQl, batch, st))
-        return s;
     NttOpts lazy;
     lazy.canonOut = false;
     for (uint32_t j = 0; j < lv->numParts; ++j) {
         const uint32_t nc = (uint32_t)lv->cidx[j].size();
         uint64_t* dj      = ws + w.dig[j];
-        if (fhe_status s = fhe_approx_switch_basis(lv->up[j], ws + w.coef, sizeQl, p->alpha * j, dj, nc, 0, batch, st))
+        if (fhe_status s = fhe_approx_switch_basis(lv->up[j], coef, sizeQl, p->alpha * j, dj, nc, 0, batch, st))
             return s;
         // the digits are only read by the inner product, whose 128-bit accumulation takes any 64-bit operand: the
         // transform's outputs stay in the lazy range (< 16q), the 4-level canonicalisation is skipped
@@ -2281,6 +2292,12 @@ static fhe_status ks_precompute_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, cons
             return s;
     }
     return FHE_OK;
+}
+static fhe_status ks_precompute_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const uint64_t* cin, uint32_t batch,
+                                    uint64_t* ws, const KsLayout& w, void* st) {
+    if (fhe_status s = fhe_ntt_inv_oop(p->ctx, cin, ws + w.coef, nullptr, lv->sizeQl, batch, st))
+        return s;
+    return ks_precompute_from_coef(p, lv, ws + w.coef, batch, ws, w, st);
 }
 // EvalFastKeySwitchCore (keyswitch-hybrid.cpp:381-435) on digits already in the workspace.
 // accumulate: out0/out1 += result (EvalMult's `cv[0] += ab[0]; cv[1] += ab[1]`, base-leveledshe.cpp:210-211)
@@ -2455,10 +2472,12 @@ static fhe_status ks_down_conv(fhe_ks_plan* p, fhe_ks_plan::Level* lv, uint64_t 
 // t: 0 = the CKKS / BFV form; >= 2 = the BGV form, the ModDown with the level's downT conversion (ks_down_conv) under the same fused epilogue
 static fhe_status ks_fast_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const fhe_ks_key* key, const uint64_t* cin,
                               uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* ws, const KsLayout& w, void* st,
-                              bool accumulate, uint64_t t = 0) {
+                              bool accumulate, uint64_t t = 0, const TwPair* C = nullptr) {
     fhe_ctx* c            = p->ctx;
     const uint32_t sizeQl = lv->sizeQl;
     fhe_conv* down        = nullptr;  // (null: the plan's own conversion, mod_down_core)
+    if (!C)
+        C = lv->d_PInv;  // (BFV below the top level: [P^-1]_{q_i} * QlHatModq(l)[i], fhe_bfv_hybrid_create)
     if (t)
         if (fhe_status s = ks_down_conv(p, lv, t, "key switch", &down))
             return s;
@@ -2471,14 +2490,14 @@ static fhe_status ks_fast_run(fhe_ks_plan* p, fhe_ks_plan::Level* lv, const fhe_
         // tower is never written to HBM in EVALUATION form and the two tail kernels disappear
         NttEpilogue epi;
         epi.mode = accumulate ? 2u : 1u, epi.split = batch, epi.aStride = sizeQl + p->sizeP, epi.aFirst = 0;
-        epi.A = ws + w.e0, epi.C = lv->d_PInv, epi.out0 = out0, epi.out1 = out1;
+        epi.A = ws + w.e0, epi.C = C, epi.out0 = out0, epi.out1 = out1;
         return mod_down_core(p, lv, ws + w.e0, 2 * batch, ws + w.pcoef, ws + w.md, st, down, &epi);
     }
     if (fhe_status s = mod_down_core(p, lv, ws + w.e0, 2 * batch, ws + w.pcoef, ws + w.md, st, down))
         return s;
-    if (fhe_status s = mod_down_tail(p, lv, ws + w.e0, ws + w.md, batch, out0, accumulate, st))
+    if (fhe_status s = mod_down_tail(p, lv, ws + w.e0, ws + w.md, batch, out0, accumulate, st, C))
         return s;
-    return mod_down_tail(p, lv, ws + w.e1, ws + w.md + ((size_t)batch * sizeQl << c->logN), batch, out1, accumulate, st);
+    return mod_down_tail(p, lv, ws + w.e1, ws + w.md + ((size_t)batch * sizeQl << c->logN), batch, out1, accumulate, st, C);
 }
 static fhe_status keyswitch_run(fhe_ks_plan* p, const fhe_ks_key* key, const uint64_t* cin, uint32_t sizeQl,
                                 uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* ws, const KsLayout& w,
@@ -5402,6 +5421,251 @@ extern "C" fhe_status fhe_bfv_eval_mult_relin_hps_bv_leveled(fhe_hps* h, const f
     if (fhe_status s = fhe_bfv_eval_mult_hps(h, a0, a1, b0, b1, c0, c1, d2, sizeQlMult, 0, batch, rest, wsBytes - d2Bytes, st))
         return s;
     return fhe_bfv_relinearize_bv(h, k, c0, c1, d2, 0, sizeQlRelin, batch, c0, c1, rest, wsBytes - d2Bytes, st);
+}
+
+// ---- BFV, HPS family, on HYBRID keys ------------------------------------------------------------------------------------------------------
+// The members of "rotations and leveled relinearisation on a BV key" above with KeySwitchHYBRID in the middle (bfvrns-leveledshe.cpp:767-938,
+// keyswitch-hybrid.cpp:308-400).  Below the top level the element goes Q -> Q_l (ScaleAndRound) straight into the key switch's coefficient
+// buffer, the key switch runs at sizeQl limbs with the ModDown constant C'_i = [P^-1]_{q_i} * QlHatModq(l)[i] mod q_i -- ((A - sw) * P^-1 mod q)
+// * QlHat mod q and (A - sw) * C' mod q are the same canonical residue, so ExpandCRTBasisQlHat's product costs nothing -- and
+// bfv_hybrid_tail_kernel zero-extends to numQ rows, adds the ciphertext's own elements and applies the automorphism, one launch.
+// workspace (words): the key switch's layout at sizeQl (ks_layout: coef = the scaled COEFFICIENT tower, d2 = its EVALUATION copy, whose own
+// limbs the inner product reads, k0 / k1 = the two ModDown results) | below numQ: coefficient copy over Q [batch][numQ][N]
+struct fhe_bfv_hybrid {
+    fhe_hps* h;
+    fhe_ks_plan* ks;
+    std::vector<fhe_ks_plan::Level*> lv;  // index sizeQl; null: a level the technique cannot use
+    std::vector<TwPair*> d_C;             // index sizeQl: C' as device Shoup pairs [sizeQl]; null at numQ (QlHatModq is all ones: the level's own P^-1)
+    std::vector<void*> owned;
+};
+extern "C" void fhe_bfv_hybrid_destroy(fhe_bfv_hybrid* bh) {
+    if (!bh)
+        return;
+    for (void* p : bh->owned)
+        rt::dfree(p);
+    delete bh;
+}
+extern "C" fhe_status fhe_bfv_hybrid_create(fhe_hps* h, fhe_ks_plan* ks, fhe_bfv_hybrid** out) {
+    ARG_CHECK(h && ks && out, "fhe_bfv_hybrid_create: null argument");
+    ARG_CHECK(h->ctx == ks->ctx, "fhe_bfv_hybrid_create: the two plans were built for different contexts");
+    for (uint32_t i = 0; i < h->numQ; ++i)
+        ARG_CHECK(h->qIdx[i] == i, "fhe_bfv_hybrid_create: Q must be the context's leading limbs");
+    ARG_CHECK(ks->sizeQ == h->numQ, "fhe_bfv_hybrid_create: the key-switch plan's Q must be the HPS plan's Q");
+    fhe_ctx* c = h->ctx;
+    RT_CHECK(rt::set_device(c->device));
+    fhe_bfv_hybrid* bh = new fhe_bfv_hybrid;
+    bh->h = h, bh->ks = ks;
+    bh->lv.assign(h->numQ + 1, nullptr), bh->d_C.assign(h->numQ + 1, nullptr);
+    std::vector<uint64_t> pm(ks->sizeP);
+    for (uint32_t j = 0; j < ks->sizeP; ++j)
+        pm[j] = c->q[ks->sizeQ + j];
+    for (uint32_t sizeQl = h->technique == 3 ? 1u : h->numQ; sizeQl <= h->numQ; ++sizeQl) {
+        fhe_status s = ks_level(ks, sizeQl, &bh->lv[sizeQl]);  // (every level now: no call below builds one)
+        if (!s && sizeQl < h->numQ) {
+            const std::vector<uint64_t>& hat = hps_level(h, sizeQl)->QlHatModq;
+            std::vector<TwPair> cp(sizeQl);
+            for (uint32_t i = 0; i < sizeQl; ++i) {
+                const uint64_t qi = c->q[i];
+                const uint64_t v  = host::mulmod(host::invmod(host::prod_mod(pm, -1, qi), qi), hat[i] % qi, qi);
+                cp[i]             = TwPair{v, host::shoup(v, qi)};
+            }
+            s = dev_copy(&bh->owned, cp.data(), cp.size(), &bh->d_C[sizeQl]);
+        }
+        if (s) {
+            fhe_bfv_hybrid_destroy(bh);
+            return s;
+        }
+    }
+    *out = bh;
+    return FHE_OK;
+}
+static bool bfv_hybrid_level_ok(const fhe_bfv_hybrid* bh, uint32_t sizeQl) {
+    return bh && sizeQl >= 1 && sizeQl <= bh->h->numQ && bh->lv[sizeQl];
+}
+static size_t bfv_hybrid_ws_words(const fhe_bfv_hybrid* bh, uint32_t sizeQl, uint32_t batch) {
+    if (!bfv_hybrid_level_ok(bh, sizeQl) || batch < 1)
+        return 0;
+    const size_t ks = ks_layout(bh->ks, sizeQl, batch).total;
+    return ks + (sizeQl < bh->h->numQ ? ((size_t)batch * bh->h->numQ) << bh->h->ctx->logN : 0);
+}
+extern "C" size_t fhe_bfv_hybrid_workspace_bytes(const fhe_bfv_hybrid* bh, uint32_t sizeQl, uint32_t batch) {
+    return bfv_hybrid_ws_words(bh, sizeQl, batch) * 8;
+}
+// everything a call below checks before it enqueues; key may be null (the precompute has none)
+static fhe_status bfv_hybrid_check(const fhe_bfv_hybrid* bh, const fhe_ks_key* key, bool needKey, uint32_t sizeQl, uint32_t batch,
+                                   const void* ws, size_t wsBytes, const char* who) {
+    ARG_CHECK(bh && ws && batch >= 1 && (key || !needKey), std::string(who) + ": null argument");
+    ARG_CHECK(bfv_hybrid_level_ok(bh, sizeQl), std::string(who) + ": sizeQl must be numQ (1 ... numQ for HPSPOVERQLEVELED)");
+    ARG_CHECK(!key || key->plan == bh->ks, std::string(who) + ": the key belongs to another key-switch plan");
+    ARG_CHECK(wsBytes >= fhe_bfv_hybrid_workspace_bytes(bh, sizeQl, batch), std::string(who) + ": workspace too small");
+    const fhe_ctx* c           = bh->h->ctx;
+    const uint32_t tilesPerRow = c->N >= (uint32_t)kTile ? (c->N >> kTileLog) : 1u;
+    ARG_CHECK((uint64_t)tilesPerRow * bh->h->numQ * batch < ((uint64_t)1 << 31), std::string(who) + ": batch too large for one launch");
+    return FHE_OK;
+}
+// [lo, lo + n) and [p, p + m) share a byte
+static bool bfv_hybrid_overlap(const void* lo, size_t n, const void* p, size_t m) {
+    const uintptr_t a = (uintptr_t)lo, b = (uintptr_t)p;
+    return a < b + m && b < a + n;
+}
+// x [batch][numQ][N] in evalFormat -> the digits at sizeQl limbs, the scaled COEFFICIENT tower and its EVALUATION copy in ws.  (The
+// EVALUATION tower whose own limbs the inner product reads is then ws's d2 -- or x itself at the top level when x is EVALUATION.)
+static fhe_status bfv_hybrid_digits(fhe_bfv_hybrid* bh, const uint64_t* x, int evalFormat, uint32_t sizeQl, uint32_t batch, uint64_t* ws,
+                                    const KsLayout& w, void* st) {
+    fhe_hps* h             = bh->h;
+    fhe_ctx* c             = h->ctx;
+    fhe_ks_plan::Level* lv = bh->lv[sizeQl];
+    if (sizeQl == h->numQ) {
+        if (evalFormat)  // the launches of fhe_ks_precompute
+            return ks_precompute_run(bh->ks, lv, x, batch, ws, w, st);
+        if (fhe_status s = fhe_ntt_fwd_oop(c, x, ws + w.d2, nullptr, sizeQl, batch, st))
+            return s;
+        return ks_precompute_from_coef(bh->ks, lv, x, batch, ws, w, st);
+    }
+    if (evalFormat) {
+        uint64_t* coefQ = ws + w.total;
+        if (fhe_status s = fhe_ntt_inv_oop(c, x, coefQ, nullptr, h->numQ, batch, st))
+            return s;
+        x = coefQ;
+    }
+    if (fhe_status s = fhe_scale_and_round(hps_level(h, sizeQl)->drop, x, 1, ws + w.coef, batch, st))
+        return s;
+    if (fhe_status s = fhe_ntt_fwd_oop(c, ws + w.coef, ws + w.d2, nullptr, sizeQl, batch, st))
+        return s;
+    return ks_precompute_from_coef(bh->ks, lv, ws + w.coef, batch, ws, w, st);
+}
+// EvalFastKeySwitchCore at sizeQl on the digits in ws (results in ws: k0, k1), then the tail kernel
+static fhe_status bfv_hybrid_fast(fhe_bfv_hybrid* bh, const fhe_ks_key* key, const uint64_t* cin, const uint64_t* add0, const uint64_t* add1,
+                                  uint32_t kAuto, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1, uint64_t* ws,
+                                  const KsLayout& w, void* st, const char* who) {
+    fhe_hps* h = bh->h;
+    fhe_ctx* c = h->ctx;
+    const uint32_t twoNmask = (2u << c->logN) - 1u;
+    uint32_t kInv = kAuto;  // Newton: the inverse of an odd k modulo 2^32, then modulo 2N
+    for (int it = 0; it < 5; ++it)
+        kInv *= 2u - kAuto * kInv;
+    kInv &= twoNmask;
+    const uint32_t tilesPerRow = c->N >= (uint32_t)kTile ? (c->N >> kTileLog) : 1u;
+    const uint64_t grid        = (uint64_t)tilesPerRow * h->numQ * batch;  // (< 2^31: bfv_hybrid_check)
+    RT_CHECK(rt::set_device(c->device));
+    if (fhe_status s = ks_fast_run(bh->ks, bh->lv[sizeQl], key, cin, batch, ws + w.k0, ws + w.k1, ws, w, st, false, 0, bh->d_C[sizeQl]))
+        return s;
+    BfvHybridTailArgs g;
+    g.t0 = ws + w.k0, g.t1 = ws + w.k1, g.add0 = add0, g.add1 = add1, g.out0 = out0, g.out1 = out1, g.lc = c->d_lc;
+    g.logN = c->logN, g.batch = batch, g.sizeQl = sizeQl, g.outRows = h->numQ, g.kInv = kInv;
+    // two adjacent coefficients per lane need 16-byte aligned towers (any device allocation is) and N >= 2
+    const uintptr_t bits = (uintptr_t)g.t0 | (uintptr_t)g.t1 | (uintptr_t)add0 | (uintptr_t)add1 | (uintptr_t)out0 | (uintptr_t)out1;
+    if ((bits & 15u) == 0 && c->N >= 2)
+        FHE_LAUNCH((bfv_hybrid_tail_kernel<2>), grid, st, g);
+    else
+        FHE_LAUNCH((bfv_hybrid_tail_kernel<1>), grid, st, g);
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+// the checks the two rotation entries share: k odd, outputs apart from c0, c1 and ws
+static fhe_status bfv_hybrid_rot_check(const fhe_bfv_hybrid* bh, const uint64_t* c0, const uint64_t* c1, uint32_t kAuto, uint32_t sizeQl,
+                                       uint32_t batch, const uint64_t* out0, const uint64_t* out1, const void* ws, const char* who) {
+    ARG_CHECK(kAuto % 2 == 1, "Automorphism index not odd");
+    const size_t tower = (((size_t)batch * bh->h->numQ) << bh->h->ctx->logN) * 8, wsB = fhe_bfv_hybrid_workspace_bytes(bh, sizeQl, batch);
+    for (const uint64_t* o : {out0, out1})
+        ARG_CHECK(!bfv_hybrid_overlap(o, tower, c0, tower) && !bfv_hybrid_overlap(o, tower, c1, tower) && !bfv_hybrid_overlap(o, tower, ws, wsB),
+                  std::string(who) + ": the outputs must not alias c0, c1 or ws");
+    ARG_CHECK(!bfv_hybrid_overlap(out0, tower, out1, tower), std::string(who) + ": the outputs must not alias each other");
+    return FHE_OK;
+}
+// LeveledSHEBFVRNS::EvalFastRotationPrecompute (bfvrns-leveledshe.cpp:782-813) with KeySwitchHYBRID::EvalKeySwitchPrecomputeCore
+extern "C" fhe_status fhe_bfv_fast_rotation_precompute_hybrid(fhe_bfv_hybrid* bh, const uint64_t* c1, uint32_t sizeQl, uint32_t batch, void* ws,
+                                                              size_t wsBytes, void* st) {
+    ARG_CHECK(c1, "fhe_bfv_fast_rotation_precompute_hybrid: null argument");
+    if (fhe_status s = bfv_hybrid_check(bh, nullptr, false, sizeQl, batch, ws, wsBytes, "fhe_bfv_fast_rotation_precompute_hybrid"))
+        return s;
+    RT_CHECK(rt::set_device(bh->h->ctx->device));
+    return bfv_hybrid_digits(bh, c1, 1, sizeQl, batch, (uint64_t*)ws, ks_layout(bh->ks, sizeQl, batch), st);
+}
+// LeveledSHEBFVRNS::EvalFastRotation (bfvrns-leveledshe.cpp:815-882) on the digits the precompute left in ws
+extern "C" fhe_status fhe_bfv_eval_fast_rotation_hybrid(fhe_bfv_hybrid* bh, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1,
+                                                        uint32_t kAuto, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1,
+                                                        void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(c0 && c1 && out0 && out1, "fhe_bfv_eval_fast_rotation_hybrid: null argument");
+    if (fhe_status s = bfv_hybrid_check(bh, key, true, sizeQl, batch, ws, wsBytes, "fhe_bfv_eval_fast_rotation_hybrid"))
+        return s;
+    if (fhe_status s = bfv_hybrid_rot_check(bh, c0, c1, kAuto, sizeQl, batch, out0, out1, ws, "fhe_bfv_eval_fast_rotation_hybrid"))
+        return s;
+    const KsLayout w = ks_layout(bh->ks, sizeQl, batch);
+    uint64_t* wsp    = (uint64_t*)ws;
+    return bfv_hybrid_fast(bh, key, sizeQl == bh->h->numQ ? c1 : wsp + w.d2, c0, nullptr, kAuto, sizeQl, batch, out0, out1, wsp, w, st,
+                           "fhe_bfv_eval_fast_rotation_hybrid");
+}
+// LeveledSHEBFVRNS::EvalAutomorphism (bfvrns-leveledshe.cpp:767-780): RelinearizeCore on two elements, then both through the automorphism
+extern "C" fhe_status fhe_bfv_eval_automorphism_hybrid(fhe_bfv_hybrid* bh, const fhe_ks_key* key, const uint64_t* c0, const uint64_t* c1,
+                                                       uint32_t kAuto, uint32_t sizeQl, uint32_t batch, uint64_t* out0, uint64_t* out1,
+                                                       void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(c0 && c1 && out0 && out1, "fhe_bfv_eval_automorphism_hybrid: null argument");
+    if (fhe_status s = bfv_hybrid_check(bh, key, true, sizeQl, batch, ws, wsBytes, "fhe_bfv_eval_automorphism_hybrid"))
+        return s;
+    if (fhe_status s = bfv_hybrid_rot_check(bh, c0, c1, kAuto, sizeQl, batch, out0, out1, ws, "fhe_bfv_eval_automorphism_hybrid"))
+        return s;
+    const KsLayout w = ks_layout(bh->ks, sizeQl, batch);
+    uint64_t* wsp    = (uint64_t*)ws;
+    RT_CHECK(rt::set_device(bh->h->ctx->device));
+    if (fhe_status s = bfv_hybrid_digits(bh, c1, 1, sizeQl, batch, wsp, w, st))
+        return s;
+    return bfv_hybrid_fast(bh, key, sizeQl == bh->h->numQ ? c1 : wsp + w.d2, c0, nullptr, kAuto, sizeQl, batch, out0, out1, wsp, w, st,
+                           "fhe_bfv_eval_automorphism_hybrid");
+}
+// LeveledSHEBFVRNS::RelinearizeCore on three elements (bfvrns-leveledshe.cpp:888-938).  inEval == 0: d2 goes straight into ScaleAndRound (at the
+// top level: straight into the digit decomposition), d0 / d1 are transformed once, into c0 / c1, and the tail adds in place.
+extern "C" fhe_status fhe_bfv_relinearize_hybrid(fhe_bfv_hybrid* bh, const fhe_ks_key* key, const uint64_t* d0, const uint64_t* d1,
+                                                 const uint64_t* d2, int inEval, uint32_t sizeQl, uint32_t batch, uint64_t* c0, uint64_t* c1,
+                                                 void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(d0 && d1 && d2 && c0 && c1, "fhe_bfv_relinearize_hybrid: null argument");
+    if (fhe_status s = bfv_hybrid_check(bh, key, true, sizeQl, batch, ws, wsBytes, "fhe_bfv_relinearize_hybrid"))
+        return s;
+    fhe_ctx* c       = bh->h->ctx;
+    const KsLayout w = ks_layout(bh->ks, sizeQl, batch);
+    uint64_t* wsp    = (uint64_t*)ws;
+    RT_CHECK(rt::set_device(c->device));
+    if (fhe_status s = bfv_hybrid_digits(bh, d2, inEval, sizeQl, batch, wsp, w, st))
+        return s;
+    if (!inEval) {
+        if (fhe_status s = fhe_ntt_fwd_oop(c, d0, c0, nullptr, bh->h->numQ, batch, st))
+            return s;
+        if (fhe_status s = fhe_ntt_fwd_oop(c, d1, c1, nullptr, bh->h->numQ, batch, st))
+            return s;
+        d0 = c0, d1 = c1;
+    }
+    return bfv_hybrid_fast(bh, key, sizeQl == bh->h->numQ && inEval ? d2 : wsp + w.d2, d0, d1, 1, sizeQl, batch, c0, c1, wsp, w, st,
+                           "fhe_bfv_relinearize_hybrid");
+}
+// LeveledSHEBFVRNS::EvalMult(ct, ct, key) (bfvrns-leveledshe.cpp:735-741): the product at sizeQlMult with d0, d1 left in c0, c1 and d2 in ws,
+// COEFFICIENT as the reference leaves them, then the relinearisation at sizeQlRelin.
+// workspace (bytes): d2 [batch][numQ][N] | max(the product's, the relinearisation's)
+extern "C" size_t fhe_bfv_eval_mult_relin_hps_hybrid_workspace_bytes(const fhe_bfv_hybrid* bh, uint32_t sizeQlMult, uint32_t sizeQlRelin,
+                                                                     uint32_t batch) {
+    if (!bh)
+        return 0;
+    const size_t mul = fhe_bfv_eval_mult_hps_workspace_bytes(bh->h, sizeQlMult, batch);
+    const size_t ks  = fhe_bfv_hybrid_workspace_bytes(bh, sizeQlRelin, batch);
+    if (!mul || !ks)
+        return 0;
+    return ((((size_t)batch * bh->h->numQ) << bh->h->ctx->logN) * 8) + std::max(mul, ks);
+}
+extern "C" fhe_status fhe_bfv_eval_mult_relin_hps_hybrid(fhe_bfv_hybrid* bh, const fhe_ks_key* key, const uint64_t* a0, const uint64_t* a1,
+                                                         const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1,
+                                                         uint32_t sizeQlMult, uint32_t sizeQlRelin, uint32_t batch, void* ws, size_t wsBytes,
+                                                         void* st) {
+    ARG_CHECK(bh && key && a0 && a1 && b0 && b1 && c0 && c1 && ws && batch >= 1, "fhe_bfv_eval_mult_relin_hps_hybrid: null argument");
+    ARG_CHECK(hps_level(bh->h, sizeQlMult), "fhe_bfv_eval_mult_relin_hps_hybrid: sizeQlMult must be numQ (1 ... numQ for HPSPOVERQLEVELED)");
+    if (fhe_status s = bfv_hybrid_check(bh, key, true, sizeQlRelin, batch, ws, ~(size_t)0, "fhe_bfv_eval_mult_relin_hps_hybrid"))
+        return s;  // (everything but the size, which is this call's own)
+    const size_t need = fhe_bfv_eval_mult_relin_hps_hybrid_workspace_bytes(bh, sizeQlMult, sizeQlRelin, batch);
+    ARG_CHECK(need && wsBytes >= need, "fhe_bfv_eval_mult_relin_hps_hybrid: workspace too small");
+    const size_t d2Bytes = (((size_t)batch * bh->h->numQ) << bh->h->ctx->logN) * 8;
+    uint64_t* d2 = (uint64_t*)ws;
+    void* rest   = (char*)ws + d2Bytes;
+    if (fhe_status s = fhe_bfv_eval_mult_hps(bh->h, a0, a1, b0, b1, c0, c1, d2, sizeQlMult, 0, batch, rest, wsBytes - d2Bytes, st))
+        return s;
+    return fhe_bfv_relinearize_hybrid(bh, key, c0, c1, d2, 0, sizeQlRelin, batch, c0, c1, rest, wsBytes - d2Bytes, st);
 }
 
 // whole-tower checksums (checksum_kernel): out[row] = {sum_i w_i, sum_i (2i + 1) w_i} mod 2^64 of every limb-row of x[rows][N]; out is DEVICE memory

@@ -127,6 +127,7 @@ class Lib:
         S("fhe_ks_plan_create", C.c_int, [vp, u32, u32, u32, C.POINTER(vp)])
         S("fhe_ks_plan_destroy", None, [vp])
         S("fhe_ks_plan_alpha", u32, [vp])
+        S("fhe_ks_plan_levels_built", u32, [vp])
         S("fhe_ks_key_alloc", C.c_int, [vp, C.POINTER(vp)])
         S("fhe_ks_key_upload", C.c_int, [vp, u64p, u64p, C.POINTER(vp)])
         S("fhe_ks_key_wrap", C.c_int, [vp, vp, vp, C.POINTER(vp)])
@@ -229,6 +230,15 @@ class Lib:
         S("fhe_bfv_relinearize_bv", C.c_int, [vp] * 5 + [C.c_int, u32, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes", C.c_size_t, [vp, u32, u32, u32, u32])
         S("fhe_bfv_eval_mult_relin_hps_bv_leveled", C.c_int, [vp] * 8 + [u32, u32, u32, vp, C.c_size_t, vp])
+        S("fhe_bfv_hybrid_create", C.c_int, [vp, vp, C.POINTER(vp)])
+        S("fhe_bfv_hybrid_destroy", None, [vp])
+        S("fhe_bfv_hybrid_workspace_bytes", C.c_size_t, [vp, u32, u32])
+        S("fhe_bfv_fast_rotation_precompute_hybrid", C.c_int, [vp, vp, u32, u32, vp, C.c_size_t, vp])
+        S("fhe_bfv_eval_fast_rotation_hybrid", C.c_int, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_eval_automorphism_hybrid", C.c_int, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_relinearize_hybrid", C.c_int, [vp] * 5 + [C.c_int, u32, u32, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_eval_mult_relin_hps_hybrid_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_bfv_eval_mult_relin_hps_hybrid", C.c_int, [vp] * 8 + [u32, u32, u32, vp, C.c_size_t, vp])
         S("fhe_param_first_prime", u64, [u32, u64])
         S("fhe_param_last_prime", u64, [u32, u64])
         S("fhe_param_next_prime", u64, [u64, u64])
@@ -1610,6 +1620,90 @@ class Hps:
         try:
             self.ctx.lib.check(L.fhe_bfv_eval_mult_relin_hps_bv(self.h, bv_key.h, a0.ptr, a1.ptr, b0.ptr, b1.ptr, c0.ptr, c1.ptr, size_ql, B,
                                                                 ws, wsb, stream))
+            self.ctx.sync(stream)
+        finally:
+            self.ctx.free(ws)
+        return c0, c1
+
+
+class BfvHybrid:
+    """BFV of the HPS family on HYBRID keys: an Hps plan paired with a KeySwitchPlan of the same context (Q the context's leading limbs, the
+    plan's sizeQ == numQ).  Keys are KeySwitchPlan handles (make_key / upload_key).  size_ql = numQ - levelsDropped for the KEY SWITCH: 1 ...
+    numQ for HPSPOVERQLEVELED, numQ otherwise; None = numQ."""
+
+    def __init__(self, hps, ks_plan):
+        self.ctx, self.hps, self.ks = hps.ctx, hps, ks_plan
+        self.numQ, self.q_idx = hps.numQ, hps.q_idx
+        h = vp()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_hybrid_create(hps.h, ks_plan.h, C.byref(h)))
+        self.h = h
+        self._ws = None  # the digits of the last FastRotationPrecompute stay here (hoisting)
+        self._ws_bytes = 0
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.L.fhe_bfv_hybrid_destroy(self.h)
+            self.h = None
+        if self._ws is not None and self.ctx.h:
+            self.ctx.free(self._ws)
+        self._ws = None
+
+    def workspace(self, size_ql, batch):
+        need = self.ctx.lib.L.fhe_bfv_hybrid_workspace_bytes(self.h, size_ql, batch)
+        if need > self._ws_bytes:
+            if self._ws is not None:
+                self.ctx.free(self._ws)
+            self._ws = self.ctx.malloc(need)
+            self._ws_bytes = need
+        return self._ws, self._ws_bytes
+
+    def FastRotationPrecompute(self, c1, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:782-813
+        """the digits of c1 (EVALUATION) at size_ql limbs, left in the plan's workspace"""
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.workspace(size_ql, c1.batch)
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_fast_rotation_precompute_hybrid(self.h, c1.ptr, size_ql, c1.batch, ws, wsb, stream))
+        return ws, wsb
+
+    def FastRotation(self, key, c0, c1, k, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:815-882
+        """on the digits of the last FastRotationPrecompute(c1) at the same size_ql; k = automorphism index"""
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.workspace(size_ql, c0.batch)
+        o0, o1 = c0.like(), c0.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_eval_fast_rotation_hybrid(self.h, key, c0.ptr, c1.ptr, k, size_ql, c0.batch, o0.ptr, o1.ptr,
+                                                                            ws, wsb, stream))
+        return o0, o1
+
+    def Automorphism(self, key, c0, c1, k, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:767-780
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.workspace(size_ql, c0.batch)
+        o0, o1 = c0.like(), c0.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_eval_automorphism_hybrid(self.h, key, c0.ptr, c1.ptr, k, size_ql, c0.batch, o0.ptr, o1.ptr,
+                                                                           ws, wsb, stream))
+        return o0, o1
+
+    def Relinearize(self, key, d0, d1, d2, size_ql=None, stream=None):  # bfvrns-leveledshe.cpp:888-938
+        """(d0 + Expand(ks0(d2)), d1 + Expand(ks1(d2))), EVALUATION; the three inputs share one format (COEFFICIENT as EvalMultNoRelin
+        leaves them, or EVALUATION)"""
+        size_ql = self.numQ if size_ql is None else size_ql
+        ws, wsb = self.workspace(size_ql, d0.batch)
+        c0, c1 = (self.ctx.empty(d0.batch, self.numQ, self.q_idx, EVALUATION) for _ in range(2))
+        self.ctx.lib.check(self.ctx.lib.L.fhe_bfv_relinearize_hybrid(self.h, key, d0.ptr, d1.ptr, d2.ptr, 1 if d2.fmt == EVALUATION else 0,
+                                                                     size_ql, d0.batch, c0.ptr, c1.ptr, ws, wsb, stream))
+        return c0, c1
+
+    def EvalMult(self, key, a0, a1, b0, b1, size_ql=None, size_ql_relin=None, stream=None):  # bfvrns-leveledshe.cpp:735-741
+        """LeveledSHEBFVRNS::EvalMult(ct, ct, key): the product at size_ql limbs, the relinearisation at size_ql_relin; returns (c0, c1),
+        EVALUATION"""
+        B = a0.batch
+        size_ql = self.numQ if size_ql is None else size_ql
+        size_ql_relin = self.numQ if size_ql_relin is None else size_ql_relin
+        c0, c1 = (self.ctx.empty(B, self.numQ, self.q_idx, EVALUATION) for _ in range(2))
+        L = self.ctx.lib.L
+        wsb = max(L.fhe_bfv_eval_mult_relin_hps_hybrid_workspace_bytes(self.h, size_ql, size_ql_relin, B), 8)
+        ws = self.ctx.malloc(wsb)
+        try:
+            self.ctx.lib.check(L.fhe_bfv_eval_mult_relin_hps_hybrid(self.h, key, a0.ptr, a1.ptr, b0.ptr, b1.ptr, c0.ptr, c1.ptr, size_ql,
+                                                                    size_ql_relin, B, ws, wsb, stream))
             self.ctx.sync(stream)
         finally:
             self.ctx.free(ws)

@@ -713,6 +713,7 @@ public:
         return {std::move(o0), std::move(o1)};
     }
     uint32_t AutomorphismIndex(int32_t index) const { return m_rot.at(index).first; }
+    const fhe_ks_key* RotationKey(int32_t index) const { return m_rot.at(index).second; }
     fhe_ks_plan* plan() const { return m_plan; }
     const fhe_ks_key* key() const { return m_key; }
 
@@ -915,6 +916,102 @@ private:
     std::shared_ptr<Params> m_params;
     uint32_t m_numQ;
     fhe_hps* m_plan = nullptr;
+};
+
+// BFV of the HPS family on HYBRID keys: rotations and relinearisation at the level the reference drops to (LeveledSHEBFVRNS::
+// EvalFastRotationPrecompute / EvalFastRotation / EvalAutomorphism / RelinearizeCore / EvalMult, bfvrns-leveledshe.cpp:735-938, with
+// KeySwitchHYBRID).  Pairs an HpsPlan with a KeySwitchHybrid of the same context (Q the context's leading limbs, the key-switch plan's
+// sizeQ == numQ); both must outlive this object.  All towers are [batch][numQ][N]; sizeQl = numQ - levelsDropped for the KEY SWITCH
+// (1 ... numQ for HPSPOVERQLEVELED, numQ otherwise; 0 = numQ).  Keys are the KeySwitchHybrid's (key() / RotationKey(index)), k is the
+// automorphism index (AutomorphismIndex(index)).
+class BfvHybrid {
+public:
+    BfvHybrid(std::shared_ptr<Params> params, HpsPlan& hps, KeySwitchHybrid& ks, uint32_t numQ)
+        : m_params(std::move(params)), m_numQ(numQ) {
+        check(fhe_bfv_hybrid_create(hps.plan(), ks.plan(), &m_plan));
+    }
+    ~BfvHybrid() {
+        fhe_bfv_hybrid_destroy(m_plan);
+        if (m_ws)
+            fhe_free(m_params->ctx(), m_ws);
+    }
+    BfvHybrid(const BfvHybrid&)            = delete;
+    BfvHybrid& operator=(const BfvHybrid&) = delete;
+    // the digits of c1 at sizeQl limbs; they live in this object's workspace until the next precompute, automorphism or relinearisation
+    void FastRotationPrecompute(const DCRTPolyHip& c1, uint32_t sizeQl = 0) {
+        sizeQl = level(sizeQl);
+        reserve(sizeQl, c1.GetBatch());
+        check(fhe_bfv_fast_rotation_precompute_hybrid(m_plan, c1.data(), sizeQl, c1.GetBatch(), m_ws, m_wsBytes, nullptr));
+    }
+    std::pair<DCRTPolyHip, DCRTPolyHip> FastRotation(const fhe_ks_key* key, const DCRTPolyHip& c0, const DCRTPolyHip& c1, uint32_t k,
+                                                     uint32_t sizeQl = 0) {
+        const uint32_t batch = c0.GetBatch();
+        DCRTPolyHip o0(m_params, m_numQ, EVALUATION, batch), o1(m_params, m_numQ, EVALUATION, batch);
+        check(fhe_bfv_eval_fast_rotation_hybrid(m_plan, key, c0.data(), c1.data(), k, level(sizeQl), batch, o0.data(), o1.data(), m_ws,
+                                                m_wsBytes, nullptr));
+        return {std::move(o0), std::move(o1)};
+    }
+    std::pair<DCRTPolyHip, DCRTPolyHip> Automorphism(const fhe_ks_key* key, const DCRTPolyHip& c0, const DCRTPolyHip& c1, uint32_t k,
+                                                     uint32_t sizeQl = 0) {
+        const uint32_t batch = c0.GetBatch();
+        sizeQl = level(sizeQl);
+        DCRTPolyHip o0(m_params, m_numQ, EVALUATION, batch), o1(m_params, m_numQ, EVALUATION, batch);
+        reserve(sizeQl, batch);
+        check(fhe_bfv_eval_automorphism_hybrid(m_plan, key, c0.data(), c1.data(), k, sizeQl, batch, o0.data(), o1.data(), m_ws, m_wsBytes,
+                                               nullptr));
+        return {std::move(o0), std::move(o1)};
+    }
+    // (d0 + Expand(ks0(d2)), d1 + Expand(ks1(d2))), EVALUATION; the three inputs share one format (COEFFICIENT as EvalMultNoRelin leaves
+    // them, or EVALUATION)
+    std::pair<DCRTPolyHip, DCRTPolyHip> Relinearize(const fhe_ks_key* key, const DCRTPolyHip& d0, const DCRTPolyHip& d1,
+                                                    const DCRTPolyHip& d2, uint32_t sizeQl = 0) {
+        const uint32_t batch = d0.GetBatch();
+        sizeQl = level(sizeQl);
+        DCRTPolyHip c0(m_params, m_numQ, EVALUATION, batch), c1(m_params, m_numQ, EVALUATION, batch);
+        reserve(sizeQl, batch);
+        check(fhe_bfv_relinearize_hybrid(m_plan, key, d0.data(), d1.data(), d2.data(), d2.GetFormat() == EVALUATION ? 1 : 0, sizeQl, batch,
+                                         c0.data(), c1.data(), m_ws, m_wsBytes, nullptr));
+        return {std::move(c0), std::move(c1)};
+    }
+    // cc->EvalMult: the product at sizeQlMult limbs, the relinearisation at sizeQlRelin
+    std::pair<DCRTPolyHip, DCRTPolyHip> EvalMult(const fhe_ks_key* key, const DCRTPolyHip& a0, const DCRTPolyHip& a1, const DCRTPolyHip& b0,
+                                                 const DCRTPolyHip& b1, uint32_t sizeQlMult = 0, uint32_t sizeQlRelin = 0) {
+        const uint32_t batch = a0.GetBatch();
+        sizeQlMult = level(sizeQlMult), sizeQlRelin = level(sizeQlRelin);
+        DCRTPolyHip c0(m_params, m_numQ, EVALUATION, batch), c1(m_params, m_numQ, EVALUATION, batch);
+        const size_t need = fhe_bfv_eval_mult_relin_hps_hybrid_workspace_bytes(m_plan, sizeQlMult, sizeQlRelin, batch);
+        if (need == 0)
+            throw Error("BFV on HYBRID keys: a level does not fit the technique");
+        void* ws = nullptr;
+        check(fhe_malloc(m_params->ctx(), need, &ws));
+        const fhe_status st = fhe_bfv_eval_mult_relin_hps_hybrid(m_plan, key, a0.data(), a1.data(), b0.data(), b1.data(), c0.data(),
+                                                                 c1.data(), sizeQlMult, sizeQlRelin, batch, ws, need, nullptr);
+        fhe_stream_sync(m_params->ctx(), nullptr);
+        fhe_free(m_params->ctx(), ws);
+        check(st);
+        return {std::move(c0), std::move(c1)};
+    }
+    fhe_bfv_hybrid* plan() const { return m_plan; }
+
+private:
+    uint32_t level(uint32_t sizeQl) const { return sizeQl ? sizeQl : m_numQ; }
+    void reserve(uint32_t sizeQl, uint32_t batch) {
+        const size_t need = fhe_bfv_hybrid_workspace_bytes(m_plan, sizeQl, batch);
+        if (need == 0)
+            throw Error("BFV on HYBRID keys: sizeQl does not fit the technique");
+        if (need > m_wsBytes) {
+            if (m_ws)
+                fhe_free(m_params->ctx(), m_ws);
+            m_ws = nullptr, m_wsBytes = 0;
+            check(fhe_malloc(m_params->ctx(), need, &m_ws));
+            m_wsBytes = need;
+        }
+    }
+    std::shared_ptr<Params> m_params;
+    uint32_t m_numQ;
+    fhe_bfv_hybrid* m_plan = nullptr;
+    void* m_ws             = nullptr;
+    size_t m_wsBytes       = 0;
 };
 
 }  // namespace fhehip
