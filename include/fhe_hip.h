@@ -292,6 +292,57 @@ void       fhe_ks_key_destroy(fhe_ks_key* key);
 uint64_t*  fhe_ks_key_devptr(fhe_ks_key* key, int which);
 size_t     fhe_ks_key_words(const fhe_ks_key* key);
 
+/* ---- evaluation-key generation on the device ---------------------------------------------------------
+ * fhe_keygen_combine: everything of key generation that is not sampling or transforming, for nKeys keys of nParts digits in ONE launch
+ * (csrc/keygen_kernels.h).  For key < nKeys, digit j < nParts, tower row i < nLimbs (context limb limbIdx[i], NULL = identity), word n:
+ *   out[key][j][i][n] = ns * e[key][j][i][n] - a[key][j][i][n] * sNew[i][pi_kNew[key](n)] + factor[j][i] * sOld[i][pi_kOld[key](n)]  mod q_i
+ * which is the loop body of KeySwitchHYBRID::KeySwitchGenInternal (src/pke/lib/keyswitch/keyswitch-hybrid.cpp:98-123:
+ * b_i = -a_i * sNewExt_i + ns * e_i [+ PModq_i * sOld_i]) with the permuted secret of LeveledSHEBase::EvalAutomorphismKeyGen
+ * (src/pke/lib/schemebase/base-leveledshe.cpp:336-379) read through the index map instead of being materialised, and with factor == NULL
+ * (no sOld term: sOld and kOld are ignored) b = ns * e - a * s of PKEBase::KeyGenInternal (src/pke/lib/schemebase/base-pke.cpp:47-98).
+ *   a, e, out  DEVICE [nKeys][nParts][nLimbs][N]; sNew, sOld DEVICE [nLimbs][N]; all EVALUATION format, canonical residues in and out;
+ *   pi_k       the index map of fhe_automorph(evalFormat = 1) for the odd index k in [1, 2N); kNew, kOld: HOST arrays [nKeys], NULL = all 1
+ *              (k = 1 reads the row in place, without a gather);
+ *   factor     HOST array [nParts][nLimbs], reduced modulo q_i inside.  A zero entry means "term absent": sOld is read only in rows where
+ *              some digit has a non-zero factor, so it needs rows only up to the last such limb (HYBRID keys: sizeQ rows; BV keys will use
+ *              the same formula with other constants);
+ *   ns         GetNoiseScale(): 1 for CKKS and BFV, t for BGV; reduced modulo every limb (ns >= q_i is legal), 0 is refused.
+ * out may be e itself (every word of e is read before the same word of out is written); it must not overlap e otherwise, nor a, sNew or
+ * sOld.  Errors (FHE_ERR_ARG, nothing is enqueued, out untouched): a null operand, nKeys == 0, nParts == 0, an even automorphism index
+ * ("Automorphism index not odd") or one >= 2N, ns == 0, a forbidden overlap.  The factors and ns go through a table cached by content:
+ * the first call with new ones uploads it (not capturable), later calls are pure launches.  One launch per 256 keys: the keys' indices
+ * travel by value in the kernel arguments (4 KiB); no grid limit is reached before that. */
+fhe_status fhe_keygen_combine(fhe_ctx* ctx, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t nKeys, uint32_t nParts, const uint64_t* a,
+                              const uint64_t* e, const uint64_t* sNew, const uint32_t* kNew, const uint64_t* sOld, const uint32_t* kOld,
+                              const uint64_t* factor, uint64_t ns, uint64_t* out, void* stream);
+/* The sNewExt block of KeySwitchHYBRID::KeySwitchGenInternal (keyswitch-hybrid.cpp:59-83): sQ [sizeQ][N] EVALUATION -> outExt
+ * [sizeQ+sizeP][N] EVALUATION.  The Q rows are copied; the P rows are limb 0 in COEFFICIENT format (inverse transform), centre-switched to
+ * every p_j (PolyImpl::SwitchModulus, the kernel of fhe_switch_modulus) and transformed.  ws: N words (8 N bytes) of device workspace.
+ * outExt may start at sQ (the Q rows then stay where they are) and must not overlap it otherwise. */
+fhe_status fhe_ks_secret_extend(fhe_ks_plan* plan, const uint64_t* sQ, uint64_t* outExt, void* ws, size_t wsBytes, void* stream);
+/* KeySwitchHYBRID::KeySwitchGenInternal(oldKey, newKey) (keyswitch-hybrid.cpp:51-130) for nKeys keys with the caller's randomness: ONE
+ * launch of fhe_keygen_combine over the plan's Q u P limbs with factor[j][i] = [P]_{q_i} for the limbs i of digit j (alpha * j <= i <
+ * min(alpha * (j + 1), sizeQ)) and 0 elsewhere.  sNewExt [sizeQ+sizeP][N] (fhe_ks_secret_extend), sOld [sizeQ][N]; a, e, devKeyB
+ * [nKeys][numPartQ][sizeQ+sizeP][N], devKeyB == e allowed.  Window `key` of devKeyB / a is what fhe_ks_key_wrap adopts.
+ * EvalAutomorphismKeyGen (base-leveledshe.cpp:336-379) for the automorphism index k: kNew = k^-1 mod 2N, kOld = 1 (the NEW secret is the
+ * permuted one); EvalMultKeyGen: kNew = kOld = 1 with sOld = s * s. */
+fhe_status fhe_ks_keygen_hybrid(fhe_ks_plan* plan, uint32_t nKeys, const uint32_t* kNew, const uint32_t* kOld, const uint64_t* sNewExt,
+                                const uint64_t* sOld, uint64_t ns, const uint64_t* a, const uint64_t* e, uint64_t* devKeyB, void* stream);
+/* The seeded form, defined as a composition (batch = nKeys * numPartQ towers over Q u P):
+ *   devKeyA = the words of fhe_sample_uniform_blake2(batch, key, counterA), used as drawn: the reference draws a in EVALUATION format;
+ *   devKeyB = fhe_sample_gaussian_blake2(batch, sigma, key, counterE), then fhe_ntt_fwd in place, then fhe_ks_keygen_hybrid in place.
+ * No workspace: the error tower never exists outside the buffer that ends up holding b.  Launches: the two samplers, the passes of one
+ * forward transform over the whole batch and one combine (per 256 keys), whatever nKeys is: five on a two-pass ring (N >= 8192), six when
+ * the batched row pass of N = 2^16 / 2^17 takes towers in pairs and an odd batch leaves it a last one.  The a half of every key is a function of
+ * (key, counterA) alone: another device can regenerate it with fhe_sample_uniform_blake2 instead of receiving it.  The blake2 key travels
+ * by value.  The first Gaussian call with a new sigma uploads its inversion table (not capturable), as in fhe_sample_gaussian.  Every
+ * argument is checked before the first launch: the errors of fhe_keygen_combine, and sigma outside 1 < sigma < 300. */
+fhe_status fhe_ks_keygen_hybrid_blake2(fhe_ks_plan* plan, uint32_t nKeys, const uint32_t* kNew, const uint32_t* kOld,
+                                       const uint64_t* sNewExt, const uint64_t* sOld, uint64_t ns, double sigma, const uint32_t key[16],
+                                       uint64_t counterA, uint64_t counterE, uint64_t* devKeyB, uint64_t* devKeyA, void* stream);
+/* blake2 counters fhe_ks_keygen_hybrid_blake2 consumes from counterA (*nA) and from counterE (*nE): lay out disjoint ranges with them */
+fhe_status fhe_ks_keygen_counters(const fhe_ks_plan* plan, uint32_t nKeys, uint64_t* nA, uint64_t* nE);
+
 /* workspace (device bytes) needed by the composite calls below for `batch` towers at level sizeQl */
 size_t     fhe_ks_workspace_bytes(const fhe_ks_plan* plan, uint32_t sizeQl, uint32_t batch);
 

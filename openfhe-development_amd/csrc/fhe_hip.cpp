@@ -23,6 +23,7 @@
 #include "bfv_kernels.h"
 #include "elemwise_kernels.h"
 #include "host_math.h"
+#include "keygen_kernels.h"
 #include "ntt_kernels.h"
 #include "ntt_static.h"
 #include "ntt_row8.h"
@@ -2767,6 +2768,186 @@ extern "C" fhe_status fhe_ks_down(fhe_ks_plan* p, const uint64_t* x0, const uint
     if (fhe_status s = mod_down_run(p, lv, x0, batch, out0, wsp + w.pcoef, wsp + w.md, st))
         return s;
     return mod_down_run(p, lv, x1, batch, out1, wsp + w.pcoef, wsp + w.md, st);
+}
+
+// ---- evaluation-key generation (keygen_kernels.h) ----
+// KeySwitchHYBRID::KeySwitchGenInternal (keyswitch-hybrid.cpp:51-130), LeveledSHEBase::EvalAutomorphismKeyGen (base-leveledshe.cpp:336-379)
+// and PKEBase::KeyGenInternal (base-pke.cpp:47-98) for any number of keys: everything that is not sampling or transforming is ONE launch
+// of keygen_combine_kernel per kKeygenKeys keys (the keys' automorphism indices travel by value in the kernel arguments, whose 4 KiB set
+// that bound; the grid never does: 256 keys x 256 limbs x 64 tiles is far below 2^31 workgroups).  The factors f[j][i] and ns mod q_i go
+// through the context's table cache (const_table): the first call with a new (factor, ns) uploads, later calls are pure launches.
+static bool keygen_overlap(const void* x, size_t nx, const void* y, size_t ny) {
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+    return a < b + ny && b < a + nx;
+}
+// every check of the family, before anything is enqueued; oldRows: rows of sOld the kernel may read (0: no sOld term)
+static fhe_status keygen_check(const std::string& who, const fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t nKeys,
+                               uint32_t nParts, const uint64_t* a, const uint64_t* e, const uint64_t* sNew, const uint32_t* kNew,
+                               const uint64_t* sOld, const uint32_t* kOld, uint32_t oldRows, uint64_t ns, const uint64_t* out) {
+    ARG_CHECK(c && a && e && sNew && out && (sOld || !oldRows), who + ": null argument");
+    ARG_CHECK(nKeys >= 1, who + ": nKeys must be >= 1");
+    ARG_CHECK(nParts >= 1, who + ": nParts must be >= 1");
+    ARG_CHECK(nLimbs >= 1 && nLimbs <= (uint32_t)kMaxLimbs, who + ": nLimbs out of range");
+    for (uint32_t i = 0; i < nLimbs; ++i)
+        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, who + ": limb index exceeds context size");
+    ARG_CHECK(ns != 0, who + ": the noise scale must not be zero");
+    for (uint32_t k = 0; k < nKeys; ++k)
+        for (const uint32_t* ks : {kNew, kOld})
+            if (ks) {
+                ARG_CHECK(ks[k] % 2 == 1, "Automorphism index not odd");  // poly-impl.h:337-338
+                ARG_CHECK(ks[k] < 2u * c->N, who + ": automorphism index out of range (1 <= k < 2N)");
+            }
+    ARG_CHECK((uint64_t)nKeys * nParts * nLimbs < ((uint64_t)1 << 31), who + ": nKeys * nParts * nLimbs too large");
+    const size_t row = (size_t)c->N * 8, slab = (size_t)nKeys * nParts * nLimbs * row;
+    ARG_CHECK(out == e || !keygen_overlap(out, slab, e, slab), who + ": out may be e itself but not overlap it otherwise");
+    ARG_CHECK(!keygen_overlap(out, slab, a, slab) && !keygen_overlap(out, slab, sNew, nLimbs * row) &&
+                  !(oldRows && keygen_overlap(out, slab, sOld, oldRows * row)),
+              who + ": out must not overlap a, sNew or sOld");
+    return FHE_OK;
+}
+// rows of sOld that the factor table makes the kernel read: up to the last limb with a non-zero factor
+static uint32_t keygen_old_rows(const fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t nParts, const uint64_t* factor) {
+    uint32_t rows = 0;
+    if (factor && c && nLimbs <= (uint32_t)kMaxLimbs)
+        for (uint32_t j = 0; j < nParts; ++j)
+            for (uint32_t i = 0; i < nLimbs; ++i)
+                if ((limbIdx ? limbIdx[i] : i) < c->L && factor[(size_t)j * nLimbs + i] % c->q[limbIdx ? limbIdx[i] : i])
+                    rows = std::max(rows, i + 1);
+    return rows;
+}
+static fhe_status keygen_combine_run(const std::string& who, fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t nKeys,
+                                     uint32_t nParts, const uint64_t* a, const uint64_t* e, const uint64_t* sNew, const uint32_t* kNew,
+                                     const uint64_t* sOld, const uint32_t* kOld, const uint64_t* factor, uint64_t ns, uint64_t* out,
+                                     void* st) {
+    const uint32_t oldRows = keygen_old_rows(c, limbIdx, nLimbs, nParts, factor);
+    if (fhe_status s = keygen_check(who, c, limbIdx, nLimbs, nKeys, nParts, a, e, sNew, kNew, sOld, kOld, oldRows, ns, out))
+        return s;
+    KeygenArgs g;
+    if (fhe_status s = make_sel(c, limbIdx, nLimbs, &g.sel, who.c_str()))
+        return s;
+    RT_CHECK(rt::set_device(c->device));
+    // the table: f[nParts][nLimbs] (when there is an sOld term), then ns mod q_i [nLimbs] (unless ns == 1)
+    std::vector<uint32_t> li;
+    std::vector<uint64_t> v;
+    for (uint32_t j = 0; j < (factor ? nParts : 0u) + (ns != 1 ? 1u : 0u); ++j)
+        for (uint32_t i = 0; i < nLimbs; ++i) {
+            const uint32_t l = limbIdx ? limbIdx[i] : i;
+            li.push_back(l);
+            v.push_back((factor && j < nParts ? factor[(size_t)j * nLimbs + i] : ns) % c->q[l]);
+        }
+    const TwPair* table = nullptr;
+    if (fhe_status s = const_tables_trim(c))
+        return s;
+    std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
+    if (!v.empty())
+        if (fhe_status s = const_table(c, li.data(), v.data(), (uint32_t)v.size(), &table))
+            return s;
+    g.sNew = sNew, g.sOld = factor ? sOld : sNew, g.lc = c->d_lc, g.tab = table;
+    g.logN = c->logN, g.nLimbs = nLimbs, g.nParts = nParts;
+    const uint32_t tilesPerRow = c->logN > (uint32_t)kKeygenTileLog ? 1u << (c->logN - kKeygenTileLog) : 1u;
+    const size_t keyWords      = ((size_t)nParts * nLimbs) << c->logN;
+    for (uint32_t first = 0; first < nKeys; first += (uint32_t)kKeygenKeys) {
+        g.nKeys = std::min<uint32_t>(kKeygenKeys, nKeys - first);
+        for (uint32_t k = 0; k < (uint32_t)kKeygenKeys; ++k) {
+            g.kNew[k] = k < g.nKeys && kNew ? kNew[first + k] : 1u;
+            g.kOld[k] = k < g.nKeys && kOld ? kOld[first + k] : 1u;
+        }
+        g.out = out + first * keyWords, g.a = a + first * keyWords, g.e = e + first * keyWords;
+        const uint32_t grid = g.nKeys * nLimbs * tilesPerRow;
+        if (factor && ns == 1)
+            FHE_LAUNCH((keygen_combine_kernel<true, true>), grid, st, g);
+        else if (factor)
+            FHE_LAUNCH((keygen_combine_kernel<false, true>), grid, st, g);
+        else if (ns == 1)
+            FHE_LAUNCH((keygen_combine_kernel<true, false>), grid, st, g);
+        else
+            FHE_LAUNCH((keygen_combine_kernel<false, false>), grid, st, g);
+        LAUNCH_CHECK();
+    }
+    return FHE_OK;
+}
+extern "C" fhe_status fhe_keygen_combine(fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t nKeys, uint32_t nParts,
+                                         const uint64_t* a, const uint64_t* e, const uint64_t* sNew, const uint32_t* kNew,
+                                         const uint64_t* sOld, const uint32_t* kOld, const uint64_t* factor, uint64_t ns, uint64_t* out,
+                                         void* st) {
+    return keygen_combine_run("fhe_keygen_combine", c, limbIdx, nLimbs, nKeys, nParts, a, e, sNew, kNew, sOld, kOld, factor, ns, out, st);
+}
+// the sNewExt block of KeySwitchGenInternal (keyswitch-hybrid.cpp:59-83): the Q rows as they are; the P rows from limb 0 in COEFFICIENT
+// format, centre-switched to every p_j (PolyImpl::SwitchModulus) and transformed
+extern "C" fhe_status fhe_ks_secret_extend(fhe_ks_plan* p, const uint64_t* sQ, uint64_t* outExt, void* ws, size_t wsBytes, void* st) {
+    ARG_CHECK(p && sQ && outExt && ws, "fhe_ks_secret_extend: null argument");
+    fhe_ctx* c       = p->ctx;
+    const size_t row = (size_t)c->N * 8;
+    ARG_CHECK(wsBytes >= row, "fhe_ks_secret_extend: workspace too small (one limb row)");
+    ARG_CHECK(outExt == sQ || !keygen_overlap(outExt, (p->sizeQ + p->sizeP) * row, sQ, p->sizeQ * row),
+              "fhe_ks_secret_extend: outExt may start at sQ but not overlap it otherwise");
+    ARG_CHECK(!keygen_overlap(ws, row, outExt, (p->sizeQ + p->sizeP) * row) && !keygen_overlap(ws, row, sQ, p->sizeQ * row),
+              "fhe_ks_secret_extend: the workspace overlaps an operand");
+    RT_CHECK(rt::set_device(c->device));
+    if (outExt != sQ)
+        RT_CHECK(rt::d2d(outExt, sQ, p->sizeQ * row, (rt::stream_t)st));
+    const uint32_t limb0 = 0;
+    if (fhe_status s = fhe_ntt_inv_oop(c, sQ, (uint64_t*)ws, &limb0, 1, 1, st))
+        return s;
+    std::vector<uint32_t> pIdx(p->sizeP);
+    for (uint32_t j = 0; j < p->sizeP; ++j)
+        pIdx[j] = p->sizeQ + j;
+    uint64_t* pRows = outExt + ((size_t)p->sizeQ << c->logN);
+    if (fhe_status s = fhe_switch_modulus(c, pRows, pIdx.data(), p->sizeP, (const uint64_t*)ws, 1, 0, 0, 1, st))
+        return s;
+    return fhe_ntt_fwd(c, pRows, pIdx.data(), p->sizeP, 1, st);
+}
+// f[j][i] = [P]_{q_i} for the limbs of digit j (keyswitch-hybrid.cpp:105-119 with the partition of rns-cryptoparameters.cpp:85-91), else 0
+static std::vector<uint64_t> ks_keygen_factors(const fhe_ks_plan* p) {
+    const fhe_ctx* c     = p->ctx;
+    const uint32_t sizeQP = p->sizeQ + p->sizeP;
+    std::vector<uint64_t> pm(c->q.begin() + p->sizeQ, c->q.begin() + sizeQP), f((size_t)p->numPartQ * sizeQP, 0);
+    for (uint32_t j = 0; j < p->numPartQ; ++j)
+        for (uint32_t i = p->alpha * j; i < std::min(p->alpha * (j + 1), p->sizeQ); ++i)
+            f[(size_t)j * sizeQP + i] = host::prod_mod(pm, -1, c->q[i]);
+    return f;
+}
+extern "C" fhe_status fhe_ks_keygen_hybrid(fhe_ks_plan* p, uint32_t nKeys, const uint32_t* kNew, const uint32_t* kOld,
+                                           const uint64_t* sNewExt, const uint64_t* sOld, uint64_t ns, const uint64_t* a, const uint64_t* e,
+                                           uint64_t* devKeyB, void* st) {
+    ARG_CHECK(p && sOld, "fhe_ks_keygen_hybrid: null argument");
+    const std::vector<uint64_t> f = ks_keygen_factors(p);
+    return keygen_combine_run("fhe_ks_keygen_hybrid", p->ctx, nullptr, p->sizeQ + p->sizeP, nKeys, p->numPartQ, a, e, sNewExt, kNew, sOld,
+                              kOld, f.data(), ns, devKeyB, st);
+}
+extern "C" fhe_status fhe_ks_keygen_counters(const fhe_ks_plan* p, uint32_t nKeys, uint64_t* nA, uint64_t* nE) {
+    ARG_CHECK(p && nA && nE, "fhe_ks_keygen_counters: null argument");
+    ARG_CHECK(nKeys >= 1, "fhe_ks_keygen_counters: nKeys must be >= 1");
+    const uint64_t towers = (uint64_t)nKeys * p->numPartQ;
+    *nA = (((towers * (p->sizeQ + p->sizeP)) << p->ctx->logN) + 255) / 256;  // two 64-bit words per uniform residue, 512 per block
+    *nE = ((towers << p->ctx->logN) + 511) / 512;                            // one word per Gaussian coefficient
+    return FHE_OK;
+}
+// the seeded form, a composition: a = the uniform sampler's words as drawn (the reference draws a in EVALUATION format); e = the Gaussian
+// sampler's words, transformed in the buffer that then becomes b.  Every argument is checked before the first launch.
+extern "C" fhe_status fhe_ks_keygen_hybrid_blake2(fhe_ks_plan* p, uint32_t nKeys, const uint32_t* kNew, const uint32_t* kOld,
+                                                  const uint64_t* sNewExt, const uint64_t* sOld, uint64_t ns, double sigma,
+                                                  const uint32_t key[16], uint64_t counterA, uint64_t counterE, uint64_t* devKeyB,
+                                                  uint64_t* devKeyA, void* st) {
+    const std::string who = "fhe_ks_keygen_hybrid_blake2";
+    ARG_CHECK(p && sOld && key && devKeyA && devKeyB, who + ": null argument");
+    fhe_ctx* c            = p->ctx;
+    const uint32_t sizeQP = p->sizeQ + p->sizeP;
+    if (fhe_status s = keygen_check(who, c, nullptr, sizeQP, nKeys, p->numPartQ, devKeyA, devKeyB, sNewExt, kNew, sOld, kOld, p->sizeQ, ns,
+                                    devKeyB))
+        return s;
+    ARG_CHECK(sigma > 1.000000001 && sigma < 300.0, who + ": the inversion sampler covers 1 < sigma < 300 (the reference's Peikert range)");
+    const size_t slab = (((size_t)nKeys * p->numPartQ * sizeQP) << c->logN) * 8, row = (size_t)c->N * 8;
+    ARG_CHECK(!keygen_overlap(devKeyA, slab, sNewExt, sizeQP * row) && !keygen_overlap(devKeyA, slab, sOld, p->sizeQ * row),
+              who + ": devKeyA must not overlap sNewExt or sOld");
+    const uint32_t towers = nKeys * p->numPartQ;
+    if (fhe_status s = fhe_sample_uniform_blake2(c, devKeyA, nullptr, sizeQP, towers, key, counterA, st))
+        return s;
+    if (fhe_status s = fhe_sample_gaussian_blake2(c, devKeyB, nullptr, sizeQP, towers, sigma, key, counterE, st))
+        return s;
+    if (fhe_status s = fhe_ntt_fwd(c, devKeyB, nullptr, sizeQP, towers, st))
+        return s;
+    return fhe_ks_keygen_hybrid(p, nKeys, kNew, kOld, sNewExt, sOld, ns, devKeyA, devKeyB, devKeyB, st);
 }
 
 // ---- BSGS plaintext-matrix product with double hoisting ----

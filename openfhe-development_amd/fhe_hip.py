@@ -134,6 +134,11 @@ class Lib:
         S("fhe_ks_key_destroy", None, [vp])
         S("fhe_ks_key_devptr", vp, [vp, C.c_int])
         S("fhe_ks_key_words", C.c_size_t, [vp])
+        S("fhe_keygen_combine", C.c_int, [vp, u32p, u32, u32, u32, vp, vp, vp, u32p, vp, u32p, u64p, u64, vp, vp])
+        S("fhe_ks_secret_extend", C.c_int, [vp, vp, vp, vp, C.c_size_t, vp])
+        S("fhe_ks_keygen_hybrid", C.c_int, [vp, u32, u32p, u32p, vp, vp, u64, vp, vp, vp, vp])
+        S("fhe_ks_keygen_hybrid_blake2", C.c_int, [vp, u32, u32p, u32p, vp, vp, u64, C.c_double, u32p, u64, u64, vp, vp, vp])
+        S("fhe_ks_keygen_counters", C.c_int, [vp, u32, u64p, u64p])
         S("fhe_ks_workspace_bytes", C.c_size_t, [vp, u32, u32])
         S("fhe_keyswitch_hybrid", C.c_int, [vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_keyswitch_hybrid_acc", C.c_int, [vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp])
@@ -694,6 +699,74 @@ class KeySwitchPlan:
         N = self.ctx.N
         return self.numPartQ * (self.sizeQ + self.sizeP) * N
 
+    # ---- key generation on the device (KeySwitchHYBRID::KeySwitchGenInternal, keyswitch-hybrid.cpp:51-130) ----
+    def extend_secret(self, s, stream=None):
+        """the sNewExt block (:59-83): s [1][sizeQ][N] EVALUATION -> [1][sizeQ+sizeP][N] EVALUATION (fhe_ks_secret_extend)"""
+        assert s.batch == 1 and s.n_limbs == self.sizeQ and s.fmt == EVALUATION
+        out = self.ctx.empty(1, self.sizeQ + self.sizeP)
+        ws = self.ctx.malloc(self.ctx.N * 8)
+        try:
+            self.ctx.lib.check(self.ctx.lib.L.fhe_ks_secret_extend(self.h, s.ptr, out.ptr, ws, self.ctx.N * 8, stream))
+            self.ctx.sync(stream)
+        finally:
+            self.ctx.free(ws)
+        return out
+
+    def keygen_counters(self, n_keys):
+        """(blake2 counters keygen_blake2 consumes from counter_a, from counter_e) (fhe_ks_keygen_counters)"""
+        na, ne = u64(), u64()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_ks_keygen_counters(self.h, n_keys, C.byref(na), C.byref(ne)))
+        return na.value, ne.value
+
+    def _wrap_keys(self, b, a, n_keys, rotations):
+        words = self.key_words()
+        keys = []
+        for i in range(n_keys):
+            k = vp()
+            self.ctx.lib.check(self.ctx.lib.L.fhe_ks_key_wrap(self.h, vp(b.ptr.value + 8 * words * i), vp(a.ptr.value + 8 * words * i),
+                                                              C.byref(k)))
+            keys.append(k)
+        return keys if rotations is None else dict(zip(rotations, keys))
+
+    def _keygen_indices(self, n_keys, k_new, k_old, rotations):
+        if rotations is not None:
+            assert k_new is None and k_old is None and len(rotations) == n_keys
+            k_new, k_old = rotation_key_indices(self.ctx.lib, rotations, self.ctx.N)
+        kn, knp = _np_u32(k_new)
+        ko, kop = _np_u32(k_old)
+        assert (kn is None or len(kn) == n_keys) and (ko is None or len(ko) == n_keys)
+        return (kn, ko), knp, kop
+
+    def keygen(self, s_new_ext, s_old, a, e, k_new=None, k_old=None, ns=1, rotations=None, in_place=False, stream=None):
+        """fhe_ks_keygen_hybrid with the caller's a and e, Towers [nKeys * numPartQ][sizeQ+sizeP][N] in EVALUATION format; s_new_ext from
+        extend_secret, s_old [1][sizeQ][N].  k_new / k_old: automorphism indices per key (None = 1), or rotations = CKKS rotation indices
+        (rotation_key_indices).  in_place: b overwrites e.  Returns (b, a, keys): the two slabs and the wrapped key handles, a dict by
+        rotation index when rotations were given; the slabs own the memory the handles point into."""
+        n_keys, rem = divmod(a.batch, self.numPartQ)
+        assert rem == 0 and e.batch == a.batch and a.n_limbs == e.n_limbs == self.sizeQ + self.sizeP
+        keep, knp, kop = self._keygen_indices(n_keys, k_new, k_old, rotations)
+        b = e if in_place else e.like()
+        self.ctx.lib.check(self.ctx.lib.L.fhe_ks_keygen_hybrid(self.h, n_keys, knp, kop, s_new_ext.ptr, s_old.ptr, ns, a.ptr, e.ptr, b.ptr,
+                                                               stream))
+        return b, a, self._wrap_keys(b, a, n_keys, rotations)
+
+    def keygen_blake2(self, s_new_ext, s_old, n_keys, key, counter_a, counter_e, k_new=None, k_old=None, ns=1, sigma=3.19, rotations=None,
+                      stream=None):
+        """fhe_ks_keygen_hybrid_blake2: a = the uniform blake2 sampler's words from counter_a, e = the Gaussian sampler's from counter_e
+        (transformed and combined in the buffer that ends up holding b).  Returns (b, a, keys) as keygen does."""
+        keep, knp, kop = self._keygen_indices(n_keys, k_new, k_old, rotations)
+        b = self.ctx.empty(n_keys * self.numPartQ, self.sizeQ + self.sizeP)
+        a = self.ctx.empty(n_keys * self.numPartQ, self.sizeQ + self.sizeP)
+        kw = _key_words(key)
+        self.ctx.lib.check(self.ctx.lib.L.fhe_ks_keygen_hybrid_blake2(self.h, n_keys, knp, kop, s_new_ext.ptr, s_old.ptr, ns, sigma,
+                                                                      kw.ctypes.data_as(u32p), counter_a, counter_e, b.ptr, a.ptr, stream))
+        return b, a, self._wrap_keys(b, a, n_keys, rotations)
+
+    def destroy_keys(self, keys):
+        """release key handles made by keygen / keygen_blake2 / make_key (the slabs of wrapped keys stay with their Towers)"""
+        for k in (keys.values() if isinstance(keys, dict) else keys):
+            self.ctx.lib.L.fhe_ks_key_destroy(k)
+
     def workspace(self, sizeQl, batch):
         need = self.ctx.lib.L.fhe_ks_workspace_bytes(self.h, sizeQl, batch)
         if need > self._ws_bytes:
@@ -930,6 +1003,38 @@ class BvKey:
         self.ctx.lib.check(self.ctx.lib.L.fhe_bv_eval_automorphism(self.h, c0.ptr, c1.ptr, k, c0.n_limbs, c0.batch, o0.ptr, o1.ptr, ws, wsb,
                                                                    stream))
         return o0, o1
+
+
+def rotation_key_indices(lib, rotations, N):
+    """(kNew, kOld) of the evaluation keys of CKKS rotations (LeveledSHEBase::EvalAutomorphismKeyGen, base-leveledshe.cpp:336-379): for
+    the automorphism index k = FindAutomorphismIndex2nComplex(rotation) the key switches sigma_{k^-1}(s) ... to s, i.e. the NEW secret is
+    the permuted one (kNew = k^-1 mod 2N) and the old one is s itself (kOld = 1)"""
+    ks = [lib.find_automorphism_index(int(r), 2 * N) for r in rotations]
+    return np.array([pow(k, -1, 2 * N) for k in ks], np.uint32), np.ones(len(ks), np.uint32)
+
+
+def keygen_combine(ctx, a, e, s_new, n_keys=1, k_new=None, s_old=None, k_old=None, factor=None, ns=1, out=None, stream=None):
+    """fhe_keygen_combine over the limbs of `a`: a, e Towers [n_keys * nParts][nLimbs][N], s_new / s_old [1][nLimbs][N], factor
+    [nParts][nLimbs] (None: no s_old term); out: a Tower to write (e itself = in place), default a new one"""
+    n_parts, rem = divmod(a.batch, n_keys)
+    assert rem == 0 and e.batch == a.batch and e.n_limbs == a.n_limbs
+    kn, knp = _np_u32(k_new)
+    ko, kop = _np_u32(k_old)
+    f = fp = None
+    if factor is not None:
+        f = np.ascontiguousarray(np.asarray(factor, dtype=np.uint64))
+        assert f.shape == (n_parts, a.n_limbs)
+        fp = f.ctypes.data_as(u64p)
+    out = a.like() if out is None else out
+    ctx.lib.check(ctx.lib.L.fhe_keygen_combine(ctx.h, a._li(), a.n_limbs, n_keys, n_parts, a.ptr, e.ptr, s_new.ptr, knp,
+                                               None if s_old is None else s_old.ptr, kop, fp, ns, out.ptr, stream))
+    return out
+
+
+def public_key(ctx, s, a, e, ns=1, stream=None):
+    """PKEBase::KeyGenInternal (base-pke.cpp:47-98): b = ns * e - a * s for towers [batch][nLimbs][N] in EVALUATION format, one public
+    key per tower of the batch against the one secret s [1][nLimbs][N]; returns b (a is the other half)"""
+    return keygen_combine(ctx, a, e, s, n_keys=a.batch, ns=ns, stream=stream)
 
 
 def rescale(ctx, x, stream=None):

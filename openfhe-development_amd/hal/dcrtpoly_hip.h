@@ -1014,5 +1014,75 @@ private:
     size_t m_wsBytes       = 0;
 };
 
+// ---- evaluation keys made on the device (KeySwitchHYBRID::KeySwitchGenInternal, keyswitch-hybrid.cpp:51-130) ----
+// The two slabs of a key set, [nKeys * numPartQ][sizeQ+sizeP][N] in EVALUATION format, and one handle per key that fhe_ks_key_wrap laid
+// over its window of them: what the composites of KeySwitchHybrid / BfvHybrid take as `key`.  The handles die with the set.
+struct HybridKeySet {
+    DCRTPolyHip b, a;
+    std::vector<fhe_ks_key*> keys;
+    HybridKeySet(fhe_ks_plan* plan, DCRTPolyHip&& b_, DCRTPolyHip&& a_, uint32_t nKeys) : b(std::move(b_)), a(std::move(a_)) {
+        const size_t words = (size_t)b.GetBatch() / nKeys * b.GetNumOfElements() * b.GetRingDimension();
+        for (uint32_t k = 0; k < nKeys; ++k) {
+            fhe_ks_key* h = nullptr;
+            check(fhe_ks_key_wrap(plan, b.data() + k * words, a.data() + k * words, &h));
+            keys.push_back(h);
+        }
+    }
+    ~HybridKeySet() {
+        for (auto* k : keys)
+            fhe_ks_key_destroy(k);
+    }
+    HybridKeySet(const HybridKeySet&)            = delete;
+    HybridKeySet& operator=(const HybridKeySet&) = delete;
+};
+// the sNewExt block (:59-83): s over Q, EVALUATION -> Q u P (fhe_ks_secret_extend)
+inline DCRTPolyHip KeySwitchSecretExtend(KeySwitchHybrid& ks, const DCRTPolyHip& s, uint32_t sizeP) {
+    const auto& params = s.GetParams();
+    DCRTPolyHip out(params, s.GetNumOfElements() + sizeP, EVALUATION);
+    const size_t wsb = (size_t)s.GetRingDimension() * 8;
+    void* ws         = nullptr;
+    check(fhe_malloc(params->ctx(), wsb, &ws));
+    const fhe_status st = fhe_ks_secret_extend(ks.plan(), s.data(), out.data(), ws, wsb, nullptr);
+    fhe_stream_sync(params->ctx(), nullptr);
+    fhe_free(params->ctx(), ws);
+    check(st);
+    return out;
+}
+// nKeys = kNew.size() keys from the caller's a and e (both [nKeys * numPartQ][sizeQ+sizeP][N], EVALUATION); e's buffer becomes b.
+// key k switches sigma_kOld[k](sOld) to sigma_kNew[k](sNew): EvalMultKeyGen is (1, 1) with sOld = s * s, EvalAutomorphismKeyGen of the
+// automorphism index i is (i^-1 mod 2N, 1) with sOld = s (base-leveledshe.cpp:146-154, 336-379).  ns = GetNoiseScale().
+inline std::unique_ptr<HybridKeySet> KeyGenHybrid(KeySwitchHybrid& ks, const DCRTPolyHip& sNewExt, const DCRTPolyHip& sOld,
+                                                  const std::vector<uint32_t>& kNew, const std::vector<uint32_t>& kOld, uint64_t ns,
+                                                  DCRTPolyHip&& a, DCRTPolyHip&& e) {
+    if (kNew.empty() || kNew.size() != kOld.size())
+        throw Error("KeyGenHybrid: one automorphism index pair per key");
+    check(fhe_ks_keygen_hybrid(ks.plan(), (uint32_t)kNew.size(), kNew.data(), kOld.data(), sNewExt.data(), sOld.data(), ns, a.data(),
+                               e.data(), e.data(), nullptr));
+    return std::make_unique<HybridKeySet>(ks.plan(), std::move(e), std::move(a), (uint32_t)kNew.size());
+}
+// the seeded form (fhe_ks_keygen_hybrid_blake2): a = the uniform blake2 sampler's words from counterA, e = the Gaussian sampler's from
+// counterE; *nextA / *nextE, when given, receive the first counters the call did not use (fhe_ks_keygen_counters)
+inline std::unique_ptr<HybridKeySet> KeyGenHybridBlake2(KeySwitchHybrid& ks, uint32_t numPartQ, const DCRTPolyHip& sNewExt,
+                                                        const DCRTPolyHip& sOld, const std::vector<uint32_t>& kNew,
+                                                        const std::vector<uint32_t>& kOld, uint64_t ns, double sigma, const uint32_t key[16],
+                                                        uint64_t counterA, uint64_t counterE, uint64_t* nextA = nullptr,
+                                                        uint64_t* nextE = nullptr) {
+    if (kNew.empty() || kNew.size() != kOld.size())
+        throw Error("KeyGenHybridBlake2: one automorphism index pair per key");
+    const uint32_t nKeys = (uint32_t)kNew.size();
+    const auto& params   = sNewExt.GetParams();
+    DCRTPolyHip b(params, sNewExt.GetNumOfElements(), EVALUATION, nKeys * numPartQ), a(params, sNewExt.GetNumOfElements(), EVALUATION,
+                                                                                        nKeys * numPartQ);
+    check(fhe_ks_keygen_hybrid_blake2(ks.plan(), nKeys, kNew.data(), kOld.data(), sNewExt.data(), sOld.data(), ns, sigma, key, counterA,
+                                      counterE, b.data(), a.data(), nullptr));
+    uint64_t nA = 0, nE = 0;
+    check(fhe_ks_keygen_counters(ks.plan(), nKeys, &nA, &nE));
+    if (nextA)
+        *nextA = counterA + nA;
+    if (nextE)
+        *nextE = counterE + nE;
+    return std::make_unique<HybridKeySet>(ks.plan(), std::move(b), std::move(a), nKeys);
+}
+
 }  // namespace fhehip
 #endif
