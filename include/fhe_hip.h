@@ -343,6 +343,66 @@ fhe_status fhe_ks_keygen_hybrid_blake2(fhe_ks_plan* plan, uint32_t nKeys, const 
 /* blake2 counters fhe_ks_keygen_hybrid_blake2 consumes from counterA (*nA) and from counterE (*nE): lay out disjoint ranges with them */
 fhe_status fhe_ks_keygen_counters(const fhe_ks_plan* plan, uint32_t nKeys, uint64_t* nA, uint64_t* nE);
 
+/* ---- encryption on the device -------------------------------------------------------------------------
+ * fhe_encrypt_pk_combine / fhe_encrypt_sk_combine: everything of encryption that is not sampling or transforming, both elements of
+ * `batch` ciphertexts in ONE launch (csrc/encrypt_kernels.h).  For ciphertext t < batch, tower row i < nLimbs (context limb limbIdx[i],
+ * NULL = identity), word n, modulo q_i:
+ *   public key   c0[t][i][n] = pkB[i][n] * v[t][i][n] + ns * e0[t][i][n] (+ msg[t][i][n])
+ *                c1[t][i][n] = pkA[i][n] * v[t][i][n] + ns * e1[t][i][n]
+ *                PKERNS::EncryptZeroCore(publicKey) (src/pke/lib/schemerns/rns-pke.cpp:148-197) and `(*ba)[0] += plaintext` of
+ *                PKERNS::Encrypt (:56-70);
+ *   secret key   c0[t][i][n] = a[t][i][n] * s[i][n] + ns * e[t][i][n] (+ msg[t][i][n])
+ *                c1[t][i][n] = -a[t][i][n]
+ *                PKERNS::EncryptZeroCore(privateKey) (:111-146) and PKERNS::Encrypt (:40-54).
+ *   v, e0, e1, a, e, msg, c0, c1  DEVICE [batch][nLimbs][N]; pkB, pkA, s DEVICE [nLimbs][N] with row stride N: the first nLimbs rows of a
+ *              full-level key serve a plaintext with fewer limbs (DropLastElements on the clones, :129-135, :175-182); all EVALUATION
+ *              format, canonical residues in and out; msg may be NULL (EncryptZeroCore alone);
+ *   ns         GetNoiseScale(): 1 for CKKS and BFV, t for BGV; reduced modulo every limb (ns >= q_i is legal), 0 is refused.
+ * In place: c0 may be e0 (or e) itself and c1 may be e1 (or a) itself: every word is read by the lane that overwrites it.  Errors
+ * (FHE_ERR_ARG, nothing is enqueued, outputs untouched): a null operand, batch == 0, nLimbs == 0, a limb outside the context, ns == 0, a
+ * forbidden overlap (the key rows, msg or v against an output; v against e0 / e1; an output against an input other than its own; c0
+ * against c1).  ns goes through a table cached by content: the first call with a new ns != 1 uploads it (not capturable), later calls are
+ * pure launches.  A workgroup walks fhe_encrypt_chunk(ctx, nLimbs, batch) ciphertexts (1, 2, 4 or 8: as many as still leave four
+ * workgroups per compute unit) with its words of the key rows in registers; batch need not be a multiple of it. */
+fhe_status fhe_encrypt_pk_combine(fhe_ctx* ctx, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* pkB,
+                                  const uint64_t* pkA, const uint64_t* v, const uint64_t* e0, const uint64_t* e1, const uint64_t* msg,
+                                  uint64_t ns, uint64_t* c0, uint64_t* c1, void* stream);
+fhe_status fhe_encrypt_sk_combine(fhe_ctx* ctx, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* s,
+                                  const uint64_t* a, const uint64_t* e, const uint64_t* msg, uint64_t ns, uint64_t* c0, uint64_t* c1,
+                                  void* stream);
+uint32_t   fhe_encrypt_chunk(const fhe_ctx* ctx, uint32_t nLimbs, uint32_t batch);
+/* The seeded public-key form, defined as a composition.  ct DEVICE [2][batch][nLimbs][N]: the c0 block, then the c1 block; ws holds v,
+ * fhe_encrypt_workspace_bytes(ctx, nLimbs, batch) bytes:
+ *   v       = fhe_sample_ternary_blake2 (vDist = 0) or fhe_sample_gaussian_blake2 (vDist = 1: the reference's choice under
+ *             SecretKeyDist == GAUSSIAN, rns-pke.cpp:164-165) over batch towers from counterV, into ws;
+ *   e0 ‖ e1 = ONE fhe_sample_gaussian_blake2 over 2 * batch towers from counterE, into ct;
+ *   msg     with msgFormat 1 (COEFFICIENT) is added to the e0 block here with the kernel of fhe_add: one more launch, the path of
+ *             PKEBFVRNS::Encrypt with the STANDARD technique (src/pke/lib/scheme/bfvrns/bfvrns-pke.cpp:157-213: TimesQovert on the
+ *             COEFFICIENT plaintext, which is fhe_times_q_over_t, then `(*ba)[0] += ptxt`).  Legal only when ns = 1 modulo every limb
+ *             in use, since e0 is scaled by ns afterwards;
+ *   fhe_ntt_fwd, ONE call over 3 * batch towers when ws == ct + 2 * batch * nLimbs * N words, else one over ct and one over ws;
+ *   fhe_encrypt_pk_combine in place in ct, with msg when msgFormat is 0 (EVALUATION).
+ * With the contiguous workspace that is five launches on a two-pass ring (N >= 8192) whatever the batch is, six when the batched row pass
+ * of N = 2^16 / 2^17 takes towers in pairs and 3 * batch is odd.  e0, e1 and v never exist outside ct / ws.  The blake2 key travels by
+ * value; the first Gaussian call with a new sigma uploads its inversion table (not capturable).  Every argument is checked before the
+ * first launch: the errors of fhe_encrypt_pk_combine, sigma outside 1 < sigma < 300, an unknown vDist or msgFormat, a COEFFICIENT message
+ * with ns != 1 modulo some limb, a short workspace, ws overlapping ct, the public key or msg. */
+size_t     fhe_encrypt_workspace_bytes(const fhe_ctx* ctx, uint32_t nLimbs, uint32_t batch);
+fhe_status fhe_encrypt_pk_blake2(fhe_ctx* ctx, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* pkB,
+                                 const uint64_t* pkA, int vDist, uint64_t ns, double sigma, const uint32_t key[16], uint64_t counterV,
+                                 uint64_t counterE, const uint64_t* msg, int msgFormat, uint64_t* ct, void* ws, size_t wsBytes,
+                                 void* stream);
+/* The seeded secret-key form: a = the words of fhe_sample_uniform_blake2(batch, key, counterA) in the c1 block, used as drawn (the
+ * reference draws a in EVALUATION format, rns-pke.cpp:122); e = fhe_sample_gaussian_blake2(batch, sigma, key, counterE) in the c0 block
+ * (+ a COEFFICIENT msg, as above), then fhe_ntt_fwd there, then fhe_encrypt_sk_combine in place.  No workspace.  The c1 half is a function
+ * of (key, counterA) alone, as the a half of the evaluation keys is.  PKEBFVRNS::Encrypt(privateKey) is bfvrns-pke.cpp:99-155. */
+fhe_status fhe_encrypt_sk_blake2(fhe_ctx* ctx, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* s, uint64_t ns,
+                                 double sigma, const uint32_t key[16], uint64_t counterA, uint64_t counterE, const uint64_t* msg,
+                                 int msgFormat, uint64_t* ct, void* stream);
+/* blake2 counters a seeded call consumes: form 0 (public key): *nVorA from counterV, *nE from counterE (e0 ‖ e1 together); form 1 (secret
+ * key): *nVorA from counterA, *nE from counterE.  The arithmetic of fhe_ks_keygen_counters. */
+fhe_status fhe_encrypt_counters(const fhe_ctx* ctx, uint32_t nLimbs, uint32_t batch, int form, uint64_t* nVorA, uint64_t* nE);
+
 /* workspace (device bytes) needed by the composite calls below for `batch` towers at level sizeQl */
 size_t     fhe_ks_workspace_bytes(const fhe_ks_plan* plan, uint32_t sizeQl, uint32_t batch);
 

@@ -24,6 +24,7 @@
 #include "elemwise_kernels.h"
 #include "host_math.h"
 #include "keygen_kernels.h"
+#include "encrypt_kernels.h"
 #include "ntt_kernels.h"
 #include "ntt_static.h"
 #include "ntt_row8.h"
@@ -2948,6 +2949,227 @@ extern "C" fhe_status fhe_ks_keygen_hybrid_blake2(fhe_ks_plan* p, uint32_t nKeys
     if (fhe_status s = fhe_ntt_fwd(c, devKeyB, nullptr, sizeQP, towers, st))
         return s;
     return fhe_ks_keygen_hybrid(p, nKeys, kNew, kOld, sNewExt, sOld, ns, devKeyA, devKeyB, devKeyB, st);
+}
+
+// ---- encryption (encrypt_kernels.h) ----
+// PKERNS::EncryptZeroCore in both forms (rns-pke.cpp:111-197) with the `(*ba)[0] += plaintext` of PKERNS::Encrypt (:40-70) for any number
+// of ciphertexts: everything that is not sampling or transforming is ONE launch of encrypt_combine_kernel.  ns mod q_i goes through the
+// context's table cache (const_table), as the keygen combine's table does.
+struct EncryptOperands {
+    const uint64_t *k0, *k1;  // pkB, pkA | s, (unused)
+    const uint64_t *v, *e0, *e1;  // v, e0, e1 | a, e, (unused)
+    const uint64_t* msg;      // EVALUATION message or null
+    uint64_t *c0, *c1;
+};
+static uint32_t encrypt_tiles(const fhe_ctx* c) {
+    return c->logN > (uint32_t)kEncryptTileLog ? 1u << (c->logN - kEncryptTileLog) : 1u;
+}
+// ciphertexts per workgroup: the longest walk that leaves four workgroups (16 waves, four per SIMD) per compute unit
+static uint32_t encrypt_chunk_for(const fhe_ctx* c, uint32_t nLimbs, uint32_t batch) {
+    return encrypt_chunk((uint64_t)nLimbs * encrypt_tiles(c), batch, 4ull * (c->cus ? c->cus : 256));
+}
+// the checks every entry of the family shares, before anything is enqueued
+static fhe_status encrypt_check_shape(const std::string& who, const fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch,
+                                      uint64_t ns) {
+    ARG_CHECK(c, who + ": null argument");
+    ARG_CHECK(batch >= 1, who + ": batch must be >= 1");
+    ARG_CHECK(nLimbs >= 1 && nLimbs <= (uint32_t)kMaxLimbs, who + ": nLimbs out of range");
+    for (uint32_t i = 0; i < nLimbs; ++i)
+        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, who + ": limb index exceeds context size");
+    ARG_CHECK(ns != 0, who + ": the noise scale must not be zero");
+    ARG_CHECK((uint64_t)batch * nLimbs * encrypt_tiles(c) < ((uint64_t)1 << 31), who + ": batch * nLimbs too large");
+    return FHE_OK;
+}
+static fhe_status encrypt_check(const std::string& who, const fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch,
+                                bool sk, const EncryptOperands& o, uint64_t ns) {
+    ARG_CHECK(c && o.k0 && (sk || o.k1) && o.v && o.e0 && (sk || o.e1) && o.c0 && o.c1, who + ": null argument");
+    if (fhe_status s = encrypt_check_shape(who, c, limbIdx, nLimbs, batch, ns))
+        return s;
+    const size_t row = (size_t)c->N * 8, key = nLimbs * row, slab = (size_t)batch * key;
+    const uint64_t* in1 = sk ? o.v : o.e1;  // what c1 may be: e1, or a
+    ARG_CHECK(!keygen_overlap(o.c0, slab, o.c1, slab), who + ": c0 and c1 overlap");
+    ARG_CHECK(o.c0 == o.e0 || !keygen_overlap(o.c0, slab, o.e0, slab),
+              who + (sk ? ": c0 may be e itself but not overlap it otherwise" : ": c0 may be e0 itself but not overlap it otherwise"));
+    ARG_CHECK(o.c1 == in1 || !keygen_overlap(o.c1, slab, in1, slab),
+              who + (sk ? ": c1 may be a itself but not overlap it otherwise" : ": c1 may be e1 itself but not overlap it otherwise"));
+    ARG_CHECK(!keygen_overlap(o.c1, slab, o.e0, slab) && !keygen_overlap(o.c0, slab, in1, slab),
+              who + (sk ? ": c0 overlaps a or c1 overlaps e" : ": c0 overlaps e1 or c1 overlaps e0"));
+    if (!sk)
+        ARG_CHECK(!keygen_overlap(o.v, slab, o.e0, slab) && !keygen_overlap(o.v, slab, o.e1, slab) &&
+                      !keygen_overlap(o.v, slab, o.c0, slab) && !keygen_overlap(o.v, slab, o.c1, slab),
+                  who + ": v overlaps e0, e1 or an output");
+    for (const uint64_t* out : {o.c0, o.c1}) {
+        ARG_CHECK(!keygen_overlap(out, slab, o.k0, key) && !(!sk && keygen_overlap(out, slab, o.k1, key)),
+                  who + (sk ? ": an output overlaps s" : ": an output overlaps the public key"));
+        ARG_CHECK(!(o.msg && keygen_overlap(out, slab, o.msg, slab)), who + ": an output overlaps msg");
+    }
+    return FHE_OK;
+}
+// (the arguments have passed encrypt_check)
+static fhe_status encrypt_combine_run(const std::string& who, fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, bool sk,
+                                      const EncryptOperands& o, uint64_t ns, void* st) {
+    EncryptArgs g;
+    if (fhe_status s = make_sel(c, limbIdx, nLimbs, &g.sel, who.c_str()))
+        return s;
+    RT_CHECK(rt::set_device(c->device));
+    std::vector<uint32_t> li;
+    std::vector<uint64_t> v;
+    bool ns1 = true;  // ns = 1 modulo every limb in use (q_i > 1): no product at all
+    for (uint32_t i = 0; i < nLimbs; ++i) {
+        const uint32_t l = limbIdx ? limbIdx[i] : i;
+        li.push_back(l);
+        v.push_back(ns % c->q[l]);
+        ns1 = ns1 && v.back() == 1;
+    }
+    const TwPair* table = nullptr;
+    if (fhe_status s = const_tables_trim(c))
+        return s;
+    std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
+    if (!ns1)
+        if (fhe_status s = const_table(c, li.data(), v.data(), (uint32_t)v.size(), &table))
+            return s;
+    g.c0 = o.c0, g.c1 = o.c1, g.k0 = o.k0, g.k1 = sk ? o.k0 : o.k1, g.v = o.v, g.e0 = o.e0, g.e1 = sk ? o.e0 : o.e1, g.msg = o.msg;
+    g.lc = c->d_lc, g.tab = table, g.logN = c->logN, g.nLimbs = nLimbs, g.batch = batch;
+    g.chunk             = encrypt_chunk_for(c, nLimbs, batch);
+    const uint32_t grid = ((batch + g.chunk - 1) / g.chunk) * nLimbs * encrypt_tiles(c);
+#define ENCRYPT_LAUNCH(NS1, MSG)                                                   \
+    do {                                                                           \
+        if (sk)                                                                    \
+            FHE_LAUNCH((encrypt_combine_kernel<NS1, MSG, true>), grid, st, g);     \
+        else                                                                       \
+            FHE_LAUNCH((encrypt_combine_kernel<NS1, MSG, false>), grid, st, g);    \
+    } while (0)
+    if (ns1 && o.msg)
+        ENCRYPT_LAUNCH(true, true);
+    else if (ns1)
+        ENCRYPT_LAUNCH(true, false);
+    else if (o.msg)
+        ENCRYPT_LAUNCH(false, true);
+    else
+        ENCRYPT_LAUNCH(false, false);
+#undef ENCRYPT_LAUNCH
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+extern "C" uint32_t fhe_encrypt_chunk(const fhe_ctx* c, uint32_t nLimbs, uint32_t batch) {
+    return c && nLimbs && batch ? encrypt_chunk_for(c, nLimbs, batch) : 0;
+}
+extern "C" fhe_status fhe_encrypt_pk_combine(fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* pkB,
+                                             const uint64_t* pkA, const uint64_t* v, const uint64_t* e0, const uint64_t* e1,
+                                             const uint64_t* msg, uint64_t ns, uint64_t* c0, uint64_t* c1, void* st) {
+    const std::string who = "fhe_encrypt_pk_combine";
+    const EncryptOperands o{pkB, pkA, v, e0, e1, msg, c0, c1};
+    if (fhe_status s = encrypt_check(who, c, limbIdx, nLimbs, batch, false, o, ns))
+        return s;
+    return encrypt_combine_run(who, c, limbIdx, nLimbs, batch, false, o, ns, st);
+}
+extern "C" fhe_status fhe_encrypt_sk_combine(fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* s,
+                                             const uint64_t* a, const uint64_t* e, const uint64_t* msg, uint64_t ns, uint64_t* c0,
+                                             uint64_t* c1, void* st) {
+    const std::string who = "fhe_encrypt_sk_combine";
+    const EncryptOperands o{s, nullptr, a, e, nullptr, msg, c0, c1};
+    if (fhe_status r = encrypt_check(who, c, limbIdx, nLimbs, batch, true, o, ns))
+        return r;
+    return encrypt_combine_run(who, c, limbIdx, nLimbs, batch, true, o, ns, st);
+}
+extern "C" size_t fhe_encrypt_workspace_bytes(const fhe_ctx* c, uint32_t nLimbs, uint32_t batch) {
+    return c ? (((size_t)batch * nLimbs) << c->logN) * 8 : 0;
+}
+extern "C" fhe_status fhe_encrypt_counters(const fhe_ctx* c, uint32_t nLimbs, uint32_t batch, int form, uint64_t* nVorA, uint64_t* nE) {
+    ARG_CHECK(c && nVorA && nE, "fhe_encrypt_counters: null argument");
+    ARG_CHECK(batch >= 1 && nLimbs >= 1, "fhe_encrypt_counters: batch and nLimbs must be >= 1");
+    ARG_CHECK(form == 0 || form == 1, "fhe_encrypt_counters: form is 0 (public key) or 1 (secret key)");
+    const uint64_t coef = (uint64_t)batch << c->logN;
+    if (form == 0) {
+        *nVorA = (coef + 511) / 512;      // one word per coefficient of v
+        *nE    = (2 * coef + 511) / 512;  // e0 || e1: ONE sampler call over 2 * batch towers
+    } else {
+        *nVorA = (coef * nLimbs + 255) / 256;  // two 64-bit words per uniform residue
+        *nE    = (coef + 511) / 512;
+    }
+    return FHE_OK;
+}
+// what the two seeded forms check alike
+static fhe_status encrypt_check_seeded(const std::string& who, const fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch,
+                                       uint64_t ns, double sigma, const uint32_t* key, const uint64_t* msg, int msgFormat) {
+    ARG_CHECK(key, who + ": null argument");
+    if (fhe_status s = encrypt_check_shape(who, c, limbIdx, nLimbs, batch, ns))
+        return s;
+    ARG_CHECK(sigma > 1.000000001 && sigma < 300.0, who + ": the inversion sampler covers 1 < sigma < 300 (the reference's Peikert range)");
+    ARG_CHECK(msgFormat == 0 || msgFormat == 1, who + ": msgFormat is 0 (EVALUATION) or 1 (COEFFICIENT)");
+    if (msg && msgFormat == 1)
+        for (uint32_t i = 0; i < nLimbs; ++i)
+            ARG_CHECK(ns % c->q[limbIdx ? limbIdx[i] : i] == 1,
+                      who + ": a COEFFICIENT message joins e before the noise scale is applied: ns must be 1 modulo every limb");
+    return FHE_OK;
+}
+// the seeded public-key form, a composition: v and e0 || e1 from the blake2 samplers, one forward transform when the workspace follows
+// ct (two otherwise), one combine in place.  Every argument is checked before the first launch.
+extern "C" fhe_status fhe_encrypt_pk_blake2(fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* pkB,
+                                            const uint64_t* pkA, int vDist, uint64_t ns, double sigma, const uint32_t key[16],
+                                            uint64_t counterV, uint64_t counterE, const uint64_t* msg, int msgFormat, uint64_t* ct,
+                                            void* ws, size_t wsBytes, void* st) {
+    const std::string who = "fhe_encrypt_pk_blake2";
+    ARG_CHECK(c && pkB && pkA && ct && ws, who + ": null argument");
+    if (fhe_status s = encrypt_check_seeded(who, c, limbIdx, nLimbs, batch, ns, sigma, key, msg, msgFormat))
+        return s;
+    ARG_CHECK(vDist == 0 || vDist == 1, who + ": vDist is 0 (ternary) or 1 (Gaussian)");
+    const size_t words = ((size_t)batch * nLimbs) << c->logN, slab = words * 8, keyBytes = ((size_t)nLimbs << c->logN) * 8;
+    ARG_CHECK(wsBytes >= fhe_encrypt_workspace_bytes(c, nLimbs, batch), who + ": workspace too small");
+    uint64_t* v = (uint64_t*)ws;
+    ARG_CHECK(!keygen_overlap(v, slab, ct, 2 * slab), who + ": the workspace overlaps ct");
+    ARG_CHECK(!keygen_overlap(v, slab, pkB, keyBytes) && !keygen_overlap(v, slab, pkA, keyBytes) && !(msg && keygen_overlap(v, slab, msg, slab)),
+              who + ": the workspace overlaps the public key or msg");
+    const uint64_t* evalMsg = msg && msgFormat == 0 ? msg : nullptr;
+    const EncryptOperands o{pkB, pkA, v, ct, ct + words, msg, ct, ct + words};  // (msg, whatever its format, must stay clear of ct)
+    if (fhe_status s = encrypt_check(who, c, limbIdx, nLimbs, batch, false, o, ns))
+        return s;
+    if (fhe_status s = vDist == 0 ? fhe_sample_ternary_blake2(c, v, limbIdx, nLimbs, batch, key, counterV, st)
+                                  : fhe_sample_gaussian_blake2(c, v, limbIdx, nLimbs, batch, sigma, key, counterV, st))
+        return s;
+    if (fhe_status s = fhe_sample_gaussian_blake2(c, ct, limbIdx, nLimbs, 2 * batch, sigma, key, counterE, st))
+        return s;
+    if (msg && msgFormat == 1)
+        if (fhe_status s = fhe_add(c, ct, ct, msg, limbIdx, nLimbs, batch, st))
+            return s;
+    if (v == ct + 2 * words) {
+        if (fhe_status s = fhe_ntt_fwd(c, ct, limbIdx, nLimbs, 3 * batch, st))
+            return s;
+    } else {
+        if (fhe_status s = fhe_ntt_fwd(c, ct, limbIdx, nLimbs, 2 * batch, st))
+            return s;
+        if (fhe_status s = fhe_ntt_fwd(c, v, limbIdx, nLimbs, batch, st))
+            return s;
+    }
+    EncryptOperands run = o;
+    run.msg             = evalMsg;
+    return encrypt_combine_run(who, c, limbIdx, nLimbs, batch, false, run, ns, st);
+}
+// the seeded secret-key form: a = the uniform sampler's words in the c1 block, used as drawn (the reference draws a in EVALUATION format);
+// e = the Gaussian sampler's words in the c0 block, transformed there; one combine in place.  No workspace.
+extern "C" fhe_status fhe_encrypt_sk_blake2(fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch, const uint64_t* sKey,
+                                            uint64_t ns, double sigma, const uint32_t key[16], uint64_t counterA, uint64_t counterE,
+                                            const uint64_t* msg, int msgFormat, uint64_t* ct, void* st) {
+    const std::string who = "fhe_encrypt_sk_blake2";
+    ARG_CHECK(c && sKey && ct, who + ": null argument");
+    if (fhe_status s = encrypt_check_seeded(who, c, limbIdx, nLimbs, batch, ns, sigma, key, msg, msgFormat))
+        return s;
+    const size_t words = ((size_t)batch * nLimbs) << c->logN;
+    const EncryptOperands o{sKey, nullptr, ct + words, ct, nullptr, msg, ct, ct + words};
+    if (fhe_status s = encrypt_check(who, c, limbIdx, nLimbs, batch, true, o, ns))
+        return s;
+    if (fhe_status s = fhe_sample_uniform_blake2(c, ct + words, limbIdx, nLimbs, batch, key, counterA, st))
+        return s;
+    if (fhe_status s = fhe_sample_gaussian_blake2(c, ct, limbIdx, nLimbs, batch, sigma, key, counterE, st))
+        return s;
+    if (msg && msgFormat == 1)
+        if (fhe_status s = fhe_add(c, ct, ct, msg, limbIdx, nLimbs, batch, st))
+            return s;
+    if (fhe_status s = fhe_ntt_fwd(c, ct, limbIdx, nLimbs, batch, st))
+        return s;
+    EncryptOperands run = o;
+    run.msg             = msg && msgFormat == 0 ? msg : nullptr;
+    return encrypt_combine_run(who, c, limbIdx, nLimbs, batch, true, run, ns, st);
 }
 
 // ---- BSGS plaintext-matrix product with double hoisting ----

@@ -139,6 +139,14 @@ class Lib:
         S("fhe_ks_keygen_hybrid", C.c_int, [vp, u32, u32p, u32p, vp, vp, u64, vp, vp, vp, vp])
         S("fhe_ks_keygen_hybrid_blake2", C.c_int, [vp, u32, u32p, u32p, vp, vp, u64, C.c_double, u32p, u64, u64, vp, vp, vp])
         S("fhe_ks_keygen_counters", C.c_int, [vp, u32, u64p, u64p])
+        S("fhe_encrypt_pk_combine", C.c_int, [vp, u32p, u32, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp])
+        S("fhe_encrypt_sk_combine", C.c_int, [vp, u32p, u32, u32, vp, vp, vp, vp, u64, vp, vp, vp])
+        S("fhe_encrypt_chunk", u32, [vp, u32, u32])
+        S("fhe_encrypt_workspace_bytes", C.c_size_t, [vp, u32, u32])
+        S("fhe_encrypt_pk_blake2", C.c_int,
+          [vp, u32p, u32, u32, vp, vp, C.c_int, u64, C.c_double, u32p, u64, u64, vp, C.c_int, vp, vp, C.c_size_t, vp])
+        S("fhe_encrypt_sk_blake2", C.c_int, [vp, u32p, u32, u32, vp, u64, C.c_double, u32p, u64, u64, vp, C.c_int, vp, vp])
+        S("fhe_encrypt_counters", C.c_int, [vp, u32, u32, C.c_int, u64p, u64p])
         S("fhe_ks_workspace_bytes", C.c_size_t, [vp, u32, u32])
         S("fhe_keyswitch_hybrid", C.c_int, [vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_keyswitch_hybrid_acc", C.c_int, [vp, vp, vp, u32, u32, vp, vp, vp, C.c_size_t, vp])
@@ -1035,6 +1043,111 @@ def public_key(ctx, s, a, e, ns=1, stream=None):
     """PKEBase::KeyGenInternal (base-pke.cpp:47-98): b = ns * e - a * s for towers [batch][nLimbs][N] in EVALUATION format, one public
     key per tower of the batch against the one secret s [1][nLimbs][N]; returns b (a is the other half)"""
     return keygen_combine(ctx, a, e, s, n_keys=a.batch, ns=ns, stream=stream)
+
+
+TERNARY, GAUSSIAN = 0, 1  # vDist of encrypt_pk_blake2: the distribution of v (SecretKeyDist != GAUSSIAN / == GAUSSIAN, rns-pke.cpp:164-165)
+PUBLIC_KEY, SECRET_KEY = 0, 1  # form of encrypt_counters
+
+
+def _window(t, first, batch):
+    """towers [first, first + batch) of the Tower t, not owned"""
+    return Tower(t.ctx, vp(t.ptr.value + 8 * first * t.n_limbs * t.ctx.N), batch, t.n_limbs, t.limb_idx, t.fmt)
+
+
+def encrypt_pk_combine(ctx, pk_b, pk_a, v, e0, e1, msg=None, ns=1, in_place=False, stream=None):
+    """fhe_encrypt_pk_combine over the limbs of v: c0 = pkB * v + ns * e0 (+ msg), c1 = pkA * v + ns * e1 for Towers [batch][nLimbs][N] in
+    EVALUATION format; pk_b, pk_a [1][>= nLimbs][N] (their first nLimbs rows are used).  Returns (c0, c1): new Towers, or e0 and e1
+    themselves with in_place"""
+    assert e0.batch == v.batch == e1.batch and e0.n_limbs == v.n_limbs == e1.n_limbs and pk_b.n_limbs >= v.n_limbs <= pk_a.n_limbs
+    c0, c1 = (e0, e1) if in_place else (e0.like(), e1.like())
+    ctx.lib.check(ctx.lib.L.fhe_encrypt_pk_combine(ctx.h, v._li(), v.n_limbs, v.batch, pk_b.ptr, pk_a.ptr, v.ptr, e0.ptr, e1.ptr,
+                                                   None if msg is None else msg.ptr, ns, c0.ptr, c1.ptr, stream))
+    return c0, c1
+
+
+def encrypt_sk_combine(ctx, s, a, e, msg=None, ns=1, in_place=False, stream=None):
+    """fhe_encrypt_sk_combine over the limbs of a: c0 = a * s + ns * e (+ msg), c1 = -a; s [1][>= nLimbs][N].  Returns (c0, c1): new
+    Towers, or e and a themselves with in_place"""
+    assert e.batch == a.batch and e.n_limbs == a.n_limbs <= s.n_limbs
+    c0, c1 = (e, a) if in_place else (e.like(), a.like())
+    ctx.lib.check(ctx.lib.L.fhe_encrypt_sk_combine(ctx.h, a._li(), a.n_limbs, a.batch, s.ptr, a.ptr, e.ptr, None if msg is None else msg.ptr,
+                                                   ns, c0.ptr, c1.ptr, stream))
+    return c0, c1
+
+
+def encrypt_counters(ctx, n_limbs, batch, form=PUBLIC_KEY):
+    """(blake2 counters a seeded call consumes from counter_v or counter_a, from counter_e) (fhe_encrypt_counters)"""
+    n0, ne = C.c_uint64(), C.c_uint64()
+    ctx.lib.check(ctx.lib.L.fhe_encrypt_counters(ctx.h, n_limbs, batch, form, C.byref(n0), C.byref(ne)))
+    return n0.value, ne.value
+
+
+def encrypt_pk_blake2(ctx, pk_b, pk_a, batch, key, counter_v, counter_e, n_limbs=None, limb_idx=None, msg=None, ns=1, sigma=3.19,
+                      v_dist=TERNARY, contiguous=True, stream=None):
+    """fhe_encrypt_pk_blake2: `batch` fresh ciphertexts under the public key (pk_b, pk_a) at the level of n_limbs rows (default: the
+    key's), v from counter_v and e0 ‖ e1 from counter_e of the blake2 key; msg: a Tower [batch][nLimbs][N] in either format, or None.
+    contiguous: the workspace follows the ciphertexts in one allocation (one forward transform instead of two).  Returns (c0, c1), windows
+    of one Tower that c0 owns."""
+    n_limbs = pk_b.n_limbs if n_limbs is None else n_limbs
+    li = pk_b.limb_idx if limb_idx is None else limb_idx
+    wsb = ctx.lib.L.fhe_encrypt_workspace_bytes(ctx.h, n_limbs, batch)
+    ct = ctx.empty((3 if contiguous else 2) * batch, n_limbs, li)
+    ws = spare = vp(ct.ptr.value + 2 * wsb) if contiguous else ctx.malloc(wsb + 16)
+    if not contiguous and ws.value == ct.ptr.value + 2 * wsb:  # the allocator put it right behind ct: step off, "apart" is what was asked for
+        ws = vp(spare.value + 16)
+    k = _key_words(key)
+    try:
+        ctx.lib.check(ctx.lib.L.fhe_encrypt_pk_blake2(ctx.h, ct._li(), n_limbs, batch, pk_b.ptr, pk_a.ptr, v_dist, ns, sigma,
+                                                      k.ctypes.data_as(u32p), counter_v, counter_e, None if msg is None else msg.ptr,
+                                                      EVALUATION if msg is None else msg.fmt, ct.ptr, ws, wsb, stream))
+        ctx.sync(stream)
+    finally:
+        if not contiguous:
+            ctx.free(spare)
+    c0, c1 = _window(ct, 0, batch), _window(ct, batch, batch)
+    c0._keep = c1._keep = ct
+    return c0, c1
+
+
+def encrypt_sk_blake2(ctx, s, batch, key, counter_a, counter_e, n_limbs=None, limb_idx=None, msg=None, ns=1, sigma=3.19, stream=None):
+    """fhe_encrypt_sk_blake2: `batch` fresh ciphertexts under the secret key s, a from counter_a (the c1 half is minus the uniform
+    sampler's words) and e from counter_e.  Returns (c0, c1) as encrypt_pk_blake2 does."""
+    n_limbs = s.n_limbs if n_limbs is None else n_limbs
+    ct = ctx.empty(2 * batch, n_limbs, s.limb_idx if limb_idx is None else limb_idx)
+    k = _key_words(key)
+    ctx.lib.check(ctx.lib.L.fhe_encrypt_sk_blake2(ctx.h, ct._li(), n_limbs, batch, s.ptr, ns, sigma, k.ctypes.data_as(u32p), counter_a,
+                                                  counter_e, None if msg is None else msg.ptr, EVALUATION if msg is None else msg.fmt,
+                                                  ct.ptr, stream))
+    c0, c1 = _window(ct, 0, batch), _window(ct, batch, batch)
+    c0._keep = c1._keep = ct
+    return c0, c1
+
+
+def _bfv_scaled(ctx, ptxt, t, neg_q_mod_t, t_inv_mod_q, stream):
+    """DCRTPoly::TimesQovert (dcrtpoly-impl.h:868-885) of a COEFFICIENT plaintext Tower: the message PKEBFVRNS::Encrypt adds"""
+    assert ptxt.fmt == COEFFICIENT
+    tinv = np.ascontiguousarray(np.asarray(t_inv_mod_q, dtype=np.uint64))
+    out = ptxt.like()
+    ctx.lib.check(ctx.lib.L.fhe_times_q_over_t(ctx.h, out.ptr, ptxt.ptr, t, neg_q_mod_t, tinv.ctypes.data_as(u64p), ptxt._li(),
+                                               ptxt.n_limbs, ptxt.batch, stream))
+    return out
+
+
+def bfv_encrypt_pk_blake2(ctx, pk_b, pk_a, ptxt, t, neg_q_mod_t, t_inv_mod_q, key, counter_v, counter_e, sigma=3.19, v_dist=TERNARY,
+                          contiguous=True, stream=None):
+    """PKEBFVRNS::Encrypt(ptxt, publicKey) with the STANDARD encryption technique (bfvrns-pke.cpp:157-213): fhe_times_q_over_t on the
+    COEFFICIENT plaintext Tower [batch][sizeQl][N] (neg_q_mod_t = GetNegQModt(level), t_inv_mod_q = GettInvModq()), then the seeded call
+    with the scaled message in COEFFICIENT format (it joins e0 before the forward transform)"""
+    m = _bfv_scaled(ctx, ptxt, t, neg_q_mod_t, t_inv_mod_q, stream)
+    return encrypt_pk_blake2(ctx, pk_b, pk_a, ptxt.batch, key, counter_v, counter_e, n_limbs=ptxt.n_limbs, limb_idx=ptxt.limb_idx, msg=m,
+                             sigma=sigma, v_dist=v_dist, contiguous=contiguous, stream=stream)
+
+
+def bfv_encrypt_sk_blake2(ctx, s, ptxt, t, neg_q_mod_t, t_inv_mod_q, key, counter_a, counter_e, sigma=3.19, stream=None):
+    """PKEBFVRNS::Encrypt(ptxt, privateKey), STANDARD (bfvrns-pke.cpp:99-155), as bfv_encrypt_pk_blake2"""
+    m = _bfv_scaled(ctx, ptxt, t, neg_q_mod_t, t_inv_mod_q, stream)
+    return encrypt_sk_blake2(ctx, s, ptxt.batch, key, counter_a, counter_e, n_limbs=ptxt.n_limbs, limb_idx=ptxt.limb_idx, msg=m,
+                             sigma=sigma, stream=stream)
 
 
 def rescale(ctx, x, stream=None):

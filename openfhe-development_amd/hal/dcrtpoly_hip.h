@@ -1084,5 +1084,96 @@ inline std::unique_ptr<HybridKeySet> KeyGenHybridBlake2(KeySwitchHybrid& ks, uin
     return std::make_unique<HybridKeySet>(ks.plan(), std::move(b), std::move(a), nKeys);
 }
 
+// ---- encryption on the device (PKERNS::EncryptZeroCore + Encrypt, rns-pke.cpp:40-70, 111-197; PKEBFVRNS::Encrypt, bfvrns-pke.cpp:99-213)
+// All towers over the leading context limbs.  The key towers may have more rows than the plaintext's level: their first rows are used.
+// `batch` fresh ciphertexts in one slab [2][batch][sizeQl][N], EVALUATION: the c0 block, then the c1 block (what the seeded calls fill).
+struct FreshCiphertexts {
+    DCRTPolyHip ct;  // [2 * batch (+ batch of workspace behind them)][sizeQl][N]
+    uint32_t batch;
+    size_t blockWords() const { return (size_t)batch * ct.GetNumOfElements() * ct.GetRingDimension(); }
+    uint64_t* c0() { return ct.data(); }
+    uint64_t* c1() { return ct.data() + blockWords(); }
+    std::vector<uint64_t> GetValues(int element) const {  // [batch][sizeQl][N] of c0 (0) or c1 (1)
+        const std::vector<uint64_t> all = ct.GetValues();
+        return std::vector<uint64_t>(all.begin() + element * blockWords(), all.begin() + (element + 1) * blockWords());
+    }
+};
+// c0 = pkB * v + ns * e0 (+ msg), c1 = pkA * v + ns * e1 with the caller's randomness, in place: returns {e0's buffer, e1's buffer}
+inline std::pair<DCRTPolyHip, DCRTPolyHip> EncryptPk(const DCRTPolyHip& pkB, const DCRTPolyHip& pkA, const DCRTPolyHip& v, DCRTPolyHip&& e0,
+                                                      DCRTPolyHip&& e1, const DCRTPolyHip* msg, uint64_t ns) {
+    if (pkB.GetNumOfElements() < v.GetNumOfElements() || pkA.GetNumOfElements() < v.GetNumOfElements())
+        throw Error("EncryptPk: the public key has fewer towers than the plaintext");
+    check(fhe_encrypt_pk_combine(v.GetParams()->ctx(), nullptr, v.GetNumOfElements(), v.GetBatch(), pkB.data(), pkA.data(), v.data(),
+                                 e0.data(), e1.data(), msg ? msg->data() : nullptr, ns, e0.data(), e1.data(), nullptr));
+    return {std::move(e0), std::move(e1)};
+}
+// c0 = a * s + ns * e (+ msg), c1 = -a, in place: returns {e's buffer, a's buffer}
+inline std::pair<DCRTPolyHip, DCRTPolyHip> EncryptSk(const DCRTPolyHip& s, DCRTPolyHip&& a, DCRTPolyHip&& e, const DCRTPolyHip* msg,
+                                                      uint64_t ns) {
+    if (s.GetNumOfElements() < a.GetNumOfElements())
+        throw Error("EncryptSk: the secret key has fewer towers than the plaintext");
+    check(fhe_encrypt_sk_combine(a.GetParams()->ctx(), nullptr, a.GetNumOfElements(), a.GetBatch(), s.data(), a.data(), e.data(),
+                                 msg ? msg->data() : nullptr, ns, e.data(), a.data(), nullptr));
+    return {std::move(e), std::move(a)};
+}
+// the seeded forms; msg: [batch][sizeQl][N] in either format (COEFFICIENT needs ns = 1 modulo every limb) or null; gaussianV: v from the
+// Gaussian sampler (SecretKeyDist == GAUSSIAN); *nextV / *nextA, *nextE: the first counters the call did not use (fhe_encrypt_counters)
+inline FreshCiphertexts EncryptPkBlake2(const DCRTPolyHip& pkB, const DCRTPolyHip& pkA, uint32_t sizeQl, uint32_t batch, bool gaussianV,
+                                        uint64_t ns, double sigma, const uint32_t key[16], uint64_t counterV, uint64_t counterE,
+                                        const DCRTPolyHip* msg = nullptr, uint64_t* nextV = nullptr, uint64_t* nextE = nullptr) {
+    const auto& params = pkB.GetParams();
+    FreshCiphertexts out{DCRTPolyHip(params, sizeQl, EVALUATION, 3 * batch), batch};  // the workspace follows ct: one forward transform
+    const size_t wsb = fhe_encrypt_workspace_bytes(params->ctx(), sizeQl, batch);
+    check(fhe_encrypt_pk_blake2(params->ctx(), nullptr, sizeQl, batch, pkB.data(), pkA.data(), gaussianV ? 1 : 0, ns, sigma, key, counterV,
+                                counterE, msg ? msg->data() : nullptr, msg ? (int)msg->GetFormat() : 0, out.ct.data(),
+                                out.ct.data() + 2 * out.blockWords(), wsb, nullptr));
+    uint64_t nV = 0, nE = 0;
+    check(fhe_encrypt_counters(params->ctx(), sizeQl, batch, 0, &nV, &nE));
+    if (nextV)
+        *nextV = counterV + nV;
+    if (nextE)
+        *nextE = counterE + nE;
+    return out;
+}
+inline FreshCiphertexts EncryptSkBlake2(const DCRTPolyHip& s, uint32_t sizeQl, uint32_t batch, uint64_t ns, double sigma,
+                                        const uint32_t key[16], uint64_t counterA, uint64_t counterE, const DCRTPolyHip* msg = nullptr,
+                                        uint64_t* nextA = nullptr, uint64_t* nextE = nullptr) {
+    const auto& params = s.GetParams();
+    FreshCiphertexts out{DCRTPolyHip(params, sizeQl, EVALUATION, 2 * batch), batch};
+    check(fhe_encrypt_sk_blake2(params->ctx(), nullptr, sizeQl, batch, s.data(), ns, sigma, key, counterA, counterE,
+                                msg ? msg->data() : nullptr, msg ? (int)msg->GetFormat() : 0, out.ct.data(), nullptr));
+    uint64_t nA = 0, nE = 0;
+    check(fhe_encrypt_counters(params->ctx(), sizeQl, batch, 1, &nA, &nE));
+    if (nextA)
+        *nextA = counterA + nA;
+    if (nextE)
+        *nextE = counterE + nE;
+    return out;
+}
+// DCRTPoly::TimesQovert (dcrtpoly-impl.h:868-885) of a COEFFICIENT plaintext: the message of PKEBFVRNS::Encrypt with the STANDARD technique
+inline DCRTPolyHip BfvScaledMessage(const DCRTPolyHip& ptxt, uint64_t t, uint64_t negQModt, const std::vector<uint64_t>& tInvModq) {
+    if (ptxt.GetFormat() != COEFFICIENT)
+        throw Error("BfvScaledMessage: COEFFICIENT format expected");
+    if (tInvModq.size() < ptxt.GetNumOfElements())
+        throw Error("BfvScaledMessage: one tInvModq residue per limb expected");
+    DCRTPolyHip m(ptxt.GetParams(), ptxt.GetNumOfElements(), COEFFICIENT, ptxt.GetBatch());
+    check(fhe_times_q_over_t(ptxt.GetParams()->ctx(), m.data(), ptxt.data(), t, negQModt, tInvModq.data(), nullptr, ptxt.GetNumOfElements(),
+                             ptxt.GetBatch(), nullptr));
+    return m;
+}
+// PKEBFVRNS::Encrypt(ptxt, publicKey / privateKey), STANDARD: negQModt = GetNegQModt(level), tInvModq = GettInvModq()
+inline FreshCiphertexts BfvEncryptPkBlake2(const DCRTPolyHip& pkB, const DCRTPolyHip& pkA, const DCRTPolyHip& ptxt, uint64_t t,
+                                           uint64_t negQModt, const std::vector<uint64_t>& tInvModq, bool gaussianV, double sigma,
+                                           const uint32_t key[16], uint64_t counterV, uint64_t counterE) {
+    const DCRTPolyHip m = BfvScaledMessage(ptxt, t, negQModt, tInvModq);
+    return EncryptPkBlake2(pkB, pkA, ptxt.GetNumOfElements(), ptxt.GetBatch(), gaussianV, 1, sigma, key, counterV, counterE, &m);
+}
+inline FreshCiphertexts BfvEncryptSkBlake2(const DCRTPolyHip& s, const DCRTPolyHip& ptxt, uint64_t t, uint64_t negQModt,
+                                           const std::vector<uint64_t>& tInvModq, double sigma, const uint32_t key[16], uint64_t counterA,
+                                           uint64_t counterE) {
+    const DCRTPolyHip m = BfvScaledMessage(ptxt, t, negQModt, tInvModq);
+    return EncryptSkBlake2(s, ptxt.GetNumOfElements(), ptxt.GetBatch(), 1, sigma, key, counterA, counterE, &m);
+}
+
 }  // namespace fhehip
 #endif
