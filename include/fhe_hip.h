@@ -403,6 +403,62 @@ fhe_status fhe_encrypt_sk_blake2(fhe_ctx* ctx, const uint32_t* limbIdx, uint32_t
  * key): *nVorA from counterA, *nE from counterE.  The arithmetic of fhe_ks_keygen_counters. */
 fhe_status fhe_encrypt_counters(const fhe_ctx* ctx, uint32_t nLimbs, uint32_t batch, int form, uint64_t* nVorA, uint64_t* nE);
 
+/* ---- decryption on the device -------------------------------------------------------------------------
+ * fhe_decrypt_core: PKERNS::DecryptCore (src/pke/lib/schemerns/rns-pke.cpp:199-225) for `batch` ciphertexts in ONE launch
+ * (csrc/decrypt_kernels.h).  For ciphertext t < batch, tower row i < nLimbs (context limb limbIdx[i], NULL = identity), word n, modulo q_i:
+ *   b[t][i][n] = [c[0][t][i][n]] + s[i][n] * c[1][t][i][n] + s[i][n]^2 * c[2][t][i][n] + s[i][n]^3 * c[3][t][i][n] [+ ns * noise[t][i][n]]
+ * evaluated by Horner: the words of the reference's loop `b += sPower * cv[i]; sPower *= s`, without a tower of s^2.
+ *   c        HOST array of nElem (2, 3 or 4) DEVICE pointers, element e of all ciphertexts [batch][nLimbs][N];
+ *   s        DEVICE, ONE tower [nLimbs][N] with row stride N: the first nLimbs rows of a full-level key serve a lower-level ciphertext
+ *            (DropLastElements on the copy of the key, :203-206);
+ *   noise    DEVICE [batch][nLimbs][N] or NULL.  With ns = 1 it is CKKS's `b += noise` under NOISE_FLOODING_DECRYPT
+ *            (src/pke/lib/scheme/ckksrns/ckksrns-pke.cpp:49-54, 75-80); with nElem = 2 it is the flooding term of
+ *            MultipartyDecryptLead (withC0 = 1: `cv[0] + s * cv[1] + ns * e`) and MultipartyDecryptMain (withC0 = 0: `s * cv[1] + ns * e`;
+ *            c[0] is not read and may be NULL) (src/pke/lib/schemerns/rns-multiparty.cpp:46-171);
+ *   ns       reduced modulo every limb through a table cached by content, as in fhe_encrypt_*_combine: the first call with a new
+ *            ns != 1 uploads it (not capturable), later calls are pure launches; ns == 0 with a noise tower is refused;
+ *   outFormat 0 (EVALUATION): exactly one launch.  1 (COEFFICIENT): that launch, then fhe_ntt_inv on out.  With nLimbs > 1 the
+ *            COEFFICIENT tower is what PKECKKSRNS::Decrypt(.., Poly*) hands to CRTInterpolate (ckksrns-pke.cpp:70-96); with one limb
+ *            it is the NativePoly of :44-68.  Interpolation and decoding stay on the host.
+ * All towers EVALUATION on entry, canonical residues in and out.  In place: out may be c[0] itself or the noise tower itself (every word
+ * is read by the lane that overwrites it); any other overlap is refused.  Errors (FHE_ERR_ARG, nothing is enqueued, out untouched): a
+ * null operand, nElem outside [2, 4], withC0 == 0 with nElem != 2, batch == 0, nLimbs == 0, a limb outside the context, ns == 0 with
+ * noise, an unknown outFormat, a forbidden overlap.  A workgroup walks fhe_decrypt_chunk(ctx, nLimbs, batch) ciphertexts (1, 2, 4 or 8, the
+ * choice of fhe_encrypt_chunk) with its words of s in registers; batch need not be a multiple of it. */
+fhe_status fhe_decrypt_core(fhe_ctx* ctx, const uint64_t* const* c, uint32_t nElem, const uint64_t* s, const uint32_t* limbIdx,
+                            uint32_t nLimbs, uint32_t batch, const uint64_t* noise, uint64_t ns, int withC0, int outFormat,
+                            uint64_t* out, void* stream);
+uint32_t   fhe_decrypt_chunk(const fhe_ctx* ctx, uint32_t nLimbs, uint32_t batch);
+/* PKEBFVRNS::Decrypt at sizeQl == sizeQ (src/pke/lib/scheme/bfvrns/bfvrns-pke.cpp:215-245) as a plan over the context limbs
+ * limbIdx[sizeQ] (NULL = the leading limbs), the plaintext modulus t and a technique: 0 BEHZ, 1 HPS, 2 HPSPOVERQ, 3 HPSPOVERQLEVELED (the
+ * three HPS techniques decrypt alike).  Every table is derived on the host from the moduli and t and kept on the device:
+ *   HPS   tQHatInvModqDivqModt, tQHatInvModqDivqFrac and, when qMSB + sizeQMSB >= 52, tQHatInvModqBDivqModt, tQHatInvModqBDivqFrac
+ *         (src/pke/lib/scheme/bfvrns/bfvrns-cryptoparameters.cpp:434-484; the Frac tables as double(numerator) / double(denominator), as there);
+ *   BEHZ  tgamma, tgammaQHatInvModq, negInvqModtgamma with gamma = 2^26 (:851-882); t >= 2^32 is FHE_ERR_UNSUPPORTED.
+ * fhe_bfv_decrypt_table reads one back: ids 0 tQHatInvModqDivqModt, 1 tQHatInvModqBDivqModt, 2 tQHatInvModqDivqFrac, 3
+ * tQHatInvModqBDivqFrac (doubles as their 64 bits), 4 tgamma (one word), 5 tgammaQHatInvModq, 6 negInvqModtgamma; returns the number of
+ * words (0: the plan has no such table) and copies min(that, cap) of them.
+ * fhe_bfv_decrypt: c[nElem] and s as for fhe_decrypt_core over the plan's limbs -> out DEVICE [batch][N], the NativePoly words modulo t.
+ * The combine into ws, ONE inverse transform of all limbs of all towers, then the kernel of fhe_scale_and_round_native or
+ * fhe_scale_and_round_behz_decrypt with the plan's tables: four launches on a two-pass ring (N >= 8192) for any batch and any nElem.
+ * ws: fhe_bfv_decrypt_workspace_bytes(plan, batch) = batch * sizeQ * N words.
+ * fhe_bfv_decrypt_b: the tail alone on a b [batch][sizeQ][N] the caller holds, what MultipartyBFVRNS::MultipartyDecryptFusion runs after
+ * its sum (src/pke/lib/scheme/bfvrns/bfvrns-multiparty.cpp:139-175).  evalFormat != 0: b is EVALUATION and is transformed out of place
+ * into ws; b is only read.  evalFormat == 0: b is COEFFICIENT, ws is not used and may be NULL.
+ * After creation the calls allocate nothing and do not wait for the device.  Errors, each before anything is enqueued (FHE_ERR_ARG, outputs
+ * untouched): those of fhe_decrypt_core; equal moduli in the plan; t < 2; an unknown technique; a short workspace; out overlapping an
+ * input or ws; ws overlapping an input.  The compressed-ciphertext branch of the member (sizeQl != sizeQ, :246-268) has no entry here: a
+ * plan decrypts at its own sizeQ only. */
+typedef struct fhe_bfv_dec fhe_bfv_dec;
+fhe_status fhe_bfv_decrypt_create(fhe_ctx* ctx, const uint32_t* limbIdx, uint32_t sizeQ, uint64_t t, int technique, fhe_bfv_dec** out);
+void       fhe_bfv_decrypt_destroy(fhe_bfv_dec* plan);
+size_t     fhe_bfv_decrypt_workspace_bytes(const fhe_bfv_dec* plan, uint32_t batch);
+size_t     fhe_bfv_decrypt_table(const fhe_bfv_dec* plan, int tableId, uint64_t* out, size_t cap);
+fhe_status fhe_bfv_decrypt(fhe_bfv_dec* plan, const uint64_t* const* c, uint32_t nElem, const uint64_t* s, uint32_t batch, uint64_t* out,
+                           void* ws, size_t wsBytes, void* stream);
+fhe_status fhe_bfv_decrypt_b(fhe_bfv_dec* plan, const uint64_t* b, int evalFormat, uint32_t batch, uint64_t* out, void* ws,
+                             size_t wsBytes, void* stream);
+
 /* workspace (device bytes) needed by the composite calls below for `batch` towers at level sizeQl */
 size_t     fhe_ks_workspace_bytes(const fhe_ks_plan* plan, uint32_t sizeQl, uint32_t batch);
 

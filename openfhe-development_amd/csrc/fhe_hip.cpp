@@ -25,6 +25,7 @@
 #include "host_math.h"
 #include "keygen_kernels.h"
 #include "encrypt_kernels.h"
+#include "decrypt_kernels.h"
 #include "ntt_kernels.h"
 #include "ntt_static.h"
 #include "ntt_row8.h"
@@ -4577,6 +4578,312 @@ extern "C" fhe_status fhe_scale_and_round_behz_decrypt(fhe_ctx* c, const uint64_
     rt::dfree(dT), rt::dfree(dQ);
     RT_CHECK(le);
     return FHE_OK;
+}
+
+// ---- decryption on the device (decrypt_kernels.h) ----
+// PKERNS::DecryptCore (rns-pke.cpp:199-225), CKKS's `b += noise` and the element arithmetic of MultipartyDecryptLead / Main
+// (rns-multiparty.cpp:46-171) for any number of ciphertexts: ONE launch of decrypt_combine_kernel.  ns mod q_i goes through the context's
+// table cache (const_table), as the encrypt combine's table does.
+struct DecryptOperands {
+    const uint64_t* const* c;  // host array [nElem]
+    uint32_t nElem;
+    const uint64_t *s, *noise;
+    uint64_t ns;
+    bool withC0;
+    uint64_t* out;
+};
+static uint32_t decrypt_chunk_for(const fhe_ctx* c, uint32_t nLimbs, uint32_t batch) {
+    return decrypt_chunk((uint64_t)nLimbs * encrypt_tiles(c), batch, 4ull * (c->cus ? c->cus : 256));
+}
+// every check of the combine, before anything is enqueued
+static fhe_status decrypt_check(const std::string& who, const fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch,
+                                const DecryptOperands& o) {
+    ARG_CHECK(c && o.c && o.s && o.out, who + ": null argument");
+    ARG_CHECK(o.nElem >= 2 && o.nElem <= (uint32_t)kDecryptMaxElems, who + ": a ciphertext of 2 to 4 elements expected");
+    ARG_CHECK(o.withC0 || o.nElem == 2, who + ": without c0 (MultipartyDecryptMain) a ciphertext has 2 elements");
+    for (uint32_t e = o.withC0 ? 0 : 1; e < o.nElem; ++e)
+        ARG_CHECK(o.c[e], who + ": null argument");
+    ARG_CHECK(batch >= 1, who + ": batch must be >= 1");
+    ARG_CHECK(nLimbs >= 1 && nLimbs <= (uint32_t)kMaxLimbs, who + ": nLimbs out of range");
+    for (uint32_t i = 0; i < nLimbs; ++i)
+        ARG_CHECK((limbIdx ? limbIdx[i] : i) < c->L, who + ": limb index exceeds context size");
+    ARG_CHECK(!(o.noise && o.ns == 0), who + ": the noise scale must not be zero");
+    ARG_CHECK((uint64_t)batch * nLimbs * encrypt_tiles(c) < ((uint64_t)1 << 31), who + ": batch * nLimbs too large");
+    const size_t row = (size_t)c->N * 8, key = nLimbs * row, slab = (size_t)batch * key;
+    ARG_CHECK(!keygen_overlap(o.out, slab, o.s, key), who + ": out overlaps s");
+    for (uint32_t e = o.withC0 ? 0 : 1; e < o.nElem; ++e)
+        ARG_CHECK((e == 0 && o.out == o.c[0]) || !keygen_overlap(o.out, slab, o.c[e], slab),
+                  who + ": out may be c[0] itself but not overlap an element otherwise");
+    ARG_CHECK(!o.noise || o.out == o.noise || !keygen_overlap(o.out, slab, o.noise, slab),
+              who + ": out may be the noise tower itself but not overlap it otherwise");
+    return FHE_OK;
+}
+// (the arguments have passed decrypt_check)
+static fhe_status decrypt_combine_run(const std::string& who, fhe_ctx* c, const uint32_t* limbIdx, uint32_t nLimbs, uint32_t batch,
+                                      const DecryptOperands& o, void* st) {
+    DecryptArgs g;
+    if (fhe_status s = make_sel(c, limbIdx, nLimbs, &g.sel, who.c_str()))
+        return s;
+    RT_CHECK(rt::set_device(c->device));
+    std::vector<uint32_t> li;
+    std::vector<uint64_t> v;
+    bool ns1 = true;  // ns = 1 modulo every limb in use: no product at all
+    for (uint32_t i = 0; i < nLimbs; ++i) {
+        const uint32_t l = limbIdx ? limbIdx[i] : i;
+        li.push_back(l);
+        v.push_back(o.ns % c->q[l]);
+        ns1 = ns1 && v.back() == 1;
+    }
+    const TwPair* table = nullptr;
+    if (fhe_status s = const_tables_trim(c))
+        return s;
+    std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
+    if (o.noise && !ns1)
+        if (fhe_status s = const_table(c, li.data(), v.data(), (uint32_t)v.size(), &table))
+            return s;
+    for (uint32_t e = 0; e < (uint32_t)kDecryptMaxElems; ++e)
+        g.c[e] = e < o.nElem && o.c[e] ? o.c[e] : o.c[1];
+    g.out = o.out, g.s = o.s, g.noise = o.noise, g.lc = c->d_lc, g.tab = table;
+    g.logN = c->logN, g.nLimbs = nLimbs, g.batch = batch;
+    g.chunk             = decrypt_chunk_for(c, nLimbs, batch);
+    const uint32_t grid = ((batch + g.chunk - 1) / g.chunk) * nLimbs * encrypt_tiles(c);
+    const int noise     = !o.noise ? kDecryptNoNoise : ns1 ? kDecryptNoiseNs1 : kDecryptNoiseScaled;
+#define DECRYPT_LAUNCH(NELEM, C0)                                                                       \
+    do {                                                                                                \
+        if (noise == kDecryptNoNoise)                                                                   \
+            FHE_LAUNCH((decrypt_combine_kernel<NELEM, C0, kDecryptNoNoise>), grid, st, g);              \
+        else if (noise == kDecryptNoiseNs1)                                                             \
+            FHE_LAUNCH((decrypt_combine_kernel<NELEM, C0, kDecryptNoiseNs1>), grid, st, g);             \
+        else                                                                                            \
+            FHE_LAUNCH((decrypt_combine_kernel<NELEM, C0, kDecryptNoiseScaled>), grid, st, g);          \
+    } while (0)
+    if (!o.withC0)
+        DECRYPT_LAUNCH(2, false);
+    else if (o.nElem == 2)
+        DECRYPT_LAUNCH(2, true);
+    else if (o.nElem == 3)
+        DECRYPT_LAUNCH(3, true);
+    else
+        DECRYPT_LAUNCH(4, true);
+#undef DECRYPT_LAUNCH
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+extern "C" uint32_t fhe_decrypt_chunk(const fhe_ctx* c, uint32_t nLimbs, uint32_t batch) {
+    return c && nLimbs && batch ? decrypt_chunk_for(c, nLimbs, batch) : 0;
+}
+extern "C" fhe_status fhe_decrypt_core(fhe_ctx* c, const uint64_t* const* ct, uint32_t nElem, const uint64_t* s, const uint32_t* limbIdx,
+                                       uint32_t nLimbs, uint32_t batch, const uint64_t* noise, uint64_t ns, int withC0, int outFormat,
+                                       uint64_t* out, void* st) {
+    const std::string who = "fhe_decrypt_core";
+    const DecryptOperands o{ct, nElem, s, noise, ns, withC0 != 0, out};
+    if (fhe_status r = decrypt_check(who, c, limbIdx, nLimbs, batch, o))
+        return r;
+    ARG_CHECK(outFormat == 0 || outFormat == 1, who + ": outFormat is 0 (EVALUATION) or 1 (COEFFICIENT)");
+    if (fhe_status r = decrypt_combine_run(who, c, limbIdx, nLimbs, batch, o, st))
+        return r;
+    return outFormat == 1 ? fhe_ntt_inv(c, out, limbIdx, nLimbs, batch, st) : FHE_OK;
+}
+
+// PKEBFVRNS::Decrypt at sizeQl == sizeQ (bfvrns-pke.cpp:215-245) as a plan: the tables of CryptoParametersBFVRNS's "Decrypt : ScaleAndRound"
+// block (bfvrns-cryptoparameters.cpp:434-484) or of its BEHZ "Decrns" block (:851-882), derived here from the moduli and t and kept on the
+// device, so that a call is the combine, one inverse transform and one launch of the scaling kernel, with no allocation and no wait.
+struct fhe_bfv_dec {
+    fhe_ctx* ctx;
+    uint32_t sizeQ;
+    int technique;
+    std::vector<uint32_t> idx;
+    ScaleRoundNativeArgs g;  // everything but in, out and batch
+    std::map<int, std::vector<uint64_t>> tables;
+    std::vector<void*> owned;
+};
+namespace {
+// a^-1 mod m for any m > 1 with gcd(a, m) = 1 (extended Euclid; 0 when there is none)
+uint64_t inv_mod_any(uint64_t a, uint64_t m) {
+    __int128 r0 = m, r1 = a % m, t0 = 0, t1 = 1;
+    while (r1) {
+        const __int128 qq = r0 / r1, r2 = r0 - qq * r1, t2 = t0 - qq * t1;
+        r0 = r1, r1 = r2, t0 = t1, t1 = t2;
+    }
+    if (r0 != 1)
+        return 0;
+    return (uint64_t)(t0 < 0 ? t0 + m : t0);
+}
+uint64_t double_bits(double d) {
+    uint64_t u;
+    std::memcpy(&u, &d, 8);
+    return u;
+}
+}  // namespace
+extern "C" void fhe_bfv_decrypt_destroy(fhe_bfv_dec* p) {
+    if (!p)
+        return;
+    for (void* q : p->owned)
+        rt::dfree(q);
+    delete p;
+}
+extern "C" fhe_status fhe_bfv_decrypt_create(fhe_ctx* c, const uint32_t* limbIdx, uint32_t sizeQ, uint64_t t, int technique,
+                                             fhe_bfv_dec** out) {
+    const std::string who = "fhe_bfv_decrypt_create";
+    ARG_CHECK(c && out, who + ": null argument");
+    ARG_CHECK(technique >= 0 && technique <= 3, who + ": technique must be BEHZ (0), HPS (1), HPSPOVERQ (2) or HPSPOVERQLEVELED (3)");
+    ARG_CHECK(sizeQ >= 1 && sizeQ <= (uint32_t)kMaxLimbs, who + ": sizeQ out of range");
+    ARG_CHECK(t >= 2, who + ": bad plaintext modulus");
+    std::vector<uint64_t> q(sizeQ);
+    std::vector<uint32_t> idx(sizeQ);
+    for (uint32_t i = 0; i < sizeQ; ++i) {
+        idx[i] = limbIdx ? limbIdx[i] : i;
+        ARG_CHECK(idx[i] < c->L, who + ": limb index exceeds context size");
+        q[i] = c->q[idx[i]];
+        for (uint32_t k = 0; k < i; ++k)
+            ARG_CHECK(q[k] != q[i], who + ": the moduli of a tower must be distinct");
+    }
+    const uint64_t gamma = 1ull << 26;  // m_gamma (bfvrns-cryptoparameters.cpp:851-857: t * gamma < 2^58)
+    if (technique == 0 && t >= (1ull << 32))
+        return fail(FHE_ERR_UNSUPPORTED, who + ": BEHZ decryption needs t * 2^26 < 2^58");
+    RT_CHECK(rt::set_device(c->device));
+    fhe_bfv_dec* p = new fhe_bfv_dec;
+    p->ctx = c, p->sizeQ = sizeQ, p->technique = technique, p->idx = idx;
+    ScaleRoundNativeArgs& g = p->g;
+    g = ScaleRoundNativeArgs{};
+    g.logN = c->logN, g.sizeQ = sizeQ;
+    std::vector<TwPair> h(2 * (size_t)sizeQ, TwPair{0, 0});
+    fhe_status s = FHE_OK;
+    if (technique != 0) {
+        const uint64_t qmax = *std::max_element(q.begin(), q.end());
+        const uint32_t qMSB = msb64(qmax), tMSB = msb64(t), sizeQMSB = msb64(sizeQ);
+        g.t = t, g.qMSBHf = qMSB >> 1;
+        g.pow2  = (t & (t - 1)) == 0 ? 1u : 0u;
+        g.split = (qMSB + sizeQMSB < 52) ? 0u : 1u;
+        if (!g.split)
+            g.nomod = g.pow2 ? (qMSB + sizeQMSB + tMSB < 63) : (qMSB + tMSB + sizeQMSB < 52);
+        else
+            g.nomod = g.pow2 ? (g.qMSBHf + tMSB + sizeQMSB < 62) : (g.qMSBHf + tMSB + sizeQMSB < 52);
+        std::vector<uint64_t> modt(sizeQ), frac(sizeQ), bmodt, bfrac;
+        std::vector<double> fr(2 * (size_t)sizeQ, 0.0);
+        if (g.split)
+            bmodt.resize(sizeQ), bfrac.resize(sizeQ);
+        for (uint32_t i = 0; i < sizeQ; ++i) {
+            // v = t * [(Q/q_i)^-1]_{q_i} = a * q_i + r, below 2^124
+            const uint64_t qi   = q[i];
+            const host::u128 v  = (host::u128)host::invmod(host::prod_mod(q, (int)i, qi), qi) * t;
+            const host::u128 a  = v / qi;
+            const uint64_t r    = (uint64_t)(v % qi);
+            modt[i]             = (uint64_t)(a % t);
+            fr[i]               = static_cast<double>((int64_t)r) / static_cast<double>((int64_t)qi);  // :454-456
+            frac[i]             = double_bits(fr[i]);
+            h[i]                = TwPair{modt[i], host::shoup(modt[i], t)};
+            if (g.split) {  // (v << qMSBHf) = (a << qMSBHf) * q_i + (r << qMSBHf), r << qMSBHf below 2^90
+                const host::u128 rs = (host::u128)r << g.qMSBHf;
+                const uint64_t hi   = host::mulmod((uint64_t)(a % t), host::powmod(2, g.qMSBHf, t), t);
+                bmodt[i]            = (uint64_t)(((host::u128)hi + (uint64_t)((rs / qi) % t)) % t);
+                fr[sizeQ + i]       = static_cast<double>((int64_t)(uint64_t)(rs % qi)) / static_cast<double>((int64_t)qi);  // :481-482
+                bfrac[i]            = double_bits(fr[sizeQ + i]);
+                h[sizeQ + i]        = TwPair{bmodt[i], host::shoup(bmodt[i], t)};
+            }
+        }
+        p->tables[0] = modt, p->tables[2] = frac;
+        if (g.split)
+            p->tables[1] = bmodt, p->tables[3] = bfrac;
+        double* dF = nullptr;
+        s          = dev_copy(&p->owned, fr.data(), fr.size(), &dF);
+        g.frac = dF, g.bfrac = dF ? dF + sizeQ : nullptr;
+    } else {
+        const uint64_t tgamma = t * gamma;
+        g.t                   = tgamma;
+        std::vector<uint64_t> a(sizeQ), b(sizeQ);
+        for (uint32_t i = 0; i < sizeQ; ++i) {
+            const uint64_t qi = q[i], inv = inv_mod_any(qi % tgamma, tgamma);
+            if (!inv) {
+                fhe_bfv_decrypt_destroy(p);
+                return fail(FHE_ERR_ARG, who + ": every modulus must be invertible modulo t * 2^26");
+            }
+            b[i] = host::mulmod(tgamma - 1, inv, tgamma);  // [-1/q_i]_{t*gamma}, :857-867
+            a[i] = host::mulmod(host::mulmod(host::invmod(host::prod_mod(q, (int)i, qi), qi), gamma % qi, qi), t % qi, qi);  // :869-882
+            h[i] = TwPair{a[i], host::shoup(a[i], qi)}, h[sizeQ + i] = TwPair{b[i], host::shoup(b[i], tgamma)};
+        }
+        p->tables[4] = std::vector<uint64_t>(1, tgamma), p->tables[5] = a, p->tables[6] = b;
+        uint64_t* dQ = nullptr;
+        s            = dev_copy(&p->owned, q.data(), q.size(), &dQ);
+        g.q          = dQ;
+    }
+    TwPair* dT = nullptr;
+    if (!s)
+        s = dev_copy(&p->owned, h.data(), h.size(), &dT);
+    if (s) {
+        fhe_bfv_decrypt_destroy(p);
+        return s;
+    }
+    g.tabModt = dT, g.tabBModt = dT + sizeQ;
+    *out = p;
+    return FHE_OK;
+}
+// ids: 0 tQHatInvModqDivqModt, 1 tQHatInvModqBDivqModt, 2 tQHatInvModqDivqFrac, 3 tQHatInvModqBDivqFrac (doubles, as their 64 bits),
+// 4 tgamma (one word), 5 tgammaQHatInvModq, 6 negInvqModtgamma; [sizeQ] each.  Returns the number of words of the table (0: no such table for
+// this plan: the B tables on the unsplit branch, the other technique's); copies min(that, cap) words into out.
+extern "C" size_t fhe_bfv_decrypt_table(const fhe_bfv_dec* p, int tableId, uint64_t* out, size_t cap) {
+    if (!p)
+        return 0;
+    auto it = p->tables.find(tableId);
+    if (it == p->tables.end())
+        return 0;
+    if (out && cap)
+        std::memcpy(out, it->second.data(), std::min(cap, it->second.size()) * 8);
+    return it->second.size();
+}
+extern "C" size_t fhe_bfv_decrypt_workspace_bytes(const fhe_bfv_dec* p, uint32_t batch) {
+    return p ? (((size_t)batch * p->sizeQ) << p->ctx->logN) * 8 : 0;
+}
+// the scaling kernel on a COEFFICIENT b [batch][sizeQ][N]
+static fhe_status bfv_decrypt_tail(const fhe_bfv_dec* p, const uint64_t* b, uint32_t batch, uint64_t* out, void* st) {
+    ScaleRoundNativeArgs g = p->g;
+    g.in = TowerView{const_cast<uint64_t*>(b), p->sizeQ, 0}, g.out = out, g.batch = batch;
+    const uint32_t grid = (uint32_t)((((uint64_t)batch << g.logN) + kThreads - 1) / kThreads);
+    if (p->technique != 0)
+        FHE_LAUNCH(scale_round_native_kernel, grid, st, g);
+    else
+        FHE_LAUNCH(scale_round_behz_decrypt_kernel, grid, st, g);
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+extern "C" fhe_status fhe_bfv_decrypt(fhe_bfv_dec* p, const uint64_t* const* ct, uint32_t nElem, const uint64_t* s, uint32_t batch,
+                                      uint64_t* out, void* wsv, size_t wsBytes, void* st) {
+    const std::string who = "fhe_bfv_decrypt";
+    ARG_CHECK(p && out && wsv, who + ": null argument");
+    fhe_ctx* c = p->ctx;
+    uint64_t* b = (uint64_t*)wsv;
+    const DecryptOperands o{ct, nElem, s, nullptr, 1, true, b};
+    if (fhe_status r = decrypt_check(who, c, p->idx.data(), p->sizeQ, batch, o))
+        return r;
+    const size_t slab = fhe_bfv_decrypt_workspace_bytes(p, batch), res = ((size_t)batch << c->logN) * 8;
+    ARG_CHECK(wsBytes >= slab, who + ": workspace too small");
+    ARG_CHECK(!keygen_overlap(out, res, b, slab) && !keygen_overlap(out, res, s, slab / batch), who + ": out overlaps the workspace or s");
+    for (uint32_t e = 0; e < nElem; ++e)
+        ARG_CHECK(!keygen_overlap(out, res, ct[e], slab) && ct[e] != b, who + ": out or the workspace overlaps an element");
+    RT_CHECK(rt::set_device(c->device));
+    if (fhe_status r = decrypt_combine_run(who, c, p->idx.data(), p->sizeQ, batch, o, st))
+        return r;
+    if (fhe_status r = fhe_ntt_inv(c, b, p->idx.data(), p->sizeQ, batch, st))  // b.SetFormat(COEFFICIENT), every limb of every tower at once
+        return r;
+    return bfv_decrypt_tail(p, b, batch, out, st);
+}
+extern "C" fhe_status fhe_bfv_decrypt_b(fhe_bfv_dec* p, const uint64_t* b, int evalFormat, uint32_t batch, uint64_t* out, void* wsv,
+                                        size_t wsBytes, void* st) {
+    const std::string who = "fhe_bfv_decrypt_b";
+    ARG_CHECK(p && b && out && (wsv || !evalFormat), who + ": null argument");
+    ARG_CHECK(batch >= 1, who + ": batch must be >= 1");
+    fhe_ctx* c = p->ctx;
+    const size_t slab = fhe_bfv_decrypt_workspace_bytes(p, batch), res = ((size_t)batch << c->logN) * 8;
+    ARG_CHECK(!keygen_overlap(out, res, b, slab), who + ": out overlaps b");
+    RT_CHECK(rt::set_device(c->device));
+    if (evalFormat) {
+        ARG_CHECK(wsBytes >= slab, who + ": workspace too small");
+        ARG_CHECK(!keygen_overlap(wsv, slab, b, slab) && !keygen_overlap(wsv, slab, out, res), who + ": the workspace overlaps b or out");
+        if (fhe_status r = fhe_ntt_inv_oop(c, b, (uint64_t*)wsv, p->idx.data(), p->sizeQ, batch, st))
+            return r;
+        b = (const uint64_t*)wsv;
+    }
+    return bfv_decrypt_tail(p, b, batch, out, st);
 }
 
 // ---- BEHZ ----

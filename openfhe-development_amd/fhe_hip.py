@@ -192,6 +192,14 @@ class Lib:
         S("fhe_mod_reduce_to_t", C.c_int, [vp, vp, u32p, u32, u64, u32, vp, vp, C.c_size_t, vp])
         S("fhe_bgv_decrypt_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
         S("fhe_bgv_decrypt", C.c_int, [vp, C.POINTER(vp), u32, vp, u32p, u32, u64, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_decrypt_core", C.c_int, [vp, C.POINTER(vp), u32, vp, u32p, u32, u32, vp, u64, C.c_int, C.c_int, vp, vp])
+        S("fhe_decrypt_chunk", u32, [vp, u32, u32])
+        S("fhe_bfv_decrypt_create", C.c_int, [vp, u32p, u32, u64, C.c_int, C.POINTER(vp)])
+        S("fhe_bfv_decrypt_destroy", None, [vp])
+        S("fhe_bfv_decrypt_workspace_bytes", C.c_size_t, [vp, u32])
+        S("fhe_bfv_decrypt_table", C.c_size_t, [vp, C.c_int, u64p, C.c_size_t])
+        S("fhe_bfv_decrypt", C.c_int, [vp, C.POINTER(vp), u32, vp, u32, vp, vp, C.c_size_t, vp])
+        S("fhe_bfv_decrypt_b", C.c_int, [vp, vp, C.c_int, u32, vp, vp, C.c_size_t, vp])
         S("fhe_bgv_keyswitch_hybrid", C.c_int, [vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_bgv_keyswitch_hybrid_acc", C.c_int, [vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_bgv_eval_mult", C.c_int, [vp, vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, C.c_size_t, vp])
@@ -1561,6 +1569,93 @@ def bgv_decrypt(ctx, elements, s, t, stream=None):
     finally:
         ctx.free(d)
         ctx.free(ws)
+
+
+def _elem_ptrs(elements):
+    """C array of the elements' device pointers (NULL for None)"""
+    return (vp * len(elements))(*[None if e is None else e.ptr.value if hasattr(e.ptr, "value") else e.ptr for e in elements])
+
+
+def decrypt_chunk(ctx, n_limbs, batch):
+    """ciphertexts a workgroup of the decrypt combine walks (fhe_decrypt_chunk)"""
+    return ctx.lib.L.fhe_decrypt_chunk(ctx.h, n_limbs, batch)
+
+
+def decrypt_core(ctx, elements, s, noise=None, ns=1, with_c0=True, out_format=EVALUATION, out=None, stream=None):
+    """PKERNS::DecryptCore (rns-pke.cpp:199-225) through fhe_decrypt_core: elements = 2 to 4 EVALUATION Towers [batch][nLimbs][N]
+    (elements[0] may be None with with_c0=False: MultipartyDecryptMain), s [1][>= nLimbs][N] (its first nLimbs rows are used), noise a
+    Tower like the elements or None.  Returns b in out_format: a new Tower, or `out` (which may be elements[0] or noise)."""
+    c1 = elements[1]
+    assert s.n_limbs >= c1.n_limbs
+    b = c1.like() if out is None else out
+    ctx.lib.check(ctx.lib.L.fhe_decrypt_core(ctx.h, _elem_ptrs(elements), len(elements), s.ptr, c1._li(), c1.n_limbs, c1.batch,
+                                             None if noise is None else noise.ptr, ns, 1 if with_c0 else 0, out_format, b.ptr, stream))
+    b.fmt = out_format
+    return b
+
+
+def ckks_decrypt(ctx, elements, s, noise=None, stream=None):
+    """PKECKKSRNS::Decrypt up to the interpolation (ckksrns-pke.cpp:44-96): the COEFFICIENT tower of b as uint64 [batch][nLimbs][N] on the
+    host (one limb: the NativePoly; more: what CRTInterpolate takes).  noise: the flooding term of NOISE_FLOODING_DECRYPT, EVALUATION."""
+    return decrypt_core(ctx, elements, s, noise=noise, out_format=COEFFICIENT, stream=stream).to_host()
+
+
+class BfvDecrypt:
+    """PKEBFVRNS::Decrypt at sizeQl == sizeQ (bfvrns-pke.cpp:215-245) with tables derived from the moduli and t (fhe_bfv_decrypt_create)."""
+
+    BEHZ, HPS, HPSPOVERQ, HPSPOVERQLEVELED = 0, 1, 2, 3
+    TABLES = ("tQHatInvModqDivqModt", "tQHatInvModqBDivqModt", "tQHatInvModqDivqFrac", "tQHatInvModqBDivqFrac", "tgamma",
+              "tgammaQHatInvModq", "negInvqModtgamma")
+
+    def __init__(self, ctx, t, technique=HPS, limb_idx=None, size_q=None):
+        self.ctx, self.t, self.technique = ctx, t, technique
+        self.limb_idx = None if limb_idx is None else np.ascontiguousarray(np.asarray(limb_idx, dtype=np.uint32))
+        self.sizeQ = (ctx.L if size_q is None else size_q) if limb_idx is None else len(self.limb_idx)
+        h = vp()
+        ctx.lib.check(ctx.lib.L.fhe_bfv_decrypt_create(ctx.h, None if limb_idx is None else self.limb_idx.ctypes.data_as(u32p), self.sizeQ,
+                                                       t, technique, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.L.fhe_bfv_decrypt_destroy(self.h)
+            self.h = None
+
+    def table(self, name):
+        """a derived table as a flat uint64 array (the Frac tables as bit patterns: .view(np.float64)); None if the plan has none"""
+        tid = self.TABLES.index(name) if isinstance(name, str) else int(name)
+        n = self.ctx.lib.L.fhe_bfv_decrypt_table(self.h, tid, None, 0)
+        if n == 0:
+            return None
+        out = np.zeros(n, np.uint64)
+        self.ctx.lib.L.fhe_bfv_decrypt_table(self.h, tid, out.ctypes.data_as(u64p), n)
+        return out
+
+    def workspace_bytes(self, batch):
+        return self.ctx.lib.L.fhe_bfv_decrypt_workspace_bytes(self.h, batch)
+
+    def _run(self, batch, call, stream):
+        ctx, need = self.ctx, self.workspace_bytes(batch)
+        ws, d = ctx.malloc(max(need, 8)), ctx.malloc(batch * ctx.N * 8)
+        try:
+            ctx.lib.check(call(d, ws, need))
+            return ctx.download(d, (batch, ctx.N), stream)
+        finally:
+            ctx.free(d)
+            ctx.free(ws)
+
+    def Decrypt(self, elements, s, stream=None):
+        """elements: 2 to 4 EVALUATION Towers [batch][sizeQ][N], s the secret key [1][sizeQ][N]; returns the NativePoly words modulo t,
+        uint64 [batch][N]"""
+        L, batch = self.ctx.lib.L, elements[0].batch
+        return self._run(batch, lambda d, ws, need: L.fhe_bfv_decrypt(self.h, _elem_ptrs(elements), len(elements), s.ptr, batch, d, ws,
+                                                                      need, stream), stream)
+
+    def DecryptB(self, b, stream=None):
+        """the tail alone on a Tower b [batch][sizeQ][N] in either format (MultipartyDecryptFusion after its sum); b is only read"""
+        L = self.ctx.lib.L
+        return self._run(b.batch, lambda d, ws, need: L.fhe_bfv_decrypt_b(self.h, b.ptr, 1 if b.fmt == EVALUATION else 0, b.batch, d, ws,
+                                                                          need, stream), stream)
 
 
 def scale_and_round_native(ctx, x, t, tab_modt, frac, tab_bmodt=None, bfrac=None, stream=None):

@@ -1175,5 +1175,97 @@ inline FreshCiphertexts BfvEncryptSkBlake2(const DCRTPolyHip& s, const DCRTPolyH
     return EncryptSkBlake2(s, ptxt.GetNumOfElements(), ptxt.GetBatch(), 1, sigma, key, counterA, counterE, &m);
 }
 
+// ---- decryption on the device (PKERNS::DecryptCore, rns-pke.cpp:199-225; MultipartyDecryptLead / Main, rns-multiparty.cpp:46-171;
+// PKEBFVRNS::Decrypt, bfvrns-pke.cpp:215-245).  All towers over the leading context limbs; the key may have more rows than the ciphertext.
+// b = [c0] + s * c1 + s^2 * c2 + s^3 * c3 [+ ns * noise] for 2 to 4 EVALUATION elements [batch][sizeQl][N] in one launch, in outFormat
+// (COEFFICIENT: what PKECKKSRNS::Decrypt interpolates, ckksrns-pke.cpp:44-96).  withC0 = false (two elements, elements[0] may be null) is
+// MultipartyDecryptMain.  noise: the flooding term, EVALUATION, or null.
+inline DCRTPolyHip DecryptCore(const std::vector<const DCRTPolyHip*>& elements, const DCRTPolyHip& s, const DCRTPolyHip* noise = nullptr,
+                               uint64_t ns = 1, bool withC0 = true, Format outFormat = EVALUATION) {
+    if (elements.size() < 2 || !elements[1])
+        throw Error("DecryptCore: a ciphertext of 2 to 4 elements expected");
+    const DCRTPolyHip& c1 = *elements[1];
+    std::vector<const uint64_t*> ptrs;
+    for (const DCRTPolyHip* e : elements) {
+        if (e && (e->GetNumOfElements() != c1.GetNumOfElements() || e->GetBatch() != c1.GetBatch() || e->GetFormat() != EVALUATION))
+            throw Error("DecryptCore: EVALUATION elements of one shape expected");
+        ptrs.push_back(e ? e->data() : nullptr);
+    }
+    if (s.GetNumOfElements() < c1.GetNumOfElements() || s.GetFormat() != EVALUATION)
+        throw Error("DecryptCore: the secret key has fewer towers than the ciphertext");
+    DCRTPolyHip b(c1.GetParams(), c1.GetNumOfElements(), outFormat, c1.GetBatch());
+    check(fhe_decrypt_core(c1.GetParams()->ctx(), ptrs.data(), (uint32_t)ptrs.size(), s.data(), nullptr, c1.GetNumOfElements(), c1.GetBatch(),
+                           noise ? noise->data() : nullptr, ns, withC0 ? 1 : 0, (int)outFormat, b.data(), nullptr));
+    return b;
+}
+// PKEBFVRNS::Decrypt at sizeQl == sizeQ over the context's leading sizeQ limbs: technique 0 = BEHZ, 1 = HPS, 2 = HPSPOVERQ,
+// 3 = HPSPOVERQLEVELED; the tables of CryptoParametersBFVRNS's decryption blocks are derived by the plan (fhe_bfv_decrypt_create).
+class BfvDecrypt {
+public:
+    BfvDecrypt(std::shared_ptr<Params> params, uint32_t sizeQ, uint64_t t, int technique) : m_params(std::move(params)), m_sizeQ(sizeQ) {
+        check(fhe_bfv_decrypt_create(m_params->ctx(), nullptr, sizeQ, t, technique, &m_plan));
+    }
+    ~BfvDecrypt() { fhe_bfv_decrypt_destroy(m_plan); }
+    BfvDecrypt(const BfvDecrypt&)            = delete;
+    BfvDecrypt& operator=(const BfvDecrypt&) = delete;
+    // a derived table (ids: fhe_bfv_decrypt_table; doubles as their 64 bits); empty when the plan has none
+    std::vector<uint64_t> Table(int id) const {
+        std::vector<uint64_t> t(fhe_bfv_decrypt_table(m_plan, id, nullptr, 0));
+        fhe_bfv_decrypt_table(m_plan, id, t.data(), t.size());
+        return t;
+    }
+    // the NativePoly words modulo t, [batch][N], of `batch` EVALUATION ciphertexts of 2 to 4 elements under the secret key s
+    std::vector<uint64_t> Decrypt(const std::vector<const DCRTPolyHip*>& elements, const DCRTPolyHip& s) const {
+        if (elements.size() < 2 || !elements[0])
+            throw Error("BfvDecrypt: a ciphertext of 2 to 4 elements expected");
+        std::vector<const uint64_t*> ptrs;
+        for (const DCRTPolyHip* e : elements) {
+            if (!e || e->GetNumOfElements() != m_sizeQ || e->GetBatch() != elements[0]->GetBatch() || e->GetFormat() != EVALUATION)
+                throw Error("BfvDecrypt: EVALUATION elements over the plan's limbs expected");
+            ptrs.push_back(e->data());
+        }
+        if (s.GetNumOfElements() != m_sizeQ || s.GetFormat() != EVALUATION)
+            throw Error("BfvDecrypt: the secret key must be one EVALUATION tower over the plan's limbs");
+        const uint32_t batch = elements[0]->GetBatch();
+        return run(batch, [&](uint64_t* out, void* ws, size_t wsb) {
+            return fhe_bfv_decrypt(m_plan, ptrs.data(), (uint32_t)ptrs.size(), s.data(), batch, out, ws, wsb, nullptr);
+        });
+    }
+    // the tail alone on b [batch][sizeQ][N] in either format (MultipartyBFVRNS::MultipartyDecryptFusion after its sum); b is only read
+    std::vector<uint64_t> DecryptB(const DCRTPolyHip& b) const {
+        if (b.GetNumOfElements() != m_sizeQ)
+            throw Error("BfvDecrypt: b over the plan's limbs expected");
+        return run(b.GetBatch(), [&](uint64_t* out, void* ws, size_t wsb) {
+            return fhe_bfv_decrypt_b(m_plan, b.data(), b.GetFormat() == EVALUATION ? 1 : 0, b.GetBatch(), out, ws, wsb, nullptr);
+        });
+    }
+    fhe_bfv_dec* plan() const { return m_plan; }
+
+private:
+    template <typename Run>
+    std::vector<uint64_t> run(uint32_t batch, Run f) const {
+        fhe_ctx* c        = m_params->ctx();
+        const size_t outb = (size_t)batch * m_params->GetRingDimension() * sizeof(uint64_t), wsb = fhe_bfv_decrypt_workspace_bytes(m_plan, batch);
+        void *ws = nullptr, *out = nullptr;
+        check(fhe_malloc(c, outb, &out));
+        if (fhe_malloc(c, wsb, &ws) != FHE_OK) {
+            fhe_free(c, out);
+            throw Error(fhe_last_error());
+        }
+        std::vector<uint64_t> h(outb / sizeof(uint64_t));
+        fhe_status s = f(static_cast<uint64_t*>(out), ws, wsb);
+        if (s == FHE_OK)
+            s = fhe_memcpy_d2h(c, h.data(), out, outb, nullptr);
+        fhe_stream_sync(c, nullptr);
+        fhe_free(c, ws);
+        fhe_free(c, out);
+        check(s);
+        return h;
+    }
+    std::shared_ptr<Params> m_params;
+    uint32_t m_sizeQ;
+    fhe_bfv_dec* m_plan = nullptr;
+};
+
 }  // namespace fhehip
 #endif
