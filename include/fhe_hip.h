@@ -304,8 +304,9 @@ size_t     fhe_ks_key_words(const fhe_ks_key* key);
  *   pi_k       the index map of fhe_automorph(evalFormat = 1) for the odd index k in [1, 2N); kNew, kOld: HOST arrays [nKeys], NULL = all 1
  *              (k = 1 reads the row in place, without a gather);
  *   factor     HOST array [nParts][nLimbs], reduced modulo q_i inside.  A zero entry means "term absent": sOld is read only in rows where
- *              some digit has a non-zero factor, so it needs rows only up to the last such limb (HYBRID keys: sizeQ rows; BV keys will use
- *              the same formula with other constants);
+ *              some digit has a non-zero factor, so it needs rows only up to the last such limb (HYBRID keys: sizeQ rows).  The
+ *              secret-key forms of a BV key are this formula with the table of fhe_bv_keygen_factors (fhe_bv_keygen below); the
+ *              public-key form of a BV key is NOT: it has a kernel of its own (fhe_bv_keygen_pk);
  *   ns         GetNoiseScale(): 1 for CKKS and BFV, t for BGV; reduced modulo every limb (ns >= q_i is legal), 0 is refused.
  * out may be e itself (every word of e is read before the same word of out is written); it must not overlap e otherwise, nor a, sNew or
  * sOld.  Errors (FHE_ERR_ARG, nothing is enqueued, out untouched): a null operand, nKeys == 0, nParts == 0, an even automorphism index
@@ -959,6 +960,71 @@ size_t     fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes(const fhe_hps*
 fhe_status fhe_bfv_eval_mult_relin_hps_bv_leveled(fhe_hps* plan, const fhe_bv_key* key, const uint64_t* a0, const uint64_t* a1,
                                                   const uint64_t* b0, const uint64_t* b1, uint64_t* c0, uint64_t* c1, uint32_t sizeQlMult,
                                                   uint32_t sizeQlRelin, uint32_t batch, void* ws, size_t wsBytes, void* stream);
+
+/* ---- BV evaluation keys on the device ----------------------------------------------------------------------------------
+ * KeySwitchBV::KeySwitchGenInternal in its three overloads (src/pke/lib/keyswitch/keyswitch-bv.cpp:49-225) for nKeys keys over the context's
+ * leading sizeQ limbs with digit size baseBits.  A key has D_0 = fhe_crt_decompose_towers(ctx, NULL, sizeQ, baseBits) towers of sizeQ rows
+ * per half, in the order of DCRTPolyImpl::CRTDecompose.  Tower d, window k of limb i, carries the old secret times 2^(baseBits * k) at row
+ * i and nothing of it elsewhere (PolyImpl::PowersOfBase, src/core/include/lattice/poly-impl.h:559-571):
+ *   factor[d][i] = 2^(baseBits * k) mod q_i for that one (d, i), 0 elsewhere; baseBits == 0: one tower per limb with factor 1.
+ * fhe_bv_keygen_factors writes that table (HOST uint64_t[D_0][sizeQ], NULL = count only) and returns D_0; 0 where fhe_crt_decompose_towers
+ * returns 0.  All towers EVALUATION, canonical residues in and out.  Window `key` of devKeyB / devKeyA (D_0 * sizeQ * N words each) is what
+ * fhe_bv_key_wrap adopts.
+ *
+ * Secret-key form (:49-160; EvalMultKeyGen, EvalAutomorphismKeyGen of base-leveledshe.cpp:336-379, KeySwitchGen): ONE launch of the kernel of
+ * fhe_keygen_combine with nParts = D_0 and the table above,
+ *   devKeyB[key][d][i] = ns * e[key][d][i] - a[key][d][i] * pi_kNew[key](sNew[i]) + factor[d][i] * pi_kOld[key](sOld[i])   mod q_i.
+ *   sNew, sOld DEVICE [sizeQ][N] (no extension, no plan object); a, e, devKeyB DEVICE [nKeys][D_0][sizeQ][N]; devKeyB == e is allowed;
+ *   kNew / kOld as for fhe_ks_keygen_hybrid: EvalAutomorphismKeyGen for the index k: kNew = k^-1 mod 2N, kOld = 1; EvalMultKeyGen: (1, 1)
+ *   with sOld = s * s.  The caller supplies a, so the third overload (:105-160, MultiKeySwitchGen's reuse of another key's a vector) is this
+ *   same call with that key's a.
+ * fhe_bv_keygen_blake2 is the seeded form, the composition of fhe_ks_keygen_hybrid_blake2 over nKeys * D_0 towers of sizeQ limbs: devKeyA =
+ * the words of fhe_sample_uniform_blake2 from counterA as drawn, devKeyB = fhe_sample_gaussian_blake2 from counterE, fhe_ntt_fwd in place,
+ * the combine in place.  No workspace; five launches on a two-pass ring.
+ *
+ * Public-key form (:162-225, what PREBase::ReKeyGen, src/pke/lib/schemebase/base-pre.cpp:42-45, calls to make a proxy re-encryption key):
+ * ONE launch of keygen_pk_combine_kernel (csrc/keygen_kernels.h),
+ *   devKeyB[key][d][i] = p0[key][i] * u[key][d][i] + ns * e0[key][d][i] + factor[d][i] * sOld[i]
+ *   devKeyA[key][d][i] = p1[key][i] * u[key][d][i] + ns * e1[key][d][i]                                mod q_i.
+ *   p0, p1     the NEW public key, DEVICE [sizeQ][N] each, or with pkPerKey != 0 [nKeys][sizeQ][N] (one delegator, many delegatees);
+ *   u, e0, e1, devKeyB, devKeyA DEVICE [nKeys][D_0][sizeQ][N]; devKeyB == e0 and devKeyA == e1 are allowed (every word is read by the lane
+ *   that overwrites it); every other overlap is refused.
+ * fhe_bv_keygen_pk_blake2 is its seeded form, a composition; ws holds u, fhe_bv_keygen_workspace_bytes(ctx, sizeQ, baseBits, nKeys) bytes
+ * (nKeys * D_0 * sizeQ * N words):
+ *   u   = fhe_sample_ternary_blake2 (uDist = 0) or fhe_sample_gaussian_blake2 (uDist = 1: the reference's choice under SecretKeyDist ==
+ *         GAUSSIAN, keyswitch-bv.cpp:196-197) over nKeys * D_0 towers from counterU, into ws;
+ *   e0  = fhe_sample_gaussian_blake2 over nKeys * D_0 towers from counterE, into devKeyB;
+ *   e1  = the same from the block after e0's last one, counterE + ceil(nKeys * D_0 * N / 512), into devKeyA (N >= 512: the Gaussian
+ *         stream's very next word, so e0 ‖ e1 is one sampler call over twice the towers);
+ *   fhe_ntt_fwd over all three blocks; fhe_bv_keygen_pk in place.
+ * When devKeyA == devKeyB + nKeys * D_0 * sizeQ * N words and ws follows devKeyA likewise, that is one Gaussian call (N >= 512) and one
+ * transform call: five launches on a two-pass ring.  Otherwise one call per block.  The words are the same function of (blake2 key,
+ * counters) either way.
+ * fhe_bv_keygen_counters: blake2 counters a seeded call consumes.  form 0 (secret key): *nAorU from counterA, *nE from counterE; form 1
+ * (public key): *nAorU from counterU, *nE from counterE (e0 and e1 together).  The arithmetic of fhe_ks_keygen_counters.
+ *
+ * Errors, all detected before anything is enqueued, outputs untouched: those of fhe_keygen_combine (a null operand, nKeys == 0, an even
+ * automorphism index or one >= 2N, ns == 0, a forbidden overlap), sizeQ outside [1, limbs of the context], FHE_ERR_UNSUPPORTED for a digit
+ * size outside the device path (fhe_crt_decompose_towers == 0), sigma outside 1 < sigma < 300, an unknown uDist or form, a short workspace,
+ * ws overlapping a key block, the public key or sOld.  The factor table and ns go through the context's table cache: the first call with
+ * new ones uploads (not capturable), later calls are pure launches. */
+uint32_t   fhe_bv_keygen_factors(const fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint64_t* factor);
+fhe_status fhe_bv_keygen(fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint32_t* kNew, const uint32_t* kOld,
+                         const uint64_t* sNew, const uint64_t* sOld, uint64_t ns, const uint64_t* a, const uint64_t* e, uint64_t* devKeyB,
+                         void* stream);
+fhe_status fhe_bv_keygen_blake2(fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint32_t* kNew, const uint32_t* kOld,
+                                const uint64_t* sNew, const uint64_t* sOld, uint64_t ns, double sigma, const uint32_t key[16],
+                                uint64_t counterA, uint64_t counterE, uint64_t* devKeyB, uint64_t* devKeyA, void* stream);
+fhe_status fhe_bv_keygen_counters(const fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, int form, uint64_t* nAorU,
+                                  uint64_t* nE);
+fhe_status fhe_bv_keygen_pk(fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint64_t* p0, const uint64_t* p1,
+                            int pkPerKey, const uint64_t* sOld, uint64_t ns, const uint64_t* u, const uint64_t* e0, const uint64_t* e1,
+                            uint64_t* devKeyB, uint64_t* devKeyA, void* stream);
+size_t     fhe_bv_keygen_workspace_bytes(const fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys);
+fhe_status fhe_bv_keygen_pk_blake2(fhe_ctx* ctx, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint64_t* p0, const uint64_t* p1,
+                                   int pkPerKey, const uint64_t* sOld, int uDist, uint64_t ns, double sigma, const uint32_t key[16],
+                                   uint64_t counterU, uint64_t counterE, uint64_t* devKeyB, uint64_t* devKeyA, void* ws, size_t wsBytes,
+                                   void* stream);
 
 /* ---- BFV, HPS family, on HYBRID keys: rotations and relinearisation at dropped levels -----------------------------
  * The BFV block above with KeySwitchHYBRID (src/pke/lib/keyswitch/keyswitch-hybrid.cpp) in the middle.  Under HPSPOVERQLEVELED the reference

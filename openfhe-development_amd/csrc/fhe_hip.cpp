@@ -2952,6 +2952,232 @@ extern "C" fhe_status fhe_ks_keygen_hybrid_blake2(fhe_ks_plan* p, uint32_t nKeys
     return fhe_ks_keygen_hybrid(p, nKeys, kNew, kOld, sNewExt, sOld, ns, devKeyA, devKeyB, devKeyB, st);
 }
 
+// ---- BV evaluation keys (KeySwitchBV::KeySwitchGenInternal, keyswitch-bv.cpp:49-225) ----
+// The secret-key overloads (:49-160) are the formula of keygen_combine_kernel with the table of host::bv_keygen_factors over the context's
+// leading sizeQ limbs: no new kernel.  The public-key overload (:162-225, PREBase::ReKeyGen) is keygen_pk_combine_kernel.
+// sizeQ and the digit size, before anything else is looked at; D0 towers and their factor table [D0][sizeQ]
+static fhe_status bv_keygen_shape(const std::string& who, const fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint32_t* D0,
+                                  std::vector<uint64_t>* factor) {
+    ARG_CHECK(c, who + ": null argument");
+    ARG_CHECK(sizeQ >= 1 && sizeQ <= c->L, who + ": sizeQ must be in [1, limbs of the context]");
+    std::vector<uint64_t> f;
+    *D0 = fhe_crt_decompose_towers(c, nullptr, sizeQ, baseBits) ? host::bv_keygen_factors(c->q.data(), sizeQ, baseBits, f) : 0;
+    if (*D0 == 0)
+        return fail(FHE_ERR_UNSUPPORTED, who + ": digit size outside the device path (baseBits <= 31, every window inside the word)");
+    if (factor)
+        factor->swap(f);
+    return FHE_OK;
+}
+extern "C" uint32_t fhe_bv_keygen_factors(const fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint64_t* factor) {
+    if (!c || sizeQ < 1 || sizeQ > c->L || fhe_crt_decompose_towers(c, nullptr, sizeQ, baseBits) == 0)
+        return 0;
+    std::vector<uint64_t> f;
+    const uint32_t D0 = host::bv_keygen_factors(c->q.data(), sizeQ, baseBits, f);
+    if (factor)
+        std::copy(f.begin(), f.end(), factor);
+    return D0;
+}
+extern "C" fhe_status fhe_bv_keygen(fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint32_t* kNew,
+                                    const uint32_t* kOld, const uint64_t* sNew, const uint64_t* sOld, uint64_t ns, const uint64_t* a,
+                                    const uint64_t* e, uint64_t* devKeyB, void* st) {
+    const std::string who = "fhe_bv_keygen";
+    ARG_CHECK(c && sOld, who + ": null argument");
+    uint32_t D0 = 0;
+    std::vector<uint64_t> f;
+    if (fhe_status s = bv_keygen_shape(who, c, sizeQ, baseBits, &D0, &f))
+        return s;
+    return keygen_combine_run(who, c, nullptr, sizeQ, nKeys, D0, a, e, sNew, kNew, sOld, kOld, f.data(), ns, devKeyB, st);
+}
+extern "C" fhe_status fhe_bv_keygen_counters(const fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, int form,
+                                             uint64_t* nAorU, uint64_t* nE) {
+    const std::string who = "fhe_bv_keygen_counters";
+    ARG_CHECK(c && nAorU && nE, who + ": null argument");
+    ARG_CHECK(nKeys >= 1, who + ": nKeys must be >= 1");
+    ARG_CHECK(form == 0 || form == 1, who + ": form is 0 (secret key) or 1 (public key)");
+    uint32_t D0 = 0;
+    if (fhe_status s = bv_keygen_shape(who, c, sizeQ, baseBits, &D0, nullptr))
+        return s;
+    const uint64_t coef = ((uint64_t)nKeys * D0) << c->logN;  // coefficients of one error tower set
+    if (form == 0) {
+        *nAorU = (coef * sizeQ + 255) / 256;  // two 64-bit words per uniform residue, 512 per block
+        *nE    = (coef + 511) / 512;          // one word per Gaussian coefficient
+    } else {
+        *nAorU = (coef + 511) / 512;      // one word per coefficient of u
+        *nE    = 2 * ((coef + 511) / 512);  // e0, then e1 from the next block (N >= 512: the next word)
+    }
+    return FHE_OK;
+}
+// the seeded secret-key form: the composition of fhe_ks_keygen_hybrid_blake2 over nKeys * D0 towers of sizeQ limbs
+extern "C" fhe_status fhe_bv_keygen_blake2(fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint32_t* kNew,
+                                           const uint32_t* kOld, const uint64_t* sNew, const uint64_t* sOld, uint64_t ns, double sigma,
+                                           const uint32_t key[16], uint64_t counterA, uint64_t counterE, uint64_t* devKeyB,
+                                           uint64_t* devKeyA, void* st) {
+    const std::string who = "fhe_bv_keygen_blake2";
+    ARG_CHECK(c && sOld && key && devKeyA && devKeyB, who + ": null argument");
+    uint32_t D0 = 0;
+    std::vector<uint64_t> f;
+    if (fhe_status s = bv_keygen_shape(who, c, sizeQ, baseBits, &D0, &f))
+        return s;
+    if (fhe_status s = keygen_check(who, c, nullptr, sizeQ, nKeys, D0, devKeyA, devKeyB, sNew, kNew, sOld, kOld, sizeQ, ns, devKeyB))
+        return s;
+    ARG_CHECK(sigma > 1.000000001 && sigma < 300.0, who + ": the inversion sampler covers 1 < sigma < 300 (the reference's Peikert range)");
+    const size_t row = (size_t)c->N * 8, slab = (size_t)nKeys * D0 * sizeQ * row;
+    ARG_CHECK(!keygen_overlap(devKeyA, slab, sNew, sizeQ * row) && !keygen_overlap(devKeyA, slab, sOld, sizeQ * row),
+              who + ": devKeyA must not overlap sNew or sOld");
+    const uint32_t towers = nKeys * D0;
+    if (fhe_status s = fhe_sample_uniform_blake2(c, devKeyA, nullptr, sizeQ, towers, key, counterA, st))
+        return s;
+    if (fhe_status s = fhe_sample_gaussian_blake2(c, devKeyB, nullptr, sizeQ, towers, sigma, key, counterE, st))
+        return s;
+    if (fhe_status s = fhe_ntt_fwd(c, devKeyB, nullptr, sizeQ, towers, st))
+        return s;
+    return keygen_combine_run(who, c, nullptr, sizeQ, nKeys, D0, devKeyA, devKeyB, sNew, kNew, sOld, kOld, f.data(), ns, devKeyB, st);
+}
+static uint32_t bv_keygen_tiles(const fhe_ctx* c) { return c->logN > (uint32_t)kKeygenTileLog ? 1u << (c->logN - kKeygenTileLog) : 1u; }
+struct BvKeygenPkOperands {
+    const uint64_t *p0, *p1, *sOld, *u, *e0, *e1;
+    uint64_t *outB, *outA;
+};
+// every check of the public-key form, before anything is enqueued
+static fhe_status bv_keygen_pk_check(const std::string& who, const fhe_ctx* c, uint32_t sizeQ, uint32_t D0, uint32_t nKeys, int pkPerKey,
+                                     const BvKeygenPkOperands& o, uint64_t ns) {
+    ARG_CHECK(o.p0 && o.p1 && o.sOld && o.u && o.e0 && o.e1 && o.outB && o.outA, who + ": null argument");
+    ARG_CHECK(nKeys >= 1, who + ": nKeys must be >= 1");
+    ARG_CHECK(sizeQ <= (uint32_t)kMaxLimbs, who + ": sizeQ out of range");
+    ARG_CHECK(ns != 0, who + ": the noise scale must not be zero");
+    ARG_CHECK((uint64_t)nKeys * D0 * sizeQ * bv_keygen_tiles(c) < ((uint64_t)1 << 31), who + ": nKeys * D_0 * sizeQ too large");
+    const size_t row = (size_t)c->N * 8, slab = (size_t)nKeys * D0 * sizeQ * row, pk = (size_t)(pkPerKey ? nKeys : 1u) * sizeQ * row;
+    ARG_CHECK(!keygen_overlap(o.outB, slab, o.outA, slab), who + ": devKeyB and devKeyA overlap");
+    ARG_CHECK(o.outB == o.e0 || !keygen_overlap(o.outB, slab, o.e0, slab), who + ": devKeyB may be e0 itself but not overlap it otherwise");
+    ARG_CHECK(o.outA == o.e1 || !keygen_overlap(o.outA, slab, o.e1, slab), who + ": devKeyA may be e1 itself but not overlap it otherwise");
+    ARG_CHECK(!keygen_overlap(o.outA, slab, o.e0, slab) && !keygen_overlap(o.outB, slab, o.e1, slab),
+              who + ": devKeyB overlaps e1 or devKeyA overlaps e0");
+    for (const uint64_t* out : {o.outB, o.outA}) {
+        ARG_CHECK(!keygen_overlap(out, slab, o.u, slab), who + ": an output overlaps u");
+        ARG_CHECK(!keygen_overlap(out, slab, o.p0, pk) && !keygen_overlap(out, slab, o.p1, pk), who + ": an output overlaps the public key");
+        ARG_CHECK(!keygen_overlap(out, slab, o.sOld, sizeQ * row), who + ": an output overlaps sOld");
+    }
+    return FHE_OK;
+}
+// pieces the tower walk of keygen_pk_combine_kernel is cut into: one, unless keys x rows x tiles alone leave fewer than four workgroups
+// (16 waves) per compute unit, the filling the encrypt and decrypt combines aim at; then as many as reach it (one key at
+// N = 2^15 with 7 limbs is 112 workgroups, and the walk in 7 pieces takes half the time of the walk in one)
+static uint32_t bv_keygen_pk_pieces(const fhe_ctx* c, uint32_t sizeQ, uint32_t D0, uint32_t nKeys) {
+    const uint64_t groups = (uint64_t)nKeys * sizeQ * bv_keygen_tiles(c), want = 4ull * (c->cus ? c->cus : 256);
+    if (groups >= want)
+        return 1;
+    return (uint32_t)std::min<uint64_t>(D0, (want + groups - 1) / groups);
+}
+// (the arguments have passed bv_keygen_pk_check)
+static fhe_status bv_keygen_pk_run(const std::string& who, fhe_ctx* c, uint32_t sizeQ, uint32_t D0, const std::vector<uint64_t>& factor,
+                                   uint32_t nKeys, int pkPerKey, const BvKeygenPkOperands& o, uint64_t ns, void* st) {
+    KeygenPkArgs g;
+    if (fhe_status s = make_sel(c, nullptr, sizeQ, &g.sel, who.c_str()))
+        return s;
+    RT_CHECK(rt::set_device(c->device));
+    // the table: f[D0][sizeQ], then ns mod q_i [sizeQ] unless ns = 1 modulo every limb
+    std::vector<uint32_t> li;
+    std::vector<uint64_t> v(factor);
+    bool ns1 = true;
+    for (uint32_t i = 0; i < sizeQ; ++i)
+        ns1 = ns1 && ns % c->q[i] == 1;
+    for (uint32_t j = 0; j < D0 + (ns1 ? 0u : 1u); ++j)
+        for (uint32_t i = 0; i < sizeQ; ++i) {
+            li.push_back(i);
+            if (j == D0)
+                v.push_back(ns % c->q[i]);
+        }
+    const TwPair* table = nullptr;
+    if (fhe_status s = const_tables_trim(c))
+        return s;
+    std::shared_lock<std::shared_mutex> gate(c->constTabsGate);
+    if (fhe_status s = const_table(c, li.data(), v.data(), (uint32_t)v.size(), &table))
+        return s;
+    g.outB = o.outB, g.outA = o.outA, g.p0 = o.p0, g.p1 = o.p1, g.sOld = o.sOld, g.u = o.u, g.e0 = o.e0, g.e1 = o.e1;
+    g.lc = c->d_lc, g.tab = table, g.logN = c->logN, g.nLimbs = sizeQ, g.nParts = D0, g.nKeys = nKeys, g.pkPerKey = pkPerKey ? 1u : 0u;
+    const uint32_t pieces = bv_keygen_pk_pieces(c, sizeQ, D0, nKeys);
+    g.chunk               = (D0 + pieces - 1) / pieces;
+    g.pieces              = (D0 + g.chunk - 1) / g.chunk;
+    const uint32_t grid   = nKeys * g.pieces * sizeQ * bv_keygen_tiles(c);
+    if (ns1)
+        FHE_LAUNCH((keygen_pk_combine_kernel<true>), grid, st, g);
+    else
+        FHE_LAUNCH((keygen_pk_combine_kernel<false>), grid, st, g);
+    LAUNCH_CHECK();
+    return FHE_OK;
+}
+extern "C" fhe_status fhe_bv_keygen_pk(fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint64_t* p0, const uint64_t* p1,
+                                       int pkPerKey, const uint64_t* sOld, uint64_t ns, const uint64_t* u, const uint64_t* e0,
+                                       const uint64_t* e1, uint64_t* devKeyB, uint64_t* devKeyA, void* st) {
+    const std::string who = "fhe_bv_keygen_pk";
+    uint32_t D0           = 0;
+    std::vector<uint64_t> f;
+    if (fhe_status s = bv_keygen_shape(who, c, sizeQ, baseBits, &D0, &f))
+        return s;
+    const BvKeygenPkOperands o{p0, p1, sOld, u, e0, e1, devKeyB, devKeyA};
+    if (fhe_status s = bv_keygen_pk_check(who, c, sizeQ, D0, nKeys, pkPerKey, o, ns))
+        return s;
+    return bv_keygen_pk_run(who, c, sizeQ, D0, f, nKeys, pkPerKey, o, ns, st);
+}
+extern "C" size_t fhe_bv_keygen_workspace_bytes(const fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys) {
+    if (!c || sizeQ < 1 || sizeQ > c->L)
+        return 0;
+    return (((size_t)nKeys * fhe_crt_decompose_towers(c, nullptr, sizeQ, baseBits) * sizeQ) << c->logN) * 8;
+}
+// the seeded public-key form, a composition: u into ws, e0 into devKeyB and e1 into devKeyA from the blake2 samplers, the forward
+// transform over all of it, one combine in place.  e1's words start at the block after e0's last one, so that the three blocks may lie
+// anywhere: contiguous (devKeyB | devKeyA | ws) they take one Gaussian call and one transform call, apart one call per block, and the
+// words are the same.  Every argument is checked before the first launch.
+extern "C" fhe_status fhe_bv_keygen_pk_blake2(fhe_ctx* c, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys, const uint64_t* p0,
+                                              const uint64_t* p1, int pkPerKey, const uint64_t* sOld, int uDist, uint64_t ns, double sigma,
+                                              const uint32_t key[16], uint64_t counterU, uint64_t counterE, uint64_t* devKeyB,
+                                              uint64_t* devKeyA, void* ws, size_t wsBytes, void* st) {
+    const std::string who = "fhe_bv_keygen_pk_blake2";
+    uint32_t D0           = 0;
+    std::vector<uint64_t> f;
+    if (fhe_status s = bv_keygen_shape(who, c, sizeQ, baseBits, &D0, &f))
+        return s;
+    ARG_CHECK(key && ws, who + ": null argument");
+    uint64_t* u = (uint64_t*)ws;
+    const BvKeygenPkOperands o{p0, p1, sOld, u, devKeyB, devKeyA, devKeyB, devKeyA};
+    ARG_CHECK(devKeyB && devKeyA && p0 && p1 && sOld, who + ": null argument");
+    ARG_CHECK(nKeys >= 1, who + ": nKeys must be >= 1");
+    ARG_CHECK(sigma > 1.000000001 && sigma < 300.0, who + ": the inversion sampler covers 1 < sigma < 300 (the reference's Peikert range)");
+    ARG_CHECK(uDist == 0 || uDist == 1, who + ": uDist is 0 (ternary) or 1 (Gaussian)");
+    ARG_CHECK(wsBytes >= fhe_bv_keygen_workspace_bytes(c, sizeQ, baseBits, nKeys), who + ": workspace too small");
+    const size_t row = (size_t)c->N * 8, words = ((size_t)nKeys * D0 * sizeQ) << c->logN, slab = words * 8;
+    ARG_CHECK(!keygen_overlap(u, slab, devKeyB, slab) && !keygen_overlap(u, slab, devKeyA, slab), who + ": the workspace overlaps a key block");
+    ARG_CHECK(!keygen_overlap(u, slab, p0, (size_t)(pkPerKey ? nKeys : 1u) * sizeQ * row) &&
+                  !keygen_overlap(u, slab, p1, (size_t)(pkPerKey ? nKeys : 1u) * sizeQ * row) && !keygen_overlap(u, slab, sOld, sizeQ * row),
+              who + ": the workspace overlaps the public key or sOld");
+    if (fhe_status s = bv_keygen_pk_check(who, c, sizeQ, D0, nKeys, pkPerKey, o, ns))
+        return s;
+    const uint32_t towers  = nKeys * D0;
+    const uint64_t coef    = (uint64_t)towers << c->logN, eBlocks = (coef + 511) / 512;
+    const bool contiguous  = devKeyA == devKeyB + words && u == devKeyA + words;
+    if (fhe_status s = uDist == 0 ? fhe_sample_ternary_blake2(c, u, nullptr, sizeQ, towers, key, counterU, st)
+                                  : fhe_sample_gaussian_blake2(c, u, nullptr, sizeQ, towers, sigma, key, counterU, st))
+        return s;
+    if (contiguous && coef % 512 == 0) {
+        if (fhe_status s = fhe_sample_gaussian_blake2(c, devKeyB, nullptr, sizeQ, 2 * towers, sigma, key, counterE, st))
+            return s;
+    } else {
+        if (fhe_status s = fhe_sample_gaussian_blake2(c, devKeyB, nullptr, sizeQ, towers, sigma, key, counterE, st))
+            return s;
+        if (fhe_status s = fhe_sample_gaussian_blake2(c, devKeyA, nullptr, sizeQ, towers, sigma, key, counterE + eBlocks, st))
+            return s;
+    }
+    if (contiguous) {
+        if (fhe_status s = fhe_ntt_fwd(c, devKeyB, nullptr, sizeQ, 3 * towers, st))
+            return s;
+    } else {
+        for (uint64_t* block : {devKeyB, devKeyA, u})
+            if (fhe_status s = fhe_ntt_fwd(c, block, nullptr, sizeQ, towers, st))
+                return s;
+    }
+    return bv_keygen_pk_run(who, c, sizeQ, D0, f, nKeys, pkPerKey, o, ns, st);
+}
+
 // ---- encryption (encrypt_kernels.h) ----
 // PKERNS::EncryptZeroCore in both forms (rns-pke.cpp:111-197) with the `(*ba)[0] += plaintext` of PKERNS::Encrypt (:40-70) for any number
 // of ciphertexts: everything that is not sampling or transforming is ONE launch of encrypt_combine_kernel.  ns mod q_i goes through the

@@ -199,6 +199,32 @@ inline void mod_reduce_multi_tables(const uint64_t* qDrop, uint32_t d, const uin
         }
 }
 
+// The factor table of a BV evaluation key over moduli q[0..sizeQ) with digit size baseBits (KeySwitchBV::KeySwitchGenInternal,
+// keyswitch-bv.cpp:49-225): tower d of the key carries sOld's limb i times one power of the base at row i and nothing of sOld elsewhere,
+//   factor[d][i] = 2^(baseBits * k) mod q_i   when tower d is window k of limb i (PolyImpl::PowersOfBase, poly-impl.h:559-571),   else 0,
+// towers in the order of DCRTPolyImpl::CRTDecompose (limb 0's windows, least significant first, then limb 1's ...), ceil(GetMSB(q_i) /
+// baseBits) windows per limb; baseBits == 0: one tower per limb with factor 1.  Returns the tower count D_0 and fills factor [D_0][sizeQ];
+// 0 and an empty table outside the device path of fhe_crt_decompose_towers (baseBits > 31, a window beyond the 64-bit word, no limbs).
+inline uint32_t bv_keygen_factors(const uint64_t* q, uint32_t sizeQ, uint32_t baseBits, std::vector<uint64_t>& factor) {
+    factor.clear();
+    if (!q || sizeQ < 1 || baseBits > 31)
+        return 0;
+    std::vector<uint32_t> windows(sizeQ);
+    uint32_t towers = 0;
+    for (uint32_t i = 0; i < sizeQ; ++i) {
+        const uint32_t nBits = bitlen(q[i]);
+        windows[i]           = baseBits ? nBits / baseBits + (nBits % baseBits != 0) : 1;
+        if ((uint64_t)windows[i] * baseBits > 64)
+            return 0;
+        towers += windows[i];
+    }
+    factor.assign((size_t)towers * sizeQ, 0);
+    for (uint32_t i = 0, d = 0; i < sizeQ; ++i)
+        for (uint32_t k = 0; k < windows[i]; ++k, ++d)
+            factor[(size_t)d * sizeQ + i] = powmod(2, (uint64_t)baseBits * k, q[i]);
+    return towers;
+}
+
 }  // namespace host
 }  // namespace fhe
 #endif

@@ -251,6 +251,14 @@ class Lib:
         S("fhe_bfv_relinearize_bv", C.c_int, [vp] * 5 + [C.c_int, u32, u32, vp, vp, vp, C.c_size_t, vp])
         S("fhe_bfv_eval_mult_relin_hps_bv_leveled_workspace_bytes", C.c_size_t, [vp, u32, u32, u32, u32])
         S("fhe_bfv_eval_mult_relin_hps_bv_leveled", C.c_int, [vp] * 8 + [u32, u32, u32, vp, C.c_size_t, vp])
+        S("fhe_bv_keygen_factors", u32, [vp, u32, u32, u64p])
+        S("fhe_bv_keygen", C.c_int, [vp, u32, u32, u32, u32p, u32p, vp, vp, u64, vp, vp, vp, vp])
+        S("fhe_bv_keygen_blake2", C.c_int, [vp, u32, u32, u32, u32p, u32p, vp, vp, u64, C.c_double, u32p, u64, u64, vp, vp, vp])
+        S("fhe_bv_keygen_counters", C.c_int, [vp, u32, u32, u32, C.c_int, u64p, u64p])
+        S("fhe_bv_keygen_pk", C.c_int, [vp, u32, u32, u32, vp, vp, C.c_int, vp, u64, vp, vp, vp, vp, vp, vp])
+        S("fhe_bv_keygen_workspace_bytes", C.c_size_t, [vp, u32, u32, u32])
+        S("fhe_bv_keygen_pk_blake2", C.c_int,
+          [vp, u32, u32, u32, vp, vp, C.c_int, vp, C.c_int, u64, C.c_double, u32p, u64, u64, vp, vp, vp, C.c_size_t, vp])
         S("fhe_bfv_hybrid_create", C.c_int, [vp, vp, C.POINTER(vp)])
         S("fhe_bfv_hybrid_destroy", None, [vp])
         S("fhe_bfv_hybrid_workspace_bytes", C.c_size_t, [vp, u32, u32])
@@ -969,6 +977,113 @@ class BvKey:
             self.ctx.free(self._ws)
         self._ws = None
 
+    # ---- key generation on the device (KeySwitchBV::KeySwitchGenInternal, keyswitch-bv.cpp:49-225) ----
+    @classmethod
+    def wrap(cls, ctx, sizeQ, base_bits, dev_b, dev_a):
+        """adopt device-resident key vectors [D_0][sizeQ][N] (fhe_bv_key_wrap): the memory stays with its owner"""
+        self = cls.__new__(cls)
+        self.ctx, self.sizeQ, self.base_bits = ctx, sizeQ, base_bits
+        h = vp()
+        ctx.lib.check(ctx.lib.L.fhe_bv_key_wrap(ctx.h, sizeQ, base_bits, vp(dev_b), vp(dev_a), C.byref(h)))
+        self.h, self._ws, self._ws_bytes = h, None, 0
+        return self
+
+    @staticmethod
+    def _towers(ctx, sizeQ, base_bits):
+        """D_0; a digit size outside the device path raises the library's own error (FHE_ERR_UNSUPPORTED)"""
+        d0 = ctx.lib.L.fhe_crt_decompose_towers(ctx.h, None, sizeQ, base_bits)
+        if d0 == 0:
+            na, ne = u64(), u64()
+            ctx.lib.check(ctx.lib.L.fhe_bv_keygen_counters(ctx.h, sizeQ, base_bits, 1, 0, C.byref(na), C.byref(ne)))
+        return d0
+
+    @classmethod
+    def _wrap_keys(cls, ctx, sizeQ, base_bits, b, a, n_keys, rotations):
+        words = (b.batch // n_keys) * sizeQ * ctx.N
+        keys = [cls.wrap(ctx, sizeQ, base_bits, b.ptr.value + 8 * words * i, a.ptr.value + 8 * words * i) for i in range(n_keys)]
+        for k in keys:
+            k._keep = (b, a)  # the slabs own the memory the handles point into
+        return keys if rotations is None else dict(zip(rotations, keys))
+
+    @staticmethod
+    def _indices(ctx, n_keys, k_new, k_old, rotations):
+        if rotations is not None:
+            assert k_new is None and k_old is None and len(rotations) == n_keys
+            k_new, k_old = rotation_key_indices(ctx.lib, rotations, ctx.N)
+        kn, knp = _np_u32(k_new)
+        ko, kop = _np_u32(k_old)
+        assert (kn is None or len(kn) == n_keys) and (ko is None or len(ko) == n_keys)
+        return (kn, ko), knp, kop
+
+    @classmethod
+    def keygen(cls, ctx, base_bits, s_new, s_old, a, e, n_keys=1, k_new=None, k_old=None, ns=1, rotations=None, in_place=False,
+               stream=None):
+        """fhe_bv_keygen with the caller's a and e, Towers [n_keys * D_0][sizeQ][N] in EVALUATION format; s_new, s_old [1][sizeQ][N].
+        k_new / k_old: automorphism indices per key (None = 1), or rotations = rotation indices (rotation_key_indices).  in_place: b
+        overwrites e.  Returns (b, a, keys): the two slabs and the wrapped BvKeys, a dict by rotation index when rotations were given."""
+        sizeQ = a.n_limbs
+        assert e.batch == a.batch and e.n_limbs == sizeQ and a.batch % n_keys == 0
+        keep, knp, kop = cls._indices(ctx, n_keys, k_new, k_old, rotations)
+        b = e if in_place else e.like()
+        ctx.lib.check(ctx.lib.L.fhe_bv_keygen(ctx.h, sizeQ, base_bits, n_keys, knp, kop, s_new.ptr, s_old.ptr, ns, a.ptr, e.ptr, b.ptr,
+                                              stream))
+        return b, a, cls._wrap_keys(ctx, sizeQ, base_bits, b, a, n_keys, rotations)
+
+    @classmethod
+    def keygen_blake2(cls, ctx, base_bits, s_new, s_old, n_keys, key, counter_a, counter_e, k_new=None, k_old=None, ns=1, sigma=3.19,
+                      rotations=None, stream=None):
+        """fhe_bv_keygen_blake2: a = the uniform blake2 sampler's words from counter_a, e = the Gaussian sampler's from counter_e.
+        Returns (b, a, keys) as keygen does."""
+        sizeQ = s_new.n_limbs
+        d0 = cls._towers(ctx, sizeQ, base_bits)
+        keep, knp, kop = cls._indices(ctx, n_keys, k_new, k_old, rotations)
+        b, a = ctx.empty(n_keys * d0, sizeQ), ctx.empty(n_keys * d0, sizeQ)
+        kw = _key_words(key)
+        ctx.lib.check(ctx.lib.L.fhe_bv_keygen_blake2(ctx.h, sizeQ, base_bits, n_keys, knp, kop, s_new.ptr, s_old.ptr, ns, sigma,
+                                                     kw.ctypes.data_as(u32p), counter_a, counter_e, b.ptr, a.ptr, stream))
+        return b, a, cls._wrap_keys(ctx, sizeQ, base_bits, b, a, n_keys, rotations)
+
+    @classmethod
+    def keygen_pk(cls, ctx, base_bits, pk_b, pk_a, s_old, u, e0, e1, n_keys=1, ns=1, in_place=False, stream=None):
+        """fhe_bv_keygen_pk (the re-encryption key of PREBase::ReKeyGen): b = p0 * u + ns * e0 + factor * s_old, a = p1 * u + ns * e1 for
+        Towers u, e0, e1 [n_keys * D_0][sizeQ][N]; pk_b, pk_a [1][sizeQ][N], or [n_keys][sizeQ][N] for one public key per key.
+        in_place: b, a overwrite e0, e1.  Returns (b, a, keys)."""
+        sizeQ = u.n_limbs
+        assert e0.batch == u.batch == e1.batch and e0.n_limbs == e1.n_limbs == sizeQ and u.batch % n_keys == 0
+        assert pk_b.batch == pk_a.batch and pk_b.batch in (1, n_keys) and pk_b.n_limbs == pk_a.n_limbs == sizeQ
+        b, a = (e0, e1) if in_place else (e0.like(), e1.like())
+        ctx.lib.check(ctx.lib.L.fhe_bv_keygen_pk(ctx.h, sizeQ, base_bits, n_keys, pk_b.ptr, pk_a.ptr, 1 if pk_b.batch > 1 else 0, s_old.ptr,
+                                                 ns, u.ptr, e0.ptr, e1.ptr, b.ptr, a.ptr, stream))
+        return b, a, cls._wrap_keys(ctx, sizeQ, base_bits, b, a, n_keys, None)
+
+    @classmethod
+    def keygen_pk_blake2(cls, ctx, base_bits, pk_b, pk_a, s_old, n_keys, key, counter_u, counter_e, ns=1, sigma=3.19, u_dist=0,
+                         contiguous=True, stream=None):
+        """fhe_bv_keygen_pk_blake2: u from counter_u, e0 and e1 from counter_e of the blake2 key.  contiguous: b, a and the workspace are
+        one allocation (one Gaussian call and one transform); otherwise three.  Returns (b, a, keys): windows of one Tower that b owns
+        when contiguous."""
+        sizeQ = s_old.n_limbs
+        d0 = cls._towers(ctx, sizeQ, base_bits)
+        assert pk_b.batch == pk_a.batch and pk_b.batch in (1, n_keys) and pk_b.n_limbs == pk_a.n_limbs == sizeQ
+        wsb = ctx.lib.L.fhe_bv_keygen_workspace_bytes(ctx.h, sizeQ, base_bits, n_keys)
+        if contiguous:
+            slab = ctx.empty(3 * n_keys * d0, sizeQ)
+            b, a, ws = _window(slab, 0, n_keys * d0), _window(slab, n_keys * d0, n_keys * d0), vp(slab.ptr.value + 2 * wsb)
+            b._keep = a._keep = slab
+        else:
+            b, a, spare = ctx.empty(n_keys * d0, sizeQ), ctx.empty(n_keys * d0, sizeQ), ctx.malloc(wsb + 16)
+            ws = vp(spare.value + 16) if spare.value == a.ptr.value + wsb and a.ptr.value == b.ptr.value + wsb else spare
+        kw = _key_words(key)
+        try:
+            ctx.lib.check(ctx.lib.L.fhe_bv_keygen_pk_blake2(ctx.h, sizeQ, base_bits, n_keys, pk_b.ptr, pk_a.ptr, 1 if pk_b.batch > 1 else 0,
+                                                            s_old.ptr, u_dist, ns, sigma, kw.ctypes.data_as(u32p), counter_u, counter_e,
+                                                            b.ptr, a.ptr, ws, wsb, stream))
+            ctx.sync(stream)
+        finally:
+            if not contiguous:
+                ctx.free(spare)
+        return b, a, cls._wrap_keys(ctx, sizeQ, base_bits, b, a, n_keys, None)
+
     def digits(self, sizeQl):
         """D_l: towers of CRTDecompose(base_bits) at level sizeQl (the first D_l towers of the key)"""
         return self.ctx.lib.L.fhe_crt_decompose_towers(self.ctx.h, None, sizeQl, self.base_bits)
@@ -1027,6 +1142,28 @@ def rotation_key_indices(lib, rotations, N):
     the permuted one (kNew = k^-1 mod 2N) and the old one is s itself (kOld = 1)"""
     ks = [lib.find_automorphism_index(int(r), 2 * N) for r in rotations]
     return np.array([pow(k, -1, 2 * N) for k in ks], np.uint32), np.ones(len(ks), np.uint32)
+
+
+SECRET_KEY_FORM, PUBLIC_KEY_FORM = 0, 1  # form of bv_keygen_counters
+
+
+def bv_keygen_counters(ctx, sizeQ, base_bits, n_keys, form=SECRET_KEY_FORM):
+    """(blake2 counters a seeded BV key generation consumes from counter_a or counter_u, from counter_e) (fhe_bv_keygen_counters)"""
+    n0, ne = u64(), u64()
+    ctx.lib.check(ctx.lib.L.fhe_bv_keygen_counters(ctx.h, sizeQ, base_bits, n_keys, form, C.byref(n0), C.byref(ne)))
+    return n0.value, ne.value
+
+
+def bv_keygen_factors(qs, base_bits):
+    """The factor table of a BV key with plain integers: rows = towers in the order of CRTDecompose (limb 0's windows, least significant
+    first, then limb 1's ...), factor[d][i] = 2^(base_bits * k) mod q_i when tower d is window k of limb i, else 0; base_bits == 0: one
+    tower per limb with factor 1 (host::bv_keygen_factors, csrc/host_math.h)"""
+    qs = [int(q) for q in qs]
+    rows = []
+    for i, q in enumerate(qs):
+        for k in range(-(-q.bit_length() // base_bits) if base_bits else 1):
+            rows.append([pow(2, base_bits * k, q) if j == i else 0 for j in range(len(qs))])
+    return rows
 
 
 def keygen_combine(ctx, a, e, s_new, n_keys=1, k_new=None, s_old=None, k_old=None, factor=None, ns=1, out=None, stream=None):

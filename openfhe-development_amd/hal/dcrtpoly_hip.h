@@ -1084,6 +1084,114 @@ inline std::unique_ptr<HybridKeySet> KeyGenHybridBlake2(KeySwitchHybrid& ks, uin
     return std::make_unique<HybridKeySet>(ks.plan(), std::move(b), std::move(a), nKeys);
 }
 
+// ---- BV evaluation keys made on the device (KeySwitchBV::KeySwitchGenInternal, keyswitch-bv.cpp:49-225) ----
+// The two halves of a key set, [nKeys * D_0][sizeQ][N] each in EVALUATION format, and one handle per key that fhe_bv_key_wrap laid over
+// its window of them: what fhe_keyswitch_bv, fhe_bv_eval_fast_rotation and the BFV composites on BV keys take as `key`.  The halves live
+// in `slabs` (two towers, or one that holds b | a | workspace for the seeded public-key form); the handles die with the set.
+struct BvKeySet {
+    std::vector<DCRTPolyHip> slabs;
+    uint64_t *b = nullptr, *a = nullptr;
+    size_t halfWords = 0;
+    std::vector<fhe_bv_key*> keys;
+    BvKeySet(std::vector<DCRTPolyHip>&& s, uint64_t* b_, uint64_t* a_, uint32_t sizeQ, uint32_t baseBits, uint32_t nKeys)
+        : slabs(std::move(s)), b(b_), a(a_) {
+        fhe_ctx* ctx       = slabs[0].GetParams()->ctx();
+        const size_t words = (size_t)fhe_crt_decompose_towers(ctx, nullptr, sizeQ, baseBits) * sizeQ * slabs[0].GetRingDimension();
+        halfWords          = words * nKeys;
+        for (uint32_t k = 0; k < nKeys; ++k) {
+            fhe_bv_key* h = nullptr;
+            check(fhe_bv_key_wrap(ctx, sizeQ, baseBits, b + k * words, a + k * words, &h));
+            keys.push_back(h);
+        }
+    }
+    ~BvKeySet() {
+        for (auto* k : keys)
+            fhe_bv_key_destroy(k);
+    }
+    BvKeySet(const BvKeySet&)            = delete;
+    BvKeySet& operator=(const BvKeySet&) = delete;
+    std::vector<uint64_t> GetValues(int half) const {  // [nKeys * D_0][sizeQ][N] of b (0) or a (1)
+        std::vector<uint64_t> out(halfWords);
+        fhe_ctx* ctx = slabs[0].GetParams()->ctx();
+        check(fhe_memcpy_d2h(ctx, out.data(), half ? a : b, halfWords * 8, nullptr));
+        check(fhe_stream_sync(ctx, nullptr));
+        return out;
+    }
+};
+inline std::unique_ptr<BvKeySet> MakeBvKeySet(DCRTPolyHip&& b, DCRTPolyHip&& a, uint32_t baseBits, uint32_t nKeys) {
+    const uint32_t sizeQ = b.GetNumOfElements();
+    uint64_t *pb = b.data(), *pa = a.data();
+    std::vector<DCRTPolyHip> slabs;
+    slabs.push_back(std::move(b)), slabs.push_back(std::move(a));
+    return std::make_unique<BvKeySet>(std::move(slabs), pb, pa, sizeQ, baseBits, nKeys);
+}
+// the secret-key form (:49-160) from the caller's a and e (both [nKeys * D_0][sizeQ][N], EVALUATION); e's buffer becomes b.  Key k
+// switches sigma_kOld[k](sOld) to sigma_kNew[k](sNew), as in KeyGenHybrid; a taken from another key is MultiKeySwitchGen's overload.
+inline std::unique_ptr<BvKeySet> KeyGenBv(uint32_t baseBits, const DCRTPolyHip& sNew, const DCRTPolyHip& sOld, const std::vector<uint32_t>& kNew,
+                                          const std::vector<uint32_t>& kOld, uint64_t ns, DCRTPolyHip&& a, DCRTPolyHip&& e) {
+    if (kNew.empty() || kNew.size() != kOld.size())
+        throw Error("KeyGenBv: one automorphism index pair per key");
+    check(fhe_bv_keygen(sNew.GetParams()->ctx(), sNew.GetNumOfElements(), baseBits, (uint32_t)kNew.size(), kNew.data(), kOld.data(),
+                        sNew.data(), sOld.data(), ns, a.data(), e.data(), e.data(), nullptr));
+    return MakeBvKeySet(std::move(e), std::move(a), baseBits, (uint32_t)kNew.size());
+}
+// the seeded form (fhe_bv_keygen_blake2); *nextA / *nextE: the first counters the call did not use (fhe_bv_keygen_counters)
+inline std::unique_ptr<BvKeySet> KeyGenBvBlake2(uint32_t baseBits, const DCRTPolyHip& sNew, const DCRTPolyHip& sOld,
+                                                const std::vector<uint32_t>& kNew, const std::vector<uint32_t>& kOld, uint64_t ns, double sigma,
+                                                const uint32_t key[16], uint64_t counterA, uint64_t counterE, uint64_t* nextA = nullptr,
+                                                uint64_t* nextE = nullptr) {
+    if (kNew.empty() || kNew.size() != kOld.size())
+        throw Error("KeyGenBvBlake2: one automorphism index pair per key");
+    const uint32_t nKeys = (uint32_t)kNew.size(), sizeQ = sNew.GetNumOfElements();
+    const auto& params   = sNew.GetParams();
+    uint64_t nA = 0, nE = 0;
+    check(fhe_bv_keygen_counters(params->ctx(), sizeQ, baseBits, nKeys, 0, &nA, &nE));  // (refuses what the key generation would)
+    const uint32_t towers = nKeys * fhe_crt_decompose_towers(params->ctx(), nullptr, sizeQ, baseBits);
+    DCRTPolyHip b(params, sizeQ, EVALUATION, towers), a(params, sizeQ, EVALUATION, towers);
+    check(fhe_bv_keygen_blake2(params->ctx(), sizeQ, baseBits, nKeys, kNew.data(), kOld.data(), sNew.data(), sOld.data(), ns, sigma, key,
+                               counterA, counterE, b.data(), a.data(), nullptr));
+    if (nextA)
+        *nextA = counterA + nA;
+    if (nextE)
+        *nextE = counterE + nE;
+    return MakeBvKeySet(std::move(b), std::move(a), baseBits, nKeys);
+}
+// the public-key form (:162-225, PREBase::ReKeyGen) from the caller's u, e0, e1 ([nKeys * D_0][sizeQ][N], EVALUATION); e0's and e1's
+// buffers become b and a.  p0, p1: the new public key, [1][sizeQ][N], or [nKeys][sizeQ][N] for one public key per key.
+inline std::unique_ptr<BvKeySet> KeyGenBvPk(uint32_t baseBits, uint32_t nKeys, const DCRTPolyHip& p0, const DCRTPolyHip& p1,
+                                            const DCRTPolyHip& sOld, uint64_t ns, const DCRTPolyHip& u, DCRTPolyHip&& e0, DCRTPolyHip&& e1) {
+    if (p0.GetBatch() != p1.GetBatch() || (p0.GetBatch() != 1 && p0.GetBatch() != nKeys))
+        throw Error("KeyGenBvPk: one public key, or one per key");
+    check(fhe_bv_keygen_pk(sOld.GetParams()->ctx(), sOld.GetNumOfElements(), baseBits, nKeys, p0.data(), p1.data(), p0.GetBatch() > 1 ? 1 : 0,
+                           sOld.data(), ns, u.data(), e0.data(), e1.data(), e0.data(), e1.data(), nullptr));
+    return MakeBvKeySet(std::move(e0), std::move(e1), baseBits, nKeys);
+}
+// its seeded form (fhe_bv_keygen_pk_blake2) in one slab b | a | workspace: one Gaussian call and one transform call; gaussianU: u from the
+// Gaussian sampler (SecretKeyDist == GAUSSIAN); *nextU / *nextE: the first counters the call did not use
+inline std::unique_ptr<BvKeySet> KeyGenBvPkBlake2(uint32_t baseBits, uint32_t nKeys, const DCRTPolyHip& p0, const DCRTPolyHip& p1,
+                                                  const DCRTPolyHip& sOld, bool gaussianU, uint64_t ns, double sigma, const uint32_t key[16],
+                                                  uint64_t counterU, uint64_t counterE, uint64_t* nextU = nullptr,
+                                                  uint64_t* nextE = nullptr) {
+    if (p0.GetBatch() != p1.GetBatch() || (p0.GetBatch() != 1 && p0.GetBatch() != nKeys))
+        throw Error("KeyGenBvPkBlake2: one public key, or one per key");
+    const auto& params   = sOld.GetParams();
+    const uint32_t sizeQ = sOld.GetNumOfElements();
+    uint64_t nU = 0, nE = 0;
+    check(fhe_bv_keygen_counters(params->ctx(), sizeQ, baseBits, nKeys, 1, &nU, &nE));
+    const uint32_t towers = nKeys * fhe_crt_decompose_towers(params->ctx(), nullptr, sizeQ, baseBits);
+    std::vector<DCRTPolyHip> slabs;
+    slabs.emplace_back(params, sizeQ, EVALUATION, 3 * towers);
+    const size_t wsb = fhe_bv_keygen_workspace_bytes(params->ctx(), sizeQ, baseBits, nKeys);
+    uint64_t* b      = slabs[0].data();
+    check(fhe_bv_keygen_pk_blake2(params->ctx(), sizeQ, baseBits, nKeys, p0.data(), p1.data(), p0.GetBatch() > 1 ? 1 : 0, sOld.data(),
+                                  gaussianU ? 1 : 0, ns, sigma, key, counterU, counterE, b, b + wsb / 8, b + 2 * (wsb / 8), wsb, nullptr));
+    if (nextU)
+        *nextU = counterU + nU;
+    if (nextE)
+        *nextE = counterE + nE;
+    return std::make_unique<BvKeySet>(std::move(slabs), b, b + wsb / 8, sizeQ, baseBits, nKeys);
+}
+
 // ---- encryption on the device (PKERNS::EncryptZeroCore + Encrypt, rns-pke.cpp:40-70, 111-197; PKEBFVRNS::Encrypt, bfvrns-pke.cpp:99-213)
 // All towers over the leading context limbs.  The key towers may have more rows than the plaintext's level: their first rows are used.
 // `batch` fresh ciphertexts in one slab [2][batch][sizeQl][N], EVALUATION: the c0 block, then the c1 block (what the seeded calls fill).
